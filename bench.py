@@ -15,9 +15,15 @@ all_gathers of the per-frame outputs (keypoint and match counts, vnMatches12 row
 
 Prints ONE JSON line on rank 0 (contract in the task statement):
   value = all ranks' frames / max-over-ranks wall time of K steps,
-  roofline = dominant kernel, algorithmic bytes / HIP-event duration (on the stream the
-             kernels run on) vs 8 TB/s HBM,
+  ms_per_step = that wall time / K, per B frames per GPU.
+A plain run does only that: set up, warm up, time the K steps, print the line.  `--full` adds
+the legs that take runs of their own (`--no-kernel-timing` / `--no-cpu` drop one of them):
+  roofline, kernels = dominant / every kernel, algorithmic bytes / HIP-event duration (on the
+             stream the kernels run on, a second, serial pass of K steps) vs 8 TB/s HBM,
   cpu_baseline = the oracle (C restatement, "port") on a bounded sample on host cores.
+`--dump-outputs DIR` writes what the last timed step computed (dump_outputs below) as
+DIR/<name>.npy; the inputs are seeded, so two builds run with the same arguments can be
+compared array for array.
 """
 import argparse
 import json
@@ -235,6 +241,62 @@ def cpu_baseline(frames, threads, nframes, nframes_1core=32):
                        % (nframes, threads, dt, nframes_1core, dt1))}
 
 
+DUMP_UNITS = 64   # frames / pairs of the last step whose per-keypoint arrays are dumped
+DUMP_SEED = 376    # of the sample (fixed: the same units in every run)
+
+
+def dump_outputs(path, ext, bstep, mode, B):
+    """--dump-outputs: what the last timed step left for its caller, as float32 / float64
+    DIR/<name>.npy (every value is an integer below 2^24 or already a float, so float32
+    holds it exactly).  The per-frame arrays are whole: the summary BenchStep fills (mono:
+    keypoints of the B + 1 images, then SearchForInitialization matches of the B pairs;
+    stereo: left keypoints, then depths of the B pairs), the vnMatches12 rows and the pose
+    stub's rows.  The per-keypoint arrays (orbg_batch_outputs, orbg_match_outputs,
+    orbg_stereo_outputs) would be several hundred MB, so they are dumped for a fixed, seeded
+    sample of DUMP_UNITS units (mono: pair p = images p, p + 1, the image dumped is p + 1;
+    stereo: pair p = images 2p, 2p + 1, both dumped), rows padded with 0 to frame_cap."""
+    ext.ctx.sync()
+    os.makedirs(path, exist_ok=True)
+    fc = ext.batch_outputs()[3]
+    units = np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=min(DUMP_UNITS, B),
+                                                            replace=False))
+    imgs = {"mono": units + 1, "extract": units,
+            "stereo": np.stack([2 * units, 2 * units + 1], 1).reshape(-1)}[mode]
+    out = {"sample_units": units.astype(np.float32), "sample_images": imgs.astype(np.float32)}
+    cnt = np.zeros(len(imgs), np.float32)
+    kps = np.zeros((len(imgs), fc, 7), np.float32)
+    desc = np.zeros((len(imgs), fc, 32), np.float32)
+    for i, f in enumerate(imgs):
+        k, d = ext.download_frame(int(f))
+        cnt[i] = len(k)
+        for j, name in enumerate(k.dtype.names):
+            kps[i, :len(k), j] = k[name]
+        desc[i, :len(k)] = d
+    out.update(keypoint_counts=cnt, keypoints=kps, descriptors=desc)
+    if mode == "mono":
+        out["summary"] = bstep.summary.cpu().numpy().astype(np.float32)
+        out["matches12"] = bstep.m12.cpu().numpy().astype(np.float32)
+        knn = np.zeros((len(units), fc, 3), np.float32)
+        for i, p in enumerate(units):  # knn2 rows: one per keypoint of the pair's image p + 1
+            n = int(cnt[i])
+            knn[i, :n] = ext.download_matches(int(p), n)[0]
+        out["knn2"] = knn
+        if bstep.pose is not None:
+            out["pose"] = bstep.pose.cpu().numpy().astype(np.float64)
+    elif mode == "stereo":
+        out["stereo_summary"] = bstep.ssum.cpu().numpy().astype(np.float32)
+        ur = np.zeros((len(units), fc), np.float32)
+        dp = np.zeros((len(units), fc), np.float32)
+        for i, p in enumerate(units):  # one row per keypoint of the pair's left image
+            n = int(cnt[2 * i])
+            ur[i, :n], dp[i, :n], _ = ext.download_stereo(int(p), n)
+        out.update(uright=ur, depth=dp)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    total = sum(a.nbytes for a in out.values())
+    print("dumped %d arrays, %.1f MB, to %s" % (len(out), total / 1e6, path), file=sys.stderr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -253,8 +315,17 @@ def main():
                     help="0: the host CPUs this process may run on (os.sched_getaffinity), "
                          "capped at the lease's CPU share (OMP_NUM_THREADS, 16 on a 1-GPU box)")
     ap.add_argument("--cpu-frames", type=int, default=0, help="0: 256 x threads (~10-20 s)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: "
+                         "the serial per-kernel HIP-event pass (`kernels`, `roofline`) and the "
+                         "CPU baseline (`cpu_baseline`); a plain run leaves them null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32 / "
+                         "float64, under 64 MB: whole per-frame arrays, per-keypoint arrays of "
+                         "a fixed seeded sample of frames); rank 0 writes its own block's")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true",
+                    help="with --full: no serial per-kernel pass")
     ap.add_argument("--pipeline", type=int, default=int(os.environ.get("ORBG_PIPELINE", "1")),
                     help="1: pipelined batches (image half of step k+1 beside the keypoint half "
                          "of step k, orbg_set_pipeline); 0: one batch after the other")
@@ -431,13 +502,15 @@ def main():
         e = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
         elapsed = float(e.item())
+    if args.dump_outputs and rank == 0:  # before --full's serial pass runs further steps
+        dump_outputs(args.dump_outputs, ext, bstep, mode, B)
     # per-kernel HIP event times (roofline): a second pass of the same K steps, so that the
     # events recorded around every launch (~5% of a step) stay out of `value`.  It runs
     # serially (orbg_set_serial, the matching after the extraction): in the timed pass the
     # kernels of two batches and three streams overlap, and an event pair around a kernel
     # would time its neighbours too.
     kern = {}
-    if not args.no_kernel_timing and not args.host_input:
+    if args.full and not args.no_kernel_timing and not args.host_input:
         ext.ctx.set_serial(True)
 
         def step_serial():
@@ -474,7 +547,7 @@ def main():
         # fractions of the chip's VALU issue / LDS cycles each kernel used
         pmc = os.path.join(ROOT, "profiles", PMC_STEREO if args.stereo else PMC_MONO)
         pmc_all = {}
-        if os.path.exists(pmc) and not args.extract_only:
+        if kern and os.path.exists(pmc) and not args.extract_only:
             with open(pmc) as f:
                 pmc_all = json.load(f)
         def pmc_hbm(name, lps):
@@ -574,13 +647,14 @@ def main():
             "candidates_per_image": round(ncand / nimg, 1),
             "keypoints_per_image": round(nkp / nimg, 1),
         }
-        if world == 1 and not args.no_cpu and args.stereo:
+        with_cpu = args.full and world == 1 and not args.no_cpu
+        if with_cpu and args.stereo:
             out["cpu_baseline"] = cpu_baseline_stereo(lefts, rights, args.cpu_threads,
                                                       args.cpu_frames or 32 * args.cpu_threads)
-        elif world == 1 and not args.no_cpu and args.extract_only:
+        elif with_cpu and args.extract_only:
             out["cpu_baseline"] = cpu_baseline_extract(frames, args.cpu_threads,
                                                        args.cpu_frames or 256 * args.cpu_threads)
-        elif world == 1 and not args.no_cpu:
+        elif with_cpu:
             n = args.cpu_frames or 256 * args.cpu_threads
             out["cpu_baseline"] = cpu_baseline(frames, args.cpu_threads, n)
         else:

@@ -10,7 +10,7 @@ mkdir -p $O
 for r in $(seq 1 $R); do
   for v in "$@"; do
     if [ "$v" = default ]; then unset ORBG_LIB_VARIANT; else export ORBG_LIB_VARIANT=$v; fi
-    timeout -k 10 120 python bench.py --steps 30 --warmup 5 --no-cpu > $O/b.json 2> $O/b.err
+    timeout -k 10 120 python bench.py --full --steps 30 --warmup 5 --no-cpu > $O/b.json 2> $O/b.err
     echo "$r $v $(python -c 'import json;d=json.load(open("'$O'/b.json"));print(d["ms_per_step"], {k:round(v["ms_per_step"],4) for k,v in d["kernels"].items()})')"
   done
 done

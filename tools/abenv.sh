@@ -13,7 +13,7 @@ for r in $(seq 1 $R); do
     name=${spec%%:*}; rest=${spec#*:}; var=""
     if [[ "$rest" == *@* ]]; then var=${rest##*@}; rest=${rest%@*}; fi
     envs=$(echo "$rest" | tr ',' ' ')
-    env $envs ${var:+ORBG_LIB_VARIANT=$var} timeout -k 10 120 python bench.py --steps 30 --warmup 5 --no-cpu > $O/b.json 2> $O/b.err
+    env $envs ${var:+ORBG_LIB_VARIANT=$var} timeout -k 10 120 python bench.py --full --steps 30 --warmup 5 --no-cpu > $O/b.json 2> $O/b.err
     echo "$r $name $(python -c 'import json;d=json.load(open("'$O'/b.json"));print(d["ms_per_step"], {k:round(v["ms_per_step"],4) for k,v in d["kernels"].items()})')"
   done
 done

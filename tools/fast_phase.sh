@@ -8,6 +8,6 @@ O=gpurun_out/${1:-fastphase}
 V=${2:-dev}
 mkdir -p $O
 for d in 11 14 12 13 0; do
-  ORBG_LIB_VARIANT=$V ORBG_DBG=$d timeout -k 10 120 python bench.py --extract-only --steps 20 --warmup 3 --no-cpu > $O/p$d.json 2> $O/p$d.err
+  ORBG_LIB_VARIANT=$V ORBG_DBG=$d timeout -k 10 120 python bench.py --full --extract-only --steps 20 --warmup 3 --no-cpu > $O/p$d.json 2> $O/p$d.err
   echo "dbg $d fast_cells $(python3 -c 'import json;d=json.load(open("'$O'/p'$d'.json"));print(d["kernels"]["fast_cells"]["ms_per_step"])')"
 done

@@ -9,10 +9,10 @@ O=gpurun_out/${1:-frphase}
 V=${2:-dev}
 mkdir -p $O
 for d in 31 32 33 34 0; do
-  ORBG_FAST_ROWS=1 ORBG_LIB_VARIANT=$V ORBG_DBG=$d timeout -k 10 120 python bench.py --extract-only --steps 20 --warmup 3 --no-cpu > $O/p$d.json 2> $O/p$d.err
+  ORBG_FAST_ROWS=1 ORBG_LIB_VARIANT=$V ORBG_DBG=$d timeout -k 10 120 python bench.py --full --extract-only --steps 20 --warmup 3 --no-cpu > $O/p$d.json 2> $O/p$d.err
   echo "dbg $d fast_cells $(python3 -c 'import json;d=json.load(open("'$O'/p'$d'.json"));print(d["kernels"]["fast_cells"]["ms_per_step"])')"
 done
-ORBG_FAST_ROWS=0 timeout -k 10 120 python bench.py --extract-only --steps 20 --warmup 3 --no-cpu > $O/old.json 2> $O/old.err
+ORBG_FAST_ROWS=0 timeout -k 10 120 python bench.py --full --extract-only --steps 20 --warmup 3 --no-cpu > $O/old.json 2> $O/old.err
 echo "k_fast2 fast_cells $(python3 -c 'import json;d=json.load(open("'$O'/old.json"));print(d["kernels"]["fast_cells"]["ms_per_step"], d["ms_per_step"])')"
-ORBG_FAST_ROWS=1 timeout -k 10 120 python bench.py --extract-only --steps 20 --warmup 3 --no-cpu > $O/new.json 2> $O/new.err
+ORBG_FAST_ROWS=1 timeout -k 10 120 python bench.py --full --extract-only --steps 20 --warmup 3 --no-cpu > $O/new.json 2> $O/new.err
 echo "k_fast_rows fast_cells $(python3 -c 'import json;d=json.load(open("'$O'/new.json"));print(d["kernels"]["fast_cells"]["ms_per_step"], d["ms_per_step"])')"

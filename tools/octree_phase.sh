@@ -10,6 +10,6 @@ O=gpurun_out/${1:-octphase}
 V=${2:-dev}
 mkdir -p $O
 for d in 1 2 3 4 0 21 22; do
-  ORBG_LIB_VARIANT=$V ORBG_DBG=$d timeout -k 10 120 python bench.py --extract-only --steps 20 --warmup 3 --no-cpu > $O/p$d.json 2> $O/p$d.err
+  ORBG_LIB_VARIANT=$V ORBG_DBG=$d timeout -k 10 120 python bench.py --full --extract-only --steps 20 --warmup 3 --no-cpu > $O/p$d.json 2> $O/p$d.err
   echo "dbg $d $(python3 -c 'import json;d=json.load(open("'$O'/p'$d'.json"));k=d["kernels"];print(" ".join("%s %.4f"%(n,k[n]["ms_per_step"]) for n in ("octree","octree_big","orient_desc") if n in k))')"
 done

@@ -8,6 +8,6 @@ O=gpurun_out/${1:-orientphase}
 V=${2:-dev}
 mkdir -p $O
 for d in 21 22 0; do
-  ORBG_LIB_VARIANT=$V ORBG_DBG=$d timeout -k 10 120 python bench.py --extract-only --steps 20 --warmup 3 --no-cpu > $O/p$d.json 2> $O/p$d.err
+  ORBG_LIB_VARIANT=$V ORBG_DBG=$d timeout -k 10 120 python bench.py --full --extract-only --steps 20 --warmup 3 --no-cpu > $O/p$d.json 2> $O/p$d.err
   echo "dbg $d orient_desc $(python3 -c 'import json;d=json.load(open("'$O'/p'$d'.json"));print(d["kernels"]["orient_desc"]["ms_per_step"])')"
 done

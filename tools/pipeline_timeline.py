@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""One pipelined bench.py step from a rocprofv3 kernel trace: every dispatch between two
+"""One pipelined bench.py --full step from a rocprofv3 kernel trace: every dispatch between two
 consecutive `resize` (k_pyramid) starts of the timed pass, by stream, relative to the step
 start, and each stream's busy time (union of its dispatches) over the step -- which stream's
 chain the step waits on.  The timed pass is the trace's dispatches before bench.py's serial

@@ -2,7 +2,7 @@
 # Kernel trace + PMC passes of one python workload (bench.py, tools/ba_bench.py, ...):
 #   gpurun --timeout 1200 -- bash tools/profile.sh <tag> <script.py> [args]
 # 1. rocprofv3 --kernel-trace --stats of `script args` (the committed *_kernel_stats.md,
-#    *_kernel_phase.md for bench.py: its pipelined timed pass vs its serial timing pass);
+#    *_kernel_phase.md for bench.py --full: its pipelined timed pass vs its serial timing pass);
 # 2. one rocprofv3 --pmc run per counter group (never combined with tracing) of
 #    `script args $PMC_ARGS`.  For bench.py pass PMC_ARGS="--serial --steps 3 --warmup 1
 #    --no-kernel-timing": every kernel then runs as one dispatch per step on one stream, so

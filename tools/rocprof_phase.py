@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Per-kernel launch durations of a rocprofv3 kernel trace of bench.py, split into the timed
-(pipelined) pass and the serial kernel-timing pass that follows it (bench.py runs the
+"""Per-kernel launch durations of a rocprofv3 kernel trace of bench.py --full, split into the
+timed (pipelined) pass and the serial kernel-timing pass that follows it (bench.py runs the
 serial pass last, `steps` steps, so each kernel's last steps x launches_per_step dispatches
 are the serial ones).  The serial averages are the ones bench.py's roofline quotes.
 

@@ -10,13 +10,13 @@ echo "[final] pytest -m gpu"
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread > $O/pytest_gpu.log 2>&1 || { tail -40 $O/pytest_gpu.log; exit 1; }
 tail -2 $O/pytest_gpu.log
 echo "[final] bench (C3 mono)"
-timeout -k 10 300 python bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 300 python bench.py --full > $O/bench.json 2> $O/bench.err
 python3 -c "import json;d=json.load(open('$O/bench.json'));print(d['value'],d['ms_per_step'],d['cpu_baseline']['value'],d['cpu_baseline']['value_1core'])"
 echo "[final] bench --extract-only (C2)"
-timeout -k 10 300 python bench.py --extract-only > $O/c2.json 2> $O/c2.err
+timeout -k 10 300 python bench.py --full --extract-only > $O/c2.json 2> $O/c2.err
 python3 -c "import json;d=json.load(open('$O/c2.json'));print(d['value'],d['ms_per_step'],d['cpu_baseline']['value'],d['cpu_baseline']['value_1core'])"
 echo "[final] bench --stereo (C4)"
-timeout -k 10 300 python bench.py --stereo > $O/stereo.json 2> $O/stereo.err
+timeout -k 10 300 python bench.py --full --stereo > $O/stereo.json 2> $O/stereo.err
 python3 -c "import json;d=json.load(open('$O/stereo.json'));print(d['value'],d['ms_per_step'],d['cpu_baseline']['value'],d['cpu_baseline']['value_1core'])"
 echo "[final] bench --host-input (C3 fed from pinned host memory)"
 timeout -k 10 300 python bench.py --host-input --no-cpu > $O/host.json 2> $O/host.err

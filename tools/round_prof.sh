@@ -9,8 +9,8 @@ mkdir -p $O
 SER="--serial --steps 3 --warmup 1 --no-kernel-timing --no-cpu"
 echo "[prof] mono"
 PMC_ARGS="$SER" PMC_STEPS=4 timeout -k 10 560 bash tools/profile.sh ${TAG}_prof bench.py \
-    --steps 10 --warmup 3 --no-cpu > $O/profile.log 2>&1 || { tail -20 $O/profile.log; exit 1; }
+    --full --steps 10 --warmup 3 --no-cpu > $O/profile.log 2>&1 || { tail -20 $O/profile.log; exit 1; }
 echo "[prof] stereo"
 PMC_ARGS="$SER" PMC_STEPS=4 timeout -k 10 560 bash tools/profile.sh ${TAG}_sprof bench.py \
-    --stereo --steps 10 --warmup 3 --no-cpu > $O/sprofile.log 2>&1 || { tail -20 $O/sprofile.log; exit 1; }
+    --full --stereo --steps 10 --warmup 3 --no-cpu > $O/sprofile.log 2>&1 || { tail -20 $O/sprofile.log; exit 1; }
 echo "[prof] done"
