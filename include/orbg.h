@@ -36,6 +36,14 @@
  *   orbg_bow_transform .............. TemplatedVocabulary::transform(features, BowVector,
  *                                     FeatureVector, levelsup) as Frame::ComputeBoW calls it
  *                                     TemplatedVocabulary.h:1126-1189, 1220-1259; Frame.cc:532-539
+ *   orbg_bow_score .................. TemplatedVocabulary::score = L1Scoring::score
+ *                                     Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68
+ *   orbg_kfdb_add / _erase / _clear . KeyFrameDatabase::add / erase / clear
+ *                                     src/KeyFrameDatabase.cc:50-83
+ *   orbg_kfdb_detect_reloc .......... KeyFrameDatabase::DetectRelocalizationCandidates
+ *                                     src/KeyFrameDatabase.cc:291-419 (Tracking.cc:1958)
+ *   orbg_kfdb_detect_loop ........... KeyFrameDatabase::DetectLoopCandidates
+ *                                     src/KeyFrameDatabase.cc:106-274 (LoopClosing.cc:162-212)
  *   orbg_search_by_bow .............. ORBmatcher::SearchByBoW(KeyFrame*, Frame&, ...)
  *                                     src/ORBmatcher.cc:195-348 (Tracking.cc:1069, 2009)
  *   orbg_search_by_bow_kf ........... ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*, vpMatches12)
@@ -1088,6 +1096,115 @@ int orbg_bow_transform_batch_device(orbg_ctx *ctx, const orbg_vocab *v, const ui
                                     int32_t *bow_words, double *bow_weights, int32_t *nbow,
                                     int32_t *fv_nodes, int32_t *fv_off, int32_t *fv_feats,
                                     int32_t *nfv, int32_t *word_of, int32_t *node_of);
+
+/* ---------------- place recognition: BoW score + KeyFrameDatabase ---------------- */
+/* A set of BowVectors in device memory, in orbg_bow_transform_batch_device's output layout:
+ * vector f's rows at words / weights + f * cap (ascending word ids), nbow[f] entries. */
+typedef struct {
+    const int32_t *words;
+    const double *weights;
+    const int32_t *nbow;
+} orbg_bow_vectors;
+
+/* TemplatedVocabulary::score(v1, v2) (TemplatedVocabulary.h:1192-1196) = L1Scoring::score
+ * (Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68), host arrays (ascending word ids).  Only
+ * ORBG_L1_NORM vocabularies (ORBvoc.txt's "10 6 0 0"; ORB-SLAM2 uses no other): any other
+ * scoring returns ORBG_ENOTSUP.  *score is the reference's double bit for bit: the terms
+ * fabs(vi - wi) - fabs(vi) - fabs(wi) of the common words summed in ascending word order, then
+ * -score / 2.0, so two vectors without a common word give -0.0 as the reference does. */
+int orbg_bow_score(orbg_ctx *ctx, const orbg_vocab *v, const int32_t *words1,
+                   const double *weights1, int n1, const int32_t *words2, const double *weights2,
+                   int n2, double *score);
+/* Batched, device memory, on the context stream: d_score[p] = score(vector d_a_index[p] of a,
+ * vector d_b_index[p] of b) for p < npairs (both sets with `cap` rows per vector, cap <= 8192;
+ * a NULL index array means vector p).  The host form runs the same kernel. */
+int orbg_bow_score_batch_device(orbg_ctx *ctx, const orbg_vocab *v, const orbg_bow_vectors *a,
+                                const orbg_bow_vectors *b, int cap, const int32_t *d_a_index,
+                                const int32_t *d_b_index, int npairs, double *d_score);
+
+/* KeyFrameDatabase (src/KeyFrameDatabase.cc), device-resident, on ctx's device.  A KeyFrame
+ * is a slot in [0, max_keyframes): the caller's handle.  The database keeps each live slot's
+ * BowVector (up to cap entries), its add-sequence number (every add takes the next value of
+ * a monotonic counter; it is the KeyFrame's position in every inverted list: erase keeps the
+ * relative order of the rest, a later add appends) and its mRelocScore (float).  The
+ * reference leaves mRelocScore uninitialised (KeyFrame.cc:39-40); here add pins it to 0.
+ * Limits: max_keyframes <= 8192 (the per-slot counters and scores of a query live in LDS:
+ * 14 bytes per slot + 4 per query word <= 144 KiB of the CU's 160; larger: ORBG_ENOTSUP),
+ * cap <= 8192.  A vocabulary whose scoring is not ORBG_L1_NORM: ORBG_ENOTSUP.  All work runs
+ * on the context stream. */
+typedef struct orbg_kfdb orbg_kfdb;
+int orbg_kfdb_create(orbg_ctx *ctx, const orbg_vocab *v, int max_keyframes, int cap,
+                     orbg_kfdb **out);
+void orbg_kfdb_destroy(orbg_kfdb *db);
+/* live slots, max_keyframes, cap, and the largest max_keyframes orbg_kfdb_create accepts
+ * (any pointer may be NULL).  Waits for the database's pending work. */
+int orbg_kfdb_info(orbg_kfdb *db, int32_t *nlive, int32_t *max_keyframes, int32_t *cap,
+                   int32_t *limit);
+/* KeyFrameDatabase::add (:50-56), host arrays.  ORBG_EINVAL for a slot out of range or
+ * already live, n > cap, word ids not strictly ascending or outside [0, nwords). */
+int orbg_kfdb_add(orbg_ctx *ctx, orbg_kfdb *db, int slot, const int32_t *words,
+                  const double *weights, int n);
+/* add for i < n, in argument order: slot d_slots[i] <- vector d_index[i] (NULL: i) of `v`
+ * (vcap rows per vector, vcap <= the database's cap), straight from a transform batch's
+ * device outputs.  The validity of the slots (in range, not live, distinct) and of the
+ * vectors is the caller's responsibility: an out-of-range slot is skipped, nothing else is
+ * checked. */
+int orbg_kfdb_add_batch_device(orbg_ctx *ctx, orbg_kfdb *db, const int32_t *d_slots,
+                               const orbg_bow_vectors *v, int vcap, const int32_t *d_index,
+                               int n);
+/* KeyFrameDatabase::erase (:58-77; a slot that is not live: no effect) and clear (:79-83) */
+int orbg_kfdb_erase(orbg_ctx *ctx, orbg_kfdb *db, int slot);
+int orbg_kfdb_clear(orbg_ctx *ctx, orbg_kfdb *db);
+/* The inverted file is rebuilt on the device by the first query after an add / erase /
+ * clear; this does it now (no effect when it is current). */
+int orbg_kfdb_rebuild(orbg_ctx *ctx, orbg_kfdb *db);
+/* mRelocScore of every slot (reloc_score[max_keyframes], host; dead slots: unspecified) */
+int orbg_kfdb_reloc_scores(orbg_ctx *ctx, orbg_kfdb *db, float *reloc_score);
+
+/* KeyFrameDatabase::DetectRelocalizationCandidates (:291-419), batched: query i < nq is
+ * vector d_qindex[i] (NULL: i) of `q` (qcap rows per vector, qcap <= 8192).  d_neigh
+ * [max_keyframes][10]: row s = GetBestCovisibilityKeyFrames(10) of slot s as slots, -1 = unused,
+ * a dead slot is skipped.  Outputs: d_cand[i * cand_cap ..] the candidates in the reference's
+ * order (lKFsSharingWords' order: ascending (position in the query vector of the first shared
+ * word, add-sequence number)), d_ncand[i] the full count (only the first cand_cap are
+ * written), and when non-NULL d_max_common[i] = maxCommonWords, d_nscored[i] = nscores.
+ * minCommonWords = (int)(maxCommonWords * 0.8f); KeyFrames with more common words are
+ * scored (si = (float)score); the accumulation over the neighbours that share a word
+ * (mnRelocQuery == F->mnId) adds in neighbour order, and a neighbour that this query did not
+ * score contributes its stored mRelocScore, as in the reference; pBestKF by strict >,
+ * minScoreToRetain = 0.75f * bestAccScore by strict >, duplicates dropped (first kept).
+ * Every query of one call reads the stored mRelocScore as it was when the call started;
+ * after the call a slot's stored value is the score from the highest-indexed query that
+ * scored it.  With one query per call that is the reference's sequence. */
+int orbg_kfdb_detect_reloc_batch_device(orbg_ctx *ctx, orbg_kfdb *db, const orbg_bow_vectors *q,
+                                        int qcap, const int32_t *d_qindex, int nq,
+                                        const int32_t *d_neigh, int32_t *d_cand, int cand_cap,
+                                        int32_t *d_ncand, int32_t *d_max_common,
+                                        int32_t *d_nscored);
+/* One query from host arrays (neigh[max_keyframes][10], cand[cand_cap]; max_common / nscored
+ * may be NULL) on the same kernels. */
+int orbg_kfdb_detect_reloc(orbg_ctx *ctx, orbg_kfdb *db, const int32_t *words,
+                           const double *weights, int n, const int32_t *neigh, int32_t *cand,
+                           int cand_cap, int32_t *ncand, int32_t *max_common, int32_t *nscored);
+
+/* KeyFrameDatabase::DetectLoopCandidates (:106-274), batched as above, plus d_conn
+ * [nq][conn_cap] / d_nconn[nq] = the slots of pKF->GetConnectedKeyFrames() and d_min_score[nq].
+ * Connected KeyFrames never enter lKFsSharingWords and never count as a neighbour (their
+ * mnLoopQuery is never set); a KeyFrame is kept when si >= minScore; bestAccScore starts at
+ * minScore; a neighbour counts only if it shares a word, is not connected and has more than
+ * minCommonWords common words, so its score is this query's own (no stored state).  The query
+ * KeyFrame's own slot, if live, is treated like any other unless listed as connected. */
+int orbg_kfdb_detect_loop_batch_device(orbg_ctx *ctx, orbg_kfdb *db, const orbg_bow_vectors *q,
+                                       int qcap, const int32_t *d_qindex, int nq,
+                                       const int32_t *d_conn, int conn_cap,
+                                       const int32_t *d_nconn, const float *d_min_score,
+                                       const int32_t *d_neigh, int32_t *d_cand, int cand_cap,
+                                       int32_t *d_ncand, int32_t *d_max_common,
+                                       int32_t *d_nscored);
+int orbg_kfdb_detect_loop(orbg_ctx *ctx, orbg_kfdb *db, const int32_t *words,
+                          const double *weights, int n, const int32_t *conn, int nconn,
+                          float min_score, const int32_t *neigh, int32_t *cand, int cand_cap,
+                          int32_t *ncand, int32_t *max_common, int32_t *nscored);
 
 /* ---------------- ORBmatcher::SearchByBoW(KeyFrame*, Frame&) ---------------- */
 /* One side of SearchByBoW pairs, device memory, in orbg_bow_transform_batch_device's layout

@@ -3,7 +3,8 @@
 ORBextractor (pyramid, FAST-9 + quadtree distribution, IC_Angle, rBRIEF), ORBmatcher's
 Hamming matching (DescriptorDistance, brute-force 2-NN, SearchForInitialization),
 Frame::ComputeStereoMatches, the tracking matchers (SearchByProjection), PoseOptimization,
-DBoW2's vocabulary transform (Frame::ComputeBoW), the LBA Schur solve and
+DBoW2's vocabulary transform (Frame::ComputeBoW) and score, KeyFrameDatabase's place
+recognition (DetectRelocalizationCandidates, DetectLoopCandidates), the LBA Schur solve and
 the per-edge arithmetic of Optimizer::LocalBundleAdjustment, as hand-written HIP
 kernels behind the C ABI in include/orbg.h (lib/liborbg.so).  The Python classes mirror
 the reference's C++ interfaces; see DESIGN.md.
@@ -14,7 +15,8 @@ from .orbmatcher import Frame, MapPointProjections, ORBmatcher  # noqa: F401
 from .frame import StereoFrame  # noqa: F401
 from .optimizer import PoseOptimization, linearize_local_ba  # noqa: F401
 from .vocabulary import ORBVocabulary, BowVector, FeatureVector  # noqa: F401
+from .keyframedatabase import KeyFrameDatabase  # noqa: F401
 
 __all__ = ["ORBextractor", "ORBmatcher", "Frame", "MapPointProjections", "StereoFrame", "PoseOptimization", "linearize_local_ba",
-           "ORBVocabulary", "BowVector", "FeatureVector", "KP_DTYPE",
+           "ORBVocabulary", "BowVector", "FeatureVector", "KeyFrameDatabase", "KP_DTYPE",
            "EDGE_DTYPE", "EDGE_OUT_DTYPE", "POSE_DTYPE"]

@@ -178,6 +178,18 @@ class BowFrames(C.Structure):
                 ("nfv", C.c_void_p), ("valid", C.c_void_p)]
 
 
+class BowVectors(C.Structure):
+    """orbg_bow_vectors (include/orbg.h): a set of BowVectors, device pointers."""
+    _fields_ = [("words", C.c_void_p), ("weights", C.c_void_p), ("nbow", C.c_void_p)]
+
+
+def bow_vectors(v):
+    """BowVectors from a dict of device pointers (ints): words / weights / nbow, or
+    transform_batch_device's output names bow_words / bow_weights / nbow."""
+    return BowVectors(v.get("words", v.get("bow_words")), v.get("weights", v.get("bow_weights")),
+                      v["nbow"])
+
+
 _lib = None
 
 
@@ -329,6 +341,26 @@ def lib():
         "orbg_is_in_frustum_batch_device": (i32, [vp, vp, vp, vp, i32, i32, f32, vp, vp]),
         "orbg_distinctive_descriptor": (i32, [vp, vp, i32, P(C.c_int32)]),
         "orbg_distinctive_descriptors_batch_device": (i32, [vp, vp, vp, vp, i32, vp, vp]),
+        "orbg_bow_score": (i32, [vp, vp, vp, vp, i32, vp, vp, i32, P(C.c_double)]),
+        "orbg_bow_score_batch_device": (i32, [vp, vp, P(BowVectors), P(BowVectors), i32, vp, vp,
+                                              i32, vp]),
+        "orbg_kfdb_create": (i32, [vp, vp, i32, i32, P(vp)]),
+        "orbg_kfdb_destroy": (None, [vp]),
+        "orbg_kfdb_info": (i32, [vp, P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_int32)]),
+        "orbg_kfdb_add": (i32, [vp, vp, i32, vp, vp, i32]),
+        "orbg_kfdb_add_batch_device": (i32, [vp, vp, vp, P(BowVectors), i32, vp, i32]),
+        "orbg_kfdb_erase": (i32, [vp, vp, i32]),
+        "orbg_kfdb_clear": (i32, [vp, vp]),
+        "orbg_kfdb_rebuild": (i32, [vp, vp]),
+        "orbg_kfdb_reloc_scores": (i32, [vp, vp, vp]),
+        "orbg_kfdb_detect_reloc_batch_device": (i32, [vp, vp, P(BowVectors), i32, vp, i32, vp, vp,
+                                                      i32, vp, vp, vp]),
+        "orbg_kfdb_detect_reloc": (i32, [vp, vp, vp, vp, i32, vp, vp, i32, P(C.c_int32),
+                                         P(C.c_int32), P(C.c_int32)]),
+        "orbg_kfdb_detect_loop_batch_device": (i32, [vp, vp, P(BowVectors), i32, vp, i32, vp, i32,
+                                                     vp, vp, vp, vp, i32, vp, vp, vp]),
+        "orbg_kfdb_detect_loop": (i32, [vp, vp, vp, vp, i32, vp, i32, f32, vp, vp, i32,
+                                        P(C.c_int32), P(C.c_int32), P(C.c_int32)]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("ORBG_LIB_VARIANT") and not hasattr(L, name):

@@ -1,7 +1,8 @@
 """ORBVocabulary -- DBoW2's TemplatedVocabulary<FORB::TDescriptor, FORB> (include/ORBVocabulary.h)
 for the part the tracking hot path calls: loadFromTextFile and transform(features, BowVector,
 FeatureVector, levelsup) (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1126-1189, 1220-1259,
-1337-1420), as Frame::ComputeBoW uses it (src/Frame.cc:532-539, levelsup 4).
+1337-1420), as Frame::ComputeBoW uses it (src/Frame.cc:532-539, levelsup 4), and score(v1, v2)
+(TemplatedVocabulary.h:1192-1196, L1Scoring::score, ScoringObject.cpp:23-68).
 
 The tree lives in HBM (one 64-byte record per tree edge, see bow_kernels.hip); transform runs
 the descent and the BowVector / FeatureVector assembly on the GPU through liborbg
@@ -146,3 +147,36 @@ class ORBVocabulary:
             out["bow_words"], out["bow_weights"], out["nbow"], out["fv_nodes"], out["fv_off"],
             out["fv_feats"], out["nfv"], out.get("word_of"), out.get("node_of")),
             "orbg_bow_transform_batch_device")
+
+    # ---- score ----
+    def score_arrays(self, words1, weights1, words2, weights2):
+        """score(v1, v2) of two BowVectors given as (ascending word ids, weights) arrays:
+        the reference's double, bit for bit (-0.0 without a common word).  L1_NORM
+        vocabularies only (OrbgError ORBG_ENOTSUP otherwise)."""
+        w1 = np.ascontiguousarray(words1, np.int32)
+        x1 = np.ascontiguousarray(weights1, np.float64)
+        w2 = np.ascontiguousarray(words2, np.int32)
+        x2 = np.ascontiguousarray(weights2, np.float64)
+        if len(w1) != len(x1) or len(w2) != len(x2):
+            raise ValueError("word and weight arrays differ in length")
+        s = C.c_double()
+        L.check(L.lib().orbg_bow_score(_ctx(self.device).handle, self.handle, L.ptr(w1), L.ptr(x1),
+                                       len(w1), L.ptr(w2), L.ptr(x2), len(w2), C.byref(s)),
+                "orbg_bow_score")
+        return s.value
+
+    def score(self, v1, v2):
+        """TemplatedVocabulary::score(const BowVector &v1, const BowVector &v2) -> float."""
+        k1, k2 = sorted(v1), sorted(v2)
+        return self.score_arrays(k1, [v1[k] for k in k1], k2, [v2[k] for k in k2])
+
+    def score_batch_device(self, a, b, cap, d_a_index, d_b_index, npairs, d_score, ctx=None):
+        """Device-resident pairs (orbg_bow_score_batch_device): a, b map words / weights /
+        nbow (or transform_batch_device's bow_words / bow_weights / nbow) to device pointers
+        (ints); d_a_index / d_b_index may be None."""
+        ctx = ctx if ctx is not None else _ctx(self.device)
+        va, vb = L.bow_vectors(a), L.bow_vectors(b)
+        L.check(L.lib().orbg_bow_score_batch_device(ctx.handle, self.handle, C.byref(va),
+                                                    C.byref(vb), cap, d_a_index, d_b_index,
+                                                    npairs, d_score),
+                "orbg_bow_score_batch_device")
