@@ -1266,6 +1266,89 @@ int orbg_search_by_bow_kf_batch_device(orbg_ctx *ctx, const orbg_bow_frames *kf1
                                        int npairs, float nnratio, int check_ori,
                                        int32_t *d_match12, int32_t *d_nmatch);
 
+/* ---------------- Sim3Solver (LoopClosing::ComputeSim3) ----------------
+ * Sim3Solver(pKF1, pKF2, vpMatched12, bFixScale) + SetRansacParameters + iterate / find
+ * (src/Sim3Solver.cc:37-364; LoopClosing.cc:530-594), every RANSAC iteration of every
+ * candidate pair evaluated in one batch.
+ *
+ * The caller compacts the correspondences (Sim3Solver.cc:62-102: the pointer tests, isBad()
+ * and GetIndexInKeyFrame stay on the host): correspondence i holds the world positions of
+ * pMP1 / pMP2, mvLevelSigma2[octave] of the two keypoints and index1 = mvnIndices1[i], the
+ * slot in vpMatched12.  The device computes X3Dc = Rcw * Xw + tcw for both cameras, the
+ * own-image projections (FromCameraToImage, :405-423) and the thresholds mvnMaxError1 / 2,
+ * which the reference keeps in a vector<size_t>: th = (float)(uint64_t)(9.210 * (double)sigma2).
+ *
+ * An iteration is Horn 1987 on its three sampled correspondences (ComputeSim3, :226-337) and
+ * CheckInliers (:340-364: err1 < th1 && err2 < th2, both strict, NaN fails), all in fp32.
+ * Departures: the 4x4 eigenvector comes from a fixed number of cyclic Jacobi sweeps, and R is
+ * built from the unit quaternion directly where the reference goes quaternion -> angle-axis
+ * -> cv::Rodrigues.  That is the same rotation (and +q / -q give the same R), except that the
+ * reference's 0 / 0 at an exactly zero rotation angle does not occur here.  A degenerate
+ * sample (largest eigenvalue not positive, e.g. three identical points, or a scale that is
+ * zero or not finite; the reference then carries NaN or infinity and finds no inlier) counts
+ * 0 inliers, with an all-zero mask and an all-zero hypothesis (s = 0).
+ *
+ * The random draws are an input: samples[it] = the three correspondence indices of iteration
+ * it, which the reference takes from rand() (DUtils::Random::RandomInt, Sim3Solver.cc:163-177).
+ *
+ * Acceptance is the reference's sequential rule (:183-200) from a fresh solver over
+ * iterations 0 .. iterations - 1: best is replaced when count >= best (ties go to the later
+ * iteration); the first iteration with count >= best && count > min_inliers (strict) is the
+ * hit and ends the scan.  hit_iter = that iteration or -1; best_iter = the iteration holding
+ * mBestT12 when the scan ended (-1: none ran); nomore = bNoMore (N < min_inliers, or every
+ * iteration used without a hit); hyp / ninliers / inliers12 are those of the returned
+ * iteration: the hit, else best_iter (all zero if none ran).  N < min_inliers or N < 3 runs
+ * no iteration. */
+typedef struct {
+    float T1w[12], T2w[12];          /* pKF1 / pKF2 GetPose() rows 0..2 */
+    float fx1, fy1, cx1, cy1;        /* pKF1->mK */
+    float fx2, fy2, cx2, cy2;        /* pKF2->mK */
+    int32_t n;                       /* N, the correspondences of this pair */
+    int32_t fix_scale;               /* mbFixScale */
+    int32_t min_inliers;             /* mRansacMinInliers */
+    int32_t iterations;              /* mRansacMaxIts (orbg_sim3_ransac_iterations) */
+} orbg_sim3_problem;
+typedef struct {
+    float Xw1[3], Xw2[3];            /* pMP1 / pMP2 GetWorldPos() */
+    float sigma2_1, sigma2_2;        /* mvLevelSigma2[kp.octave] in pKF1 / pKF2 */
+    int32_t index1;                  /* mvnIndices1[i] */
+} orbg_sim3_corr;
+typedef struct {
+    float R[9], t[3], s;             /* mR12i (row-major), mt12i, ms12i */
+} orbg_sim3_hyp;
+typedef struct {
+    int32_t hit_iter, best_iter, ninliers, nomore;
+    orbg_sim3_hyp hyp;
+} orbg_sim3_result;
+/* Sim3Solver::SetRansacParameters (:114-138): mRansacMaxIts for N = n correspondences
+ * (epsilon a float, pow / log in double; 1 when min_inliers == n; max(1, min(nIterations,
+ * max_its))).  LoopClosing uses (0.99, 20, 300).  Host arithmetic only: no GPU, no context. */
+int orbg_sim3_ransac_iterations(double prob, int min_inliers, int max_its, int n);
+/* One pair from host arrays: corrs[problem->n], samples[problem->iterations][3], n1 =
+ * vpMatched12.size().  Outputs: result, inliers12[n1] (vbInliers as bytes) and, where not
+ * NULL, counts[iterations] (mnInliersi), hyps[iterations] and masks[iterations][ceil(n / 64)]
+ * (bit i % 64 of word i / 64 = mvbInliersi[i]).  ORBG_EINVAL for a NULL context or required
+ * pointer, an index1 outside [0, n1), a sample index outside [0, n) or one repeated within its
+ * triple; ORBG_ENOTSUP past 8192 correspondences.  Runs the batched kernels with npairs = 1
+ * (bit-identical results).  Synchronises. */
+int orbg_sim3_solve(orbg_ctx *ctx, const orbg_sim3_problem *problem, const orbg_sim3_corr *corrs,
+                    const int32_t *samples, int n1, int32_t *counts, orbg_sim3_hyp *hyps,
+                    uint64_t *masks, orbg_sim3_result *result, uint8_t *inliers12);
+/* Batched, device memory: pair p = d_problems[p] with d_corrs + p * cap, d_samples +
+ * (p * max_its) * 3; cap a multiple of 64 (ORBG_ENOTSUP past 8192), d_problems[p].n <= cap and
+ * .iterations <= max_its (a count outside that runs nothing; more iterations are cut at
+ * max_its).  Outputs d_counts[npairs][max_its], d_hyps[npairs][max_its], d_masks[npairs]
+ * [max_its][cap / 64], d_results[npairs], d_inliers12[npairs][n1cap] (an index1 outside
+ * [0, n1cap) is not written).  Iterations past a pair's own and mask words past its n are
+ * zero; a triple with an index outside [0, n) or a repeated one is a degenerate iteration.
+ * Context stream, no host synchronisation; the only allocation is the context scratch, grown
+ * when a call needs more than any before it. */
+int orbg_sim3_solve_batch_device(orbg_ctx *ctx, const orbg_sim3_problem *d_problems,
+                                 const orbg_sim3_corr *d_corrs, const int32_t *d_samples,
+                                 int npairs, int cap, int max_its, int32_t *d_counts,
+                                 orbg_sim3_hyp *d_hyps, uint64_t *d_masks,
+                                 orbg_sim3_result *d_results, uint8_t *d_inliers12, int n1cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,6 +56,17 @@ SIM3_PAIR_DTYPE = np.dtype([("T1w", "<f4", 12), ("T2w", "<f4", 12), ("R12", "<f4
                             ("cx", "<f4"), ("cy", "<f4"), ("log_scale_factor", "<f4"),
                             ("nlevels", "<i4"), ("min_x", "<f4"), ("max_x", "<f4"),
                             ("min_y", "<f4"), ("max_y", "<f4")])
+# Sim3Solver records (orbg_sim3_problem, orbg_sim3_corr, orbg_sim3_hyp, orbg_sim3_result)
+SIM3_PROBLEM_DTYPE = np.dtype([("T1w", "<f4", 12), ("T2w", "<f4", 12), ("fx1", "<f4"),
+                               ("fy1", "<f4"), ("cx1", "<f4"), ("cy1", "<f4"), ("fx2", "<f4"),
+                               ("fy2", "<f4"), ("cx2", "<f4"), ("cy2", "<f4"), ("n", "<i4"),
+                               ("fix_scale", "<i4"), ("min_inliers", "<i4"),
+                               ("iterations", "<i4")])
+SIM3_CORR_DTYPE = np.dtype([("Xw1", "<f4", 3), ("Xw2", "<f4", 3), ("sigma2_1", "<f4"),
+                            ("sigma2_2", "<f4"), ("index1", "<i4")])
+SIM3_HYP_DTYPE = np.dtype([("R", "<f4", 9), ("t", "<f4", 3), ("s", "<f4")])
+SIM3_RESULT_DTYPE = np.dtype([("hit_iter", "<i4"), ("best_iter", "<i4"), ("ninliers", "<i4"),
+                              ("nomore", "<i4"), ("hyp", SIM3_HYP_DTYPE)])
 RELOC_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("min_dist", "<f4"),
                         ("max_dist", "<f4"), ("angle", "<f4"), ("flags", "<i4")])
 MAPPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"),
@@ -361,6 +372,10 @@ def lib():
                                                      vp, vp, vp, vp, i32, vp, vp, vp]),
         "orbg_kfdb_detect_loop": (i32, [vp, vp, vp, vp, i32, vp, i32, f32, vp, vp, i32,
                                         P(C.c_int32), P(C.c_int32), P(C.c_int32)]),
+        "orbg_sim3_ransac_iterations": (i32, [C.c_double, i32, i32, i32]),
+        "orbg_sim3_solve": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
+        "orbg_sim3_solve_batch_device": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp,
+                                               i32]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("ORBG_LIB_VARIANT") and not hasattr(L, name):

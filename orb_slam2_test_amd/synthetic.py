@@ -508,3 +508,60 @@ def write_vocabulary_text(path, voc, weight_fmt="%.17g"):
             f.write("%d %d %s %s\n" % (voc["parent"][i], voc["is_leaf"][i],
                                        " ".join(str(int(b)) for b in voc["desc"][i]),
                                        weight_fmt % voc["weight"][i]))
+
+
+# ---------------------------------------------------------------------------
+# Sim3Solver scenes (LoopClosing::ComputeSim3): two KeyFrames seeing the same points up to a
+# planted similarity, as compacted correspondences
+# ---------------------------------------------------------------------------
+SIM3_K = (718.856, 718.856, 607.19, 185.2157)
+
+
+def _random_pose(rng, ang, trans):
+    """4x4 world -> camera pose: `ang` rad about a random axis, translation of norm <= trans"""
+    T = np.eye(4)
+    T[:3, :3] = _rot(_quat_from_axis_angle(rng.normal(size=3), ang))
+    T[:3, 3] = rng.uniform(-1, 1, 3) * trans
+    return T
+
+
+def sim3_scene(seed=DEFAULT_SEED, n=100, outlier_frac=0.3, noise=0.02, fix_scale=False,
+               angle=0.15, scale=1.3, t12=(0.4, -0.1, 0.8), K=SIM3_K, n1=None,
+               identical=0):
+    """n correspondences between KeyFrame 1 and KeyFrame 2 under a planted Sim3
+    (P1 = s R P2 + t in camera coordinates: `angle` rad about a random axis, `scale` (1 with
+    fix_scale), t12).  Points lie in x [-8, 8], y [-2, 2], z [4, 40] of camera 1; camera-2 points
+    get Gaussian `noise`, and outlier_frac of them are replaced by random ones.  Octaves are
+    uniform in 0..7 with sigma2 = 1.2^(2 octave).  Both KeyFrame poses are non-identity.
+    n1 = vpMatched12.size(): None gives index1 = 0..n-1, a number gives n distinct slots of
+    [0, n1) in random order.  identical = k makes correspondences 0..k-1 copies of one another.
+
+    Returns float32 arrays: T1w, T2w (4x4), K, Xw1, Xw2 [n][3], sigma2_1, sigma2_2, index1, n1,
+    and the planted R12, t12, s12 with the outlier flags."""
+    rng = np.random.default_rng(seed)
+    s = 1.0 if fix_scale else float(scale)
+    R = _rot(_quat_from_axis_angle(rng.normal(size=3), angle))
+    t = np.asarray(t12, np.float64)
+    lo, hi = np.array([-8.0, -2.0, 4.0]), np.array([8.0, 2.0, 40.0])
+    P1 = rng.uniform(lo, hi, (n, 3))
+    P2 = (P1 - t) @ R / s                     # rows: (1 / s) R^T (P1 - t)
+    P2 += rng.normal(0.0, noise, (n, 3))
+    outlier = rng.random(n) < outlier_frac
+    P2[outlier] = rng.uniform(lo, hi, (int(outlier.sum()), 3))
+    if identical:
+        P1[:identical] = P1[0]
+        P2[:identical] = P2[0]
+    T1w, T2w = _random_pose(rng, 0.7, 5.0), _random_pose(rng, 1.1, 8.0)
+    Xw1 = (P1 - T1w[:3, 3]) @ T1w[:3, :3]     # rows: R^T (P - t)
+    Xw2 = (P2 - T2w[:3, 3]) @ T2w[:3, :3]
+    oct1, oct2 = rng.integers(0, 8, n), rng.integers(0, 8, n)
+    if n1 is None:
+        n1, index1 = n, np.arange(n)
+    else:
+        index1 = rng.permutation(n1)[:n]
+    f = np.float32
+    return {"T1w": T1w.astype(f), "T2w": T2w.astype(f), "K": tuple(float(k) for k in K),
+            "Xw1": Xw1.astype(f), "Xw2": Xw2.astype(f),
+            "sigma2_1": (1.2 ** (2 * oct1)).astype(f), "sigma2_2": (1.2 ** (2 * oct2)).astype(f),
+            "index1": index1.astype(np.int32), "n1": int(n1), "n": int(n),
+            "fix_scale": bool(fix_scale), "R12": R, "t12": t, "s12": s, "outlier": outlier}
