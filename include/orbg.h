@@ -67,6 +67,8 @@
  *   orbg_ba_linearize ............... g2o computeActiveErrors + BlockSolver::buildSystem arithmetic
  *                                     for EdgeSE3ProjectXYZ / EdgeStereoSE3ProjectXYZ inside
  *                                     Optimizer::LocalBundleAdjustment  src/Optimizer.cc:633-979
+ *   orbg_optimize_sim3 .............. Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2,
+ *                                     bFixScale)  src/Optimizer.cc:1366-1578 (LoopClosing.cc:598)
  *
  * Batched, device-resident entry points (orbg_*_device) run the same kernels over many
  * frames at once; they exist for the batched-sequence mode and the bench.
@@ -1348,6 +1350,79 @@ int orbg_sim3_solve_batch_device(orbg_ctx *ctx, const orbg_sim3_problem *d_probl
                                  int npairs, int cap, int max_its, int32_t *d_counts,
                                  orbg_sim3_hyp *d_hyps, uint64_t *d_masks,
                                  orbg_sim3_result *d_results, uint8_t *d_inliers12, int n1cap);
+
+/* ---------------- Optimizer::OptimizeSim3 (LoopClosing::ComputeSim3) ----------------
+ * Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) (src/Optimizer.cc:
+ * 1366-1578; LoopClosing.cc:598-603 with th2 = 10), one workgroup per loop candidate: g2o's
+ * Levenberg-Marquardt (BlockSolverX + LinearSolverDense) on the one free VertexSim3Expmap,
+ * in fp64, with the numeric Jacobian g2o really uses for these edges
+ * (BaseBinaryEdge::linearizeOplus: central differences, delta 1e-9, through
+ * Sim3(update) * estimate), Huber of delta = (float)sqrt(th2), optimize(5), the drop test,
+ * optimize(nBad > 0 ? 10 : 5) on the kept pairs and the final test.
+ *
+ * The caller compacts the correspondences as the loop of Optimizer.cc:1426-1513 does (the
+ * pointer tests, isBad() and GetIndexInKeyFrame stay on the host): correspondence i holds
+ * the world positions of pMP1 = vpMapPoints1[index1] and pMP2 = vpMatches1[index1], the
+ * undistorted keypoints obs1 = pKF1->mvKeysUn[index1].pt and obs2 = pKF2->mvKeysUn[i2].pt,
+ * mvInvLevelSigma2[octave] of the two and index1, the slot in vpMatches1.  The device
+ * computes the fixed points P1c = R1w Xw1 + t1w and P2c = R2w Xw2 + t2w in float and widens
+ * them.  The initial Sim3 is an orbg_sim3_hyp (float R, t, s), as orbg_sim3_result.hyp holds
+ * it: g2o::Sim3(Converter::toMatrix3d(R), toVector3d(t), s), i.e. Eigen's Quaterniond(R).
+ *
+ * A pair is dropped when e12.chi2() > th2 || e21.chi2() > th2, evaluated in double at the
+ * estimate of the last LM trial g2o evaluated, accepted or not (g2o does not recompute the
+ * errors after a rejected trial, and OptimizeSim3 classifies on the stored ones).  A NaN is
+ * not greater than th2, so the pair stays.  A point with non-positive depth is not treated
+ * specially anywhere: z = 0 divides to +-infinity or NaN, z < 0 projects through the
+ * camera centre, and the chi2 that results takes the same comparisons as any other.
+ *
+ * Result: q (x, y, z, w; not re-normalised, as g2o::Sim3 keeps it), t, s of g2oS12 in
+ * double; R = Quaterniond::toRotationMatrix(), tf, sf = the same estimate rounded to float
+ * once (for orbg_sim3_pair and Scw); ninliers = the return value (0 when fewer than 10 pairs
+ * survive the first test, and then q, t, s are the input, as g2oS12 is not written back);
+ * nbad = nBad of the first test; ncorr = nCorrespondences; iterations = the LM iterations
+ * each optimize() ran.  keep[j] = 1 iff slot j had a correspondence and vpMatches1[j] was
+ * not set to NULL (on the return-0 path too: the first test's drops stay dropped). */
+typedef struct {
+    float T1w[12], T2w[12];          /* pKF1 / pKF2 GetPose() rows 0..2 */
+    float fx1, fy1, cx1, cy1;        /* pKF1->mK */
+    float fx2, fy2, cx2, cy2;        /* pKF2->mK */
+    int32_t n;                       /* nCorrespondences */
+    int32_t fix_scale;               /* bFixScale */
+    float th2;                       /* th2 (LoopClosing: 10) */
+    int32_t pad;
+} orbg_sim3opt_problem;
+typedef struct {
+    float Xw1[3], Xw2[3];            /* pMP1 / pMP2 GetWorldPos() */
+    float obs1[2], obs2[2];          /* kpUn1.pt, kpUn2.pt */
+    float inv_sigma2_1, inv_sigma2_2;/* mvInvLevelSigma2[kpUn.octave] in pKF1 / pKF2 */
+    int32_t index1;                  /* the slot i of vpMatches1 */
+} orbg_sim3opt_corr;
+typedef struct {
+    double q[4], t[3], s;            /* g2oS12 (q = x, y, z, w) */
+    float R[9], tf[3], sf;           /* the same, rounded once (R row-major) */
+    int32_t ninliers, nbad, ncorr;
+    int32_t iterations[2];
+} orbg_sim3opt_result;
+/* One candidate from host arrays: corrs[problem->n], init = the Sim3 to refine, n1 =
+ * vpMatches1.size(); outputs result and keep[n1].  ORBG_EINVAL for a NULL context or required
+ * pointer, an index1 outside [0, n1), a th2 that is not finite or <= 0; ORBG_ENOTSUP past
+ * 8192 correspondences.  Runs the batched kernel with npairs = 1 (bit-identical results).
+ * Synchronises. */
+int orbg_optimize_sim3(orbg_ctx *ctx, const orbg_sim3opt_problem *problem,
+                       const orbg_sim3opt_corr *corrs, const orbg_sim3_hyp *init, int n1,
+                       orbg_sim3opt_result *result, uint8_t *keep);
+/* Batched, device memory: candidate p = d_problems[p] with d_corrs + p * cap and d_init[p];
+ * cap a multiple of 64 (ORBG_ENOTSUP past 8192).  A count outside [0, cap], or a th2 that is
+ * not finite and positive, runs nothing: the record is that of n = 0 (the input Sim3, all
+ * counts 0).  d_keep[npairs][n1cap]: every byte of a candidate's row is written, 0 where no
+ * correspondence names the slot; an index1 outside [0, n1cap) writes nothing.  Context
+ * stream, no host synchronisation, no allocation.  The sums are reduced in a fixed order:
+ * results are reproducible run to run and equal to orbg_optimize_sim3's. */
+int orbg_optimize_sim3_batch_device(orbg_ctx *ctx, const orbg_sim3opt_problem *d_problems,
+                                    const orbg_sim3opt_corr *d_corrs, const orbg_sim3_hyp *d_init,
+                                    int npairs, int cap, orbg_sim3opt_result *d_results,
+                                    uint8_t *d_keep, int n1cap);
 
 #ifdef __cplusplus
 }

@@ -4,8 +4,8 @@ ORBextractor (pyramid, FAST-9 + quadtree distribution, IC_Angle, rBRIEF), ORBmat
 Hamming matching (DescriptorDistance, brute-force 2-NN, SearchForInitialization),
 Frame::ComputeStereoMatches, the tracking matchers (SearchByProjection), PoseOptimization,
 DBoW2's vocabulary transform (Frame::ComputeBoW) and score, KeyFrameDatabase's place
-recognition (DetectRelocalizationCandidates, DetectLoopCandidates), Sim3Solver's RANSAC
-(LoopClosing::ComputeSim3), the LBA Schur solve and
+recognition (DetectRelocalizationCandidates, DetectLoopCandidates), Sim3Solver's RANSAC and
+Optimizer::OptimizeSim3 (LoopClosing::ComputeSim3), the LBA Schur solve and
 the per-edge arithmetic of Optimizer::LocalBundleAdjustment, as hand-written HIP
 kernels behind the C ABI in include/orbg.h (lib/liborbg.so).  The Python classes mirror
 the reference's C++ interfaces; see DESIGN.md.
@@ -14,12 +14,12 @@ from ._lib import KP_DTYPE, EDGE_DTYPE, EDGE_OUT_DTYPE, POSE_DTYPE, LIB_PATH  # 
 from .orbextractor import ORBextractor  # noqa: F401
 from .orbmatcher import Frame, MapPointProjections, ORBmatcher  # noqa: F401
 from .frame import StereoFrame  # noqa: F401
-from .optimizer import PoseOptimization, linearize_local_ba  # noqa: F401
+from .optimizer import PoseOptimization, linearize_local_ba, OptimizeSim3, OptimizeSim3Batch  # noqa: F401
 from .vocabulary import ORBVocabulary, BowVector, FeatureVector  # noqa: F401
 from .keyframedatabase import KeyFrameDatabase  # noqa: F401
 from .sim3solver import Sim3Solver  # noqa: F401
 
-__all__ = ["ORBextractor", "ORBmatcher", "Frame", "MapPointProjections", "StereoFrame", "PoseOptimization", "linearize_local_ba",
+__all__ = ["ORBextractor", "ORBmatcher", "Frame", "MapPointProjections", "StereoFrame", "PoseOptimization", "linearize_local_ba", "OptimizeSim3", "OptimizeSim3Batch",
            "ORBVocabulary", "BowVector", "FeatureVector", "KeyFrameDatabase", "Sim3Solver",
            "KP_DTYPE",
            "EDGE_DTYPE", "EDGE_OUT_DTYPE", "POSE_DTYPE"]

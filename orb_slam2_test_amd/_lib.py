@@ -67,6 +67,18 @@ SIM3_CORR_DTYPE = np.dtype([("Xw1", "<f4", 3), ("Xw2", "<f4", 3), ("sigma2_1", "
 SIM3_HYP_DTYPE = np.dtype([("R", "<f4", 9), ("t", "<f4", 3), ("s", "<f4")])
 SIM3_RESULT_DTYPE = np.dtype([("hit_iter", "<i4"), ("best_iter", "<i4"), ("ninliers", "<i4"),
                               ("nomore", "<i4"), ("hyp", SIM3_HYP_DTYPE)])
+# OptimizeSim3 records (orbg_sim3opt_problem, orbg_sim3opt_corr, orbg_sim3opt_result)
+SIM3OPT_PROBLEM_DTYPE = np.dtype([("T1w", "<f4", 12), ("T2w", "<f4", 12), ("fx1", "<f4"),
+                                  ("fy1", "<f4"), ("cx1", "<f4"), ("cy1", "<f4"), ("fx2", "<f4"),
+                                  ("fy2", "<f4"), ("cx2", "<f4"), ("cy2", "<f4"), ("n", "<i4"),
+                                  ("fix_scale", "<i4"), ("th2", "<f4"), ("pad", "<i4")])
+SIM3OPT_CORR_DTYPE = np.dtype([("Xw1", "<f4", 3), ("Xw2", "<f4", 3), ("obs1", "<f4", 2),
+                               ("obs2", "<f4", 2), ("inv_sigma2_1", "<f4"),
+                               ("inv_sigma2_2", "<f4"), ("index1", "<i4")])
+SIM3OPT_RESULT_DTYPE = np.dtype([("q", "<f8", 4), ("t", "<f8", 3), ("s", "<f8"),
+                                 ("R", "<f4", 9), ("tf", "<f4", 3), ("sf", "<f4"),
+                                 ("ninliers", "<i4"), ("nbad", "<i4"), ("ncorr", "<i4"),
+                                 ("iterations", "<i4", 2)])
 RELOC_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("min_dist", "<f4"),
                         ("max_dist", "<f4"), ("angle", "<f4"), ("flags", "<i4")])
 MAPPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"),
@@ -376,6 +388,8 @@ def lib():
         "orbg_sim3_solve": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
         "orbg_sim3_solve_batch_device": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp,
                                                i32]),
+        "orbg_optimize_sim3": (i32, [vp, vp, vp, vp, i32, vp, vp]),
+        "orbg_optimize_sim3_batch_device": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, i32]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("ORBG_LIB_VARIANT") and not hasattr(L, name):

@@ -26,6 +26,7 @@
 #include "bow_args.h"
 #include "place_args.h"
 #include "sim3_args.h"
+#include "sim3opt_args.h"
 #include "pyramid_args.h"
 #include "frame_device.h"
 
@@ -6444,6 +6445,85 @@ extern "C" int orbg_sim3_solve(orbg_ctx *c, const orbg_sim3_problem *problem,
                                 hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(result, b + o_r, sizeof(orbg_sim3_result), hipMemcpyDeviceToHost, c->stream));
     if (n1) HIPCHK(hipMemcpyAsync(inliers12, b + o_i, (size_t)n1, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->prof.collect();
+    return ORBG_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Optimizer::OptimizeSim3: batched Sim3 refinement of loop candidates (sim3opt_kernels.hip)
+// ---------------------------------------------------------------------------
+extern "C" int orbg_optimize_sim3_batch_device(orbg_ctx *c, const orbg_sim3opt_problem *d_problems,
+                                               const orbg_sim3opt_corr *d_corrs,
+                                               const orbg_sim3_hyp *d_init, int npairs, int cap,
+                                               orbg_sim3opt_result *d_results, uint8_t *d_keep,
+                                               int n1cap)
+{
+    if (!c) return set_err(ORBG_EINVAL, "context is NULL");
+    if (npairs < 0 || cap < 64 || (cap & 63) || n1cap < 1)
+        return set_err(ORBG_EINVAL, "bad npairs / cap (a multiple of 64) / n1cap");
+    if (cap > ORBG_SIM3OPT_MAX_N)
+        return set_err(ORBG_ENOTSUP, "cap %d (> %d correspondences per candidate)", cap,
+                       ORBG_SIM3OPT_MAX_N);
+    if (npairs == 0) return ORBG_OK;
+    if (!d_problems || !d_corrs || !d_init || !d_results || !d_keep)
+        return set_err(ORBG_EINVAL, "NULL device array");
+    HIPCHK(hipSetDevice(c->device));
+    Sim3OptArgs A{};
+    A.problems = d_problems;
+    A.corrs = d_corrs;
+    A.init = d_init;
+    A.npairs = npairs;
+    A.cap = cap;
+    A.n1cap = n1cap;
+    A.results = d_results;
+    A.keep = d_keep;
+    int rc;
+    if ((rc = launch_sim3opt(c->stream, A, &c->prof))) return set_err(rc, "OptimizeSim3 launch failed");
+    return ORBG_OK;
+}
+
+extern "C" int orbg_optimize_sim3(orbg_ctx *c, const orbg_sim3opt_problem *problem,
+                                  const orbg_sim3opt_corr *corrs, const orbg_sim3_hyp *init, int n1,
+                                  orbg_sim3opt_result *result, uint8_t *keep)
+{
+    if (!c || !problem || !init || !result) return set_err(ORBG_EINVAL, "NULL argument");
+    const orbg_sim3opt_problem P = *problem;
+    if (P.n < 0 || n1 < 0) return set_err(ORBG_EINVAL, "negative size");
+    if (!(P.th2 > 0.0f) || !(P.th2 <= FLT_MAX))
+        return set_err(ORBG_EINVAL, "th2 %g is not finite and positive", (double)P.th2);
+    if (P.n > ORBG_SIM3OPT_MAX_N)
+        return set_err(ORBG_ENOTSUP, "%d correspondences (> %d)", P.n, ORBG_SIM3OPT_MAX_N);
+    if ((P.n && !corrs) || (n1 && !keep)) return set_err(ORBG_EINVAL, "NULL array");
+    for (int i = 0; i < P.n; i++)
+        if (corrs[i].index1 < 0 || corrs[i].index1 >= n1)
+            return set_err(ORBG_EINVAL, "index1 %d of correspondence %d outside [0, %d)",
+                           corrs[i].index1, i, n1);
+    const int cap = std::max(64, (P.n + 63) & ~63);
+    HIPCHK(hipSetDevice(c->device));
+    PlaceUpload U;
+    const size_t o_p = U.take(sizeof(P)), o_k = U.take((size_t)cap * sizeof(orbg_sim3opt_corr));
+    const size_t o_h = U.take(sizeof(orbg_sim3_hyp)), o_r = U.take(sizeof(orbg_sim3opt_result));
+    const size_t o_i = U.take((size_t)std::max(n1, 1));
+    void *sp;
+    int rc = scratch(c, U.off, &sp);
+    if (rc) return rc;
+    uint8_t *b = (uint8_t *)sp;
+    HIPCHK(hipMemcpyAsync(b + o_p, &P, sizeof(P), hipMemcpyHostToDevice, c->stream));
+    if (P.n) HIPCHK(hipMemcpyAsync(b + o_k, corrs, (size_t)P.n * sizeof(orbg_sim3opt_corr), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(b + o_h, init, sizeof(orbg_sim3_hyp), hipMemcpyHostToDevice, c->stream));
+    Sim3OptArgs A{};
+    A.problems = (const orbg_sim3opt_problem *)(b + o_p);
+    A.corrs = (const orbg_sim3opt_corr *)(b + o_k);
+    A.init = (const orbg_sim3_hyp *)(b + o_h);
+    A.npairs = 1;
+    A.cap = cap;
+    A.n1cap = std::max(n1, 1);
+    A.results = (orbg_sim3opt_result *)(b + o_r);
+    A.keep = b + o_i;
+    if ((rc = launch_sim3opt(c->stream, A, &c->prof))) return set_err(rc, "OptimizeSim3 launch failed");
+    HIPCHK(hipMemcpyAsync(result, b + o_r, sizeof(orbg_sim3opt_result), hipMemcpyDeviceToHost, c->stream));
+    if (n1) HIPCHK(hipMemcpyAsync(keep, b + o_i, (size_t)n1, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     c->prof.collect();
     return ORBG_OK;

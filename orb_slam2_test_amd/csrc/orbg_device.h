@@ -91,7 +91,8 @@ __device__ __forceinline__ int xcd_remap(int orig, int nwg)
 }
 
 // double sin/cos pinned to one polynomial so the oracle (orb_oracle.c) matches bit for bit
-__device__ __forceinline__ void pinned_sincos(double x, double *s, double *c)
+// (__host__ too: sim3opt_args.h's host program runs the same statements)
+__host__ __device__ __forceinline__ void pinned_sincos(double x, double *s, double *c)
 {
     const double two_over_pi = 6.36619772367581382433e-01;
     const double pio2_1 = 1.57079632673412561417e+00;

@@ -8,6 +8,10 @@ arithmetic g2o performs per edge in computeActiveErrors + BlockSolver::buildSyst
 residual, analytic Jacobians, chi2, Huber weight and the J^T W J / J^T W r blocks.
 
 Arrays use the dtypes of ``_lib`` (POSE_DTYPE, EDGE_DTYPE, EDGE_OUT_DTYPE).
+
+PoseOptimization (Optimizer.cc:356-631) and OptimizeSim3 (:1366-1578, the Sim3 refinement of
+LoopClosing::ComputeSim3) run whole on the device, LM driver included: one workgroup per frame
+or per loop candidate.
 """
 import ctypes
 import math
@@ -97,6 +101,138 @@ def PoseOptimization(edges, Tcw, fx, fy, cx, cy, bf, device=0):
                                            L.ptr(T), L.ptr(q), L.ptr(t), L.ptr(To), L.ptr(out),
                                            ctypes.byref(ni)), "orbg_pose_optimization")
     return ni.value, To.reshape(3, 4), q, t, out[:len(e)].astype(bool)
+
+
+def _pose34(T):
+    T = np.asarray(T, np.float32)
+    if T.shape not in ((3, 4), (4, 4)):
+        raise ValueError("a pose is 3x4 or 4x4")
+    return np.ascontiguousarray(T[:3, :4]).reshape(12)
+
+
+def _intrinsics(K):
+    K = np.asarray(K, np.float32)
+    if K.shape == (3, 3):
+        return K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+    if K.shape == (4,):
+        return tuple(K)
+    raise ValueError("K is 3x3 or (fx, fy, cx, cy)")
+
+
+SIM3OPT_MAX_N = 8192   # correspondences per candidate (ORBG_ENOTSUP past it)
+
+
+def sim3opt_records(T1w, T2w, K1, K2, Xw1, Xw2, obs1, obs2, inv_sigma2_1, inv_sigma2_2, index1,
+                    R12, t12, s12, th2, bFixScale):
+    """(orbg_sim3opt_problem [1], orbg_sim3opt_corr [n], orbg_sim3_hyp [1]) of one
+    OptimizeSim3 call from its arrays."""
+    Xw1 = np.asarray(Xw1, np.float32).reshape(-1, 3)
+    n = len(Xw1)
+    p = np.zeros(1, L.SIM3OPT_PROBLEM_DTYPE)
+    p["T1w"][0], p["T2w"][0] = _pose34(T1w), _pose34(T2w)
+    p["fx1"], p["fy1"], p["cx1"], p["cy1"] = _intrinsics(K1)
+    p["fx2"], p["fy2"], p["cx2"], p["cy2"] = _intrinsics(K2)
+    p["n"], p["fix_scale"], p["th2"] = n, 1 if bFixScale else 0, np.float32(th2)
+    c = np.zeros(n, L.SIM3OPT_CORR_DTYPE)
+    c["Xw1"] = Xw1
+    c["Xw2"] = np.asarray(Xw2, np.float32).reshape(n, 3)
+    c["obs1"] = np.asarray(obs1, np.float32).reshape(n, 2)
+    c["obs2"] = np.asarray(obs2, np.float32).reshape(n, 2)
+    c["inv_sigma2_1"] = np.asarray(inv_sigma2_1, np.float32).reshape(n)
+    c["inv_sigma2_2"] = np.asarray(inv_sigma2_2, np.float32).reshape(n)
+    c["index1"] = np.asarray(index1, np.int32).reshape(n)
+    h = np.zeros(1, L.SIM3_HYP_DTYPE)
+    h["R"][0] = np.asarray(R12, np.float32).reshape(9)
+    h["t"][0] = np.asarray(t12, np.float32).reshape(3)
+    h["s"] = np.float32(s12)
+    return p, c, h
+
+
+def optimize_sim3(problem, corrs, init, n1, ctx=None, device=0):
+    """orbg_optimize_sim3 on records: (SIM3OPT_RESULT_DTYPE scalar, keep uint8 [n1])."""
+    problem = np.ascontiguousarray(problem, L.SIM3OPT_PROBLEM_DTYPE).reshape(1)
+    corrs = np.ascontiguousarray(corrs, L.SIM3OPT_CORR_DTYPE).reshape(-1)
+    init = np.ascontiguousarray(init, L.SIM3_HYP_DTYPE).reshape(1)
+    if len(corrs) < int(problem["n"][0]):
+        raise ValueError("fewer correspondences than the problem names")
+    result = np.zeros(1, L.SIM3OPT_RESULT_DTYPE)
+    keep = np.zeros(int(n1), np.uint8)
+    h = (ctx if ctx is not None else _ctx(device)).handle
+    L.check(L.lib().orbg_optimize_sim3(h, L.ptr(problem), L.ptr(corrs), L.ptr(init), int(n1),
+                                       L.ptr(result), L.ptr(keep)), "orbg_optimize_sim3")
+    return result[0], keep
+
+
+def OptimizeSim3(T1w, T2w, K1, K2, Xw1, Xw2, obs1, obs2, inv_sigma2_1, inv_sigma2_2, index1, n1,
+                 R12, t12, s12, th2=10.0, bFixScale=False, device=0):
+    """Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale)
+    (Optimizer.cc:1366-1578) on the device.
+
+    T1w / T2w: pKF1 / pKF2 GetPose(); K1 / K2: mK (3x3, or fx, fy, cx, cy).  Per compacted
+    correspondence (the pointer tests of :1426-1463 stay with the caller): Xw1 / Xw2 the world
+    positions of pMP1 / pMP2, obs1 / obs2 the undistorted keypoints, inv_sigma2_* =
+    mvInvLevelSigma2[octave], index1 the slot in vpMatches1 (n1 = its size).  R12, t12, s12:
+    the Sim3 to refine (float, as Sim3Solver returns it).
+
+    Returns (nIn, (q, t, s), keep): the return value, g2oS12 in double (q = x, y, z, w) and
+    keep bool [n1], True where vpMatches1[j] is still set."""
+    p, c, h = sim3opt_records(T1w, T2w, K1, K2, Xw1, Xw2, obs1, obs2, inv_sigma2_1,
+                              inv_sigma2_2, index1, R12, t12, s12, th2, bFixScale)
+    r, keep = optimize_sim3(p, c, h, n1, device=device)
+    return int(r["ninliers"]), (r["q"].copy(), r["t"].copy(), float(r["s"])), keep.astype(bool)
+
+
+def OptimizeSim3Batch(problems, device=0):
+    """OptimizeSim3 over a list of candidates in one launch
+    (orbg_optimize_sim3_batch_device).  Each item is a dict of OptimizeSim3's arguments
+    (th2 and bFixScale optional).  Returns a list of (nIn, (q, t, s), keep)."""
+    if not problems:
+        return []
+    recs = [sim3opt_records(*[d[k] for k in ("T1w", "T2w", "K1", "K2", "Xw1", "Xw2", "obs1", "obs2",
+                                             "inv_sigma2_1", "inv_sigma2_2", "index1", "R12", "t12",
+                                             "s12")], d.get("th2", 10.0), d.get("bFixScale", False))
+            for d in problems]
+    n1s = [int(d["n1"]) for d in problems]
+    nmax = max(len(c) for _, c, _ in recs)
+    if nmax > SIM3OPT_MAX_N:
+        raise L.OrbgError(L.ORBG_ENOTSUP, "OptimizeSim3: more than %d correspondences" % SIM3OPT_MAX_N)
+    for (_, c, _), n1 in zip(recs, n1s):
+        if len(c) and not (0 <= c["index1"].min() and c["index1"].max() < n1):
+            raise ValueError("index1 outside [0, n1)")
+    res, keep = optimize_sim3_batch(np.concatenate([p for p, _, _ in recs]), [c for _, c, _ in recs],
+                                    np.concatenate([h for _, _, h in recs]), max(max(n1s), 1),
+                                    device=device)
+    return [(int(r["ninliers"]), (r["q"].copy(), r["t"].copy(), float(r["s"])),
+             keep[i, :n1s[i]].astype(bool)) for i, r in enumerate(res)]
+
+
+def optimize_sim3_batch(problems, corr_list, init, n1cap, cap=None, ctx=None, device=0):
+    """orbg_optimize_sim3_batch_device from host records: uploads, launches once on the context
+    stream, downloads.  corr_list[p] = candidate p's records; cap defaults to the smallest
+    multiple of 64 that holds the longest.  Returns (SIM3OPT_RESULT_DTYPE [npairs], keep uint8
+    [npairs][n1cap])."""
+    import torch
+    problems = np.ascontiguousarray(problems, L.SIM3OPT_PROBLEM_DTYPE).reshape(-1)
+    init = np.ascontiguousarray(init, L.SIM3_HYP_DTYPE).reshape(-1)
+    npairs = len(problems)
+    if cap is None:
+        cap = max(64, (max([len(c) for c in corr_list] + [1]) + 63) // 64 * 64)
+    corrs = np.zeros((npairs, cap), L.SIM3OPT_CORR_DTYPE)
+    for i, c in enumerate(corr_list):
+        corrs[i, :len(c)] = c
+
+    def up(a):
+        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
+    c_ = ctx if ctx is not None else _ctx(device)
+    d_p, d_c, d_h = up(problems), up(corrs), up(init)
+    d_r = torch.zeros(npairs * L.SIM3OPT_RESULT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+    d_k = torch.zeros((npairs, int(n1cap)), dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    L.check(L.lib().orbg_optimize_sim3_batch_device(
+        c_.handle, d_p.data_ptr(), d_c.data_ptr(), d_h.data_ptr(), npairs, int(cap),
+        d_r.data_ptr(), d_k.data_ptr(), int(n1cap)), "orbg_optimize_sim3_batch_device")
+    c_.sync()
+    return d_r.cpu().numpy().view(L.SIM3OPT_RESULT_DTYPE), d_k.cpu().numpy()
 
 
 def vertex_csr(edges, field, nvert):
