@@ -69,6 +69,9 @@
  *                                     Optimizer::LocalBundleAdjustment  src/Optimizer.cc:633-979
  *   orbg_optimize_sim3 .............. Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2,
  *                                     bFixScale)  src/Optimizer.cc:1366-1578 (LoopClosing.cc:598)
+ *   orbg_pnp_solve .................. PnPsolver(F, vpMapPointMatches) + SetRansacParameters +
+ *                                     iterate / find  src/PnPsolver.cc:67-900
+ *                                     (Tracking::Relocalization, Tracking.cc:2017-2060)
  *
  * Batched, device-resident entry points (orbg_*_device) run the same kernels over many
  * frames at once; they exist for the batched-sequence mode and the bench.
@@ -1423,6 +1426,128 @@ int orbg_optimize_sim3_batch_device(orbg_ctx *ctx, const orbg_sim3opt_problem *d
                                     const orbg_sim3opt_corr *d_corrs, const orbg_sim3_hyp *d_init,
                                     int npairs, int cap, orbg_sim3opt_result *d_results,
                                     uint8_t *d_keep, int n1cap);
+
+/* ---------------- PnPsolver (Tracking::Relocalization) ----------------
+ * PnPsolver(F, vpMapPointMatches) + SetRansacParameters + iterate / find (src/PnPsolver.cc:
+ * 67-340, EPnP proper :342-900; Tracking.cc:1958-2180), every RANSAC iteration of every
+ * candidate KeyFrame evaluated in one batch.
+ *
+ * The caller compacts the correspondences (PnPsolver.cc:79-101: the pointer test and isBad()
+ * stay on the host): correspondence i holds Xw = pMP->GetWorldPos(), uv = mvKeysUn[k].pt,
+ * sigma2 = mvLevelSigma2[octave] and index = mvKeyPointIndices[i] = k, the slot in
+ * vpMapPointMatches.  The device forms mvMaxError[i] = sigma2 * th2 as a float product.
+ *
+ * An iteration is EPnP's compute_pose (:477-525) on its min_set sampled correspondences, in
+ * fp64: centroid and PCA control points, barycentric coordinates, M^T M and its four
+ * eigenvectors of least eigenvalue, L_6x10 and rho, the three linearised beta starts, five
+ * Gauss-Newton steps each, compute_R_and_t (solve_for_sign on the first point's depth; row 2
+ * of R negated when det < 0, as :618-622) and the candidate of least mean reprojection error
+ * (compared with <: a NaN never wins, candidate 1 stands when all are NaN).  Then CheckInliers
+ * (:308-339) with the reference's types: Xc, Yc the double sums rounded to float, invZc =
+ * (float)(1 / double sum), ue / ve in double, distX, distY, error2 in float, error2 <
+ * mvMaxError[i] strict (a NaN fails).  A hypothesis that is not finite counts 0 inliers, with
+ * an all-zero mask and an all-zero hypothesis.
+ *
+ * Departures: the 12x12 and 3x3 symmetric eigen problems (cvSVD of M^T M and of PW0^T PW0)
+ * are solved by a fixed number of cyclic Jacobi sweeps in fp64; the 3x3 SVD of
+ * estimate_R_and_t by one-sided Jacobi; the inverse of the control-point matrix
+ * (cvInvert(CV_SVD)) is formed from the orthonormal PCA axes; the beta starts
+ * (cvSolve(CV_SVD)) are Householder least squares, as the Gauss-Newton steps are in the
+ * reference (qr_solve).  These differ from the reference only for rank-deficient systems,
+ * e.g. exactly coplanar samples, where cvSVD returns the minimum-norm solution and this code
+ * a hypothesis that is not finite (0 inliers).  The sums over a sample's points run in index
+ * order.  The sign of a PCA axis is the SVD routine's choice in the reference, and the pose of
+ * a noisy sample depends on it (a flipped axis mirrors the control tetrahedron); here every
+ * axis has its component of largest magnitude positive.  For min_set = 4 (and 5) M^T M has an exactly four-dimensional null space, the four
+ * eigenvectors are an arbitrary basis of it and the beta starts depend on that basis: there
+ * the hypotheses are implementation-defined (here: the basis the Jacobi sweeps end with, in
+ * ascending eigenvalue order), as they are for cvSVD.
+ *
+ * The random draws are an input: samples[it][0 .. min_set) = the correspondence indices of
+ * iteration it, which the reference takes from rand() (DUtils::Random::RandomInt,
+ * PnPsolver.cc:191-201).
+ *
+ * Acceptance is the reference's rule (:209-255) from a fresh solver over iterations
+ * 0 .. iterations - 1 with best = 0: an iteration with count >= min_inliers and count > best
+ * (strict: ties keep the earlier one) becomes the best, a "record iteration"; then Refine()
+ * runs on the best set so far (EPnP on all its inliers, then CheckInliers), ok = refined
+ * count > min_inliers (strict).  The first iteration with count >= min_inliers whose current
+ * best has ok is the hit and returns the refined pose, count and mask.  Refine's outcome
+ * depends on the best set alone, so it is evaluated once per record iteration: refines[it] =
+ * {valid = 1, count, ok, hyp} and refined_masks[it] at a record iteration, all zero elsewhere.
+ * Without a hit nomore = 1 and the result is the last record's unrefined hypothesis, count and
+ * mask (refined = 0), or all zero if there was none.  N < min_inliers runs nothing and sets
+ * nomore = 1.  (After a hit a later iterate() call hits again at the next iteration with
+ * count >= min_inliers, as Refine reruns on the unchanged best set.) */
+#define ORBG_PNP_MAX_SET 8
+typedef struct {
+    float fx, fy, cx, cy;            /* F.fx, F.fy, F.cx, F.cy */
+    int32_t n;                       /* N, the correspondences of this candidate */
+    int32_t min_set;                 /* mRansacMinSet, 4 .. 8 */
+    int32_t min_inliers;             /* mRansacMinInliers as SetRansacParameters adjusted it */
+    int32_t iterations;              /* mRansacMaxIts (orbg_pnp_ransac_parameters) */
+    float th2;                       /* th2 of SetRansacParameters (Tracking: 5.991) */
+} orbg_pnp_problem;
+typedef struct {
+    float Xw[3];                     /* pMP->GetWorldPos() */
+    float uv[2];                     /* F.mvKeysUn[index].pt */
+    float sigma2;                    /* F.mvLevelSigma2[kp.octave] */
+    int32_t index;                   /* mvKeyPointIndices[i] */
+} orbg_pnp_corr;
+typedef struct {
+    double R[9], t[3];               /* mRi (row-major), mti */
+} orbg_pnp_hyp;
+typedef struct {
+    int32_t valid;                   /* 1 at a record iteration */
+    int32_t count;                   /* mnRefinedInliers */
+    int32_t ok;                      /* Refine()'s return value */
+    int32_t pad;
+    orbg_pnp_hyp hyp;                /* the refined mRi, mti */
+} orbg_pnp_refine;
+typedef struct {
+    int32_t hit_iter, best_iter, ninliers, nomore, refined;
+    float Tcw[12];                   /* rows 0..2 of mRefinedTcw / mBestTcw: the double pose
+                                        rounded once, as convertTo(CV_32F); zeros if none */
+} orbg_pnp_result;
+/* PnPsolver::SetRansacParameters (:121-152) for N = n correspondences, type for type:
+ * nMinInliers = (int)(N * epsilon) through float, raised to min_inliers and min_set; epsilon
+ * raised to (float)nMinInliers / N; iterations = 1 when nMinInliers == N, else
+ * ceil(log(1 - prob) / log(1 - pow(epsilon, 3))) in double; max(1, min(iterations, max_its)).
+ * Tracking uses (0.99, 10, 300, 4, 0.5f) and th2 = 5.991f.  ORBG_EINVAL for n < 1 (the
+ * reference divides by N) or a NULL output.  Host arithmetic only: no GPU, no context. */
+int orbg_pnp_ransac_parameters(double prob, int min_inliers, int max_its, int min_set,
+                               float epsilon, int n, int *min_inliers_out, int *iterations_out);
+/* One candidate from host arrays: corrs[problem->n], samples[problem->iterations]
+ * [problem->min_set], n1 = vpMapPointMatches.size().  Outputs: result, inliers[n1] (vbInliers
+ * as bytes) and, where not NULL, counts[iterations] (mnInliersi), hyps[iterations],
+ * masks[iterations][ceil(n / 64)] (bit i % 64 of word i / 64 = mvbInliersi[i]),
+ * refines[iterations] and refined_masks[iterations][ceil(n / 64)].  ORBG_EINVAL for a NULL
+ * context or required pointer, an index outside [0, n1), min_set outside 4 .. 8, a sample
+ * index outside [0, n) or one repeated within its sample; ORBG_ENOTSUP past 8192
+ * correspondences.  Runs the batched kernels with ncand = 1 (bit-identical results).
+ * Synchronises. */
+int orbg_pnp_solve(orbg_ctx *ctx, const orbg_pnp_problem *problem, const orbg_pnp_corr *corrs,
+                   const int32_t *samples, int n1, int32_t *counts, orbg_pnp_hyp *hyps,
+                   uint64_t *masks, orbg_pnp_refine *refines, uint64_t *refined_masks,
+                   orbg_pnp_result *result, uint8_t *inliers);
+/* Batched, device memory: candidate p = d_problems[p] with d_corrs + p * cap and d_samples +
+ * (p * max_its + it) * ORBG_PNP_MAX_SET (the first min_set entries are read); cap a multiple
+ * of 64 (ORBG_ENOTSUP past 8192), d_problems[p].n <= cap and .iterations <= max_its (a count
+ * outside that, or a min_set outside 4 .. 8, runs nothing; more iterations are cut at
+ * max_its).  Outputs d_counts[ncand][max_its], d_hyps[ncand][max_its], d_masks[ncand][max_its]
+ * [cap / 64], d_refines[ncand][max_its], d_refined_masks[ncand][max_its][cap / 64],
+ * d_results[ncand], d_inliers[ncand][n1cap] (an index outside [0, n1cap) is not written).
+ * Iterations past a candidate's own and mask words past its n are zero; a sample with an
+ * index outside [0, n) or a repeated one is a degenerate iteration (count 0, zero mask, zero
+ * hypothesis).  Context stream, no host synchronisation, no allocation.  No floating-point
+ * atomics and fixed summation orders: results are reproducible run to run and equal to
+ * orbg_pnp_solve's. */
+int orbg_pnp_solve_batch_device(orbg_ctx *ctx, const orbg_pnp_problem *d_problems,
+                                const orbg_pnp_corr *d_corrs, const int32_t *d_samples,
+                                int ncand, int cap, int max_its, int32_t *d_counts,
+                                orbg_pnp_hyp *d_hyps, uint64_t *d_masks,
+                                orbg_pnp_refine *d_refines, uint64_t *d_refined_masks,
+                                orbg_pnp_result *d_results, uint8_t *d_inliers, int n1cap);
 
 #ifdef __cplusplus
 }

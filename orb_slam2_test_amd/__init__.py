@@ -18,8 +18,9 @@ from .optimizer import PoseOptimization, linearize_local_ba, OptimizeSim3, Optim
 from .vocabulary import ORBVocabulary, BowVector, FeatureVector  # noqa: F401
 from .keyframedatabase import KeyFrameDatabase  # noqa: F401
 from .sim3solver import Sim3Solver  # noqa: F401
+from .pnpsolver import PnPsolver  # noqa: F401
 
 __all__ = ["ORBextractor", "ORBmatcher", "Frame", "MapPointProjections", "StereoFrame", "PoseOptimization", "linearize_local_ba", "OptimizeSim3", "OptimizeSim3Batch",
-           "ORBVocabulary", "BowVector", "FeatureVector", "KeyFrameDatabase", "Sim3Solver",
+           "ORBVocabulary", "BowVector", "FeatureVector", "KeyFrameDatabase", "Sim3Solver", "PnPsolver",
            "KP_DTYPE",
            "EDGE_DTYPE", "EDGE_OUT_DTYPE", "POSE_DTYPE"]

@@ -67,6 +67,18 @@ SIM3_CORR_DTYPE = np.dtype([("Xw1", "<f4", 3), ("Xw2", "<f4", 3), ("sigma2_1", "
 SIM3_HYP_DTYPE = np.dtype([("R", "<f4", 9), ("t", "<f4", 3), ("s", "<f4")])
 SIM3_RESULT_DTYPE = np.dtype([("hit_iter", "<i4"), ("best_iter", "<i4"), ("ninliers", "<i4"),
                               ("nomore", "<i4"), ("hyp", SIM3_HYP_DTYPE)])
+# PnPsolver records (orbg_pnp_problem, orbg_pnp_corr, orbg_pnp_hyp, orbg_pnp_refine, orbg_pnp_result)
+PNP_MAX_SET = 8
+PNP_PROBLEM_DTYPE = np.dtype([("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"),
+                              ("n", "<i4"), ("min_set", "<i4"), ("min_inliers", "<i4"),
+                              ("iterations", "<i4"), ("th2", "<f4")])
+PNP_CORR_DTYPE = np.dtype([("Xw", "<f4", 3), ("uv", "<f4", 2), ("sigma2", "<f4"),
+                           ("index", "<i4")])
+PNP_HYP_DTYPE = np.dtype([("R", "<f8", 9), ("t", "<f8", 3)])
+PNP_REFINE_DTYPE = np.dtype([("valid", "<i4"), ("count", "<i4"), ("ok", "<i4"), ("pad", "<i4"),
+                             ("hyp", PNP_HYP_DTYPE)])
+PNP_RESULT_DTYPE = np.dtype([("hit_iter", "<i4"), ("best_iter", "<i4"), ("ninliers", "<i4"),
+                             ("nomore", "<i4"), ("refined", "<i4"), ("Tcw", "<f4", 12)])
 # OptimizeSim3 records (orbg_sim3opt_problem, orbg_sim3opt_corr, orbg_sim3opt_result)
 SIM3OPT_PROBLEM_DTYPE = np.dtype([("T1w", "<f4", 12), ("T2w", "<f4", 12), ("fx1", "<f4"),
                                   ("fy1", "<f4"), ("cx1", "<f4"), ("cy1", "<f4"), ("fx2", "<f4"),
@@ -388,6 +400,11 @@ def lib():
         "orbg_sim3_solve": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
         "orbg_sim3_solve_batch_device": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp,
                                                i32]),
+        "orbg_pnp_ransac_parameters": (i32, [C.c_double, i32, i32, i32, f32, i32, P(C.c_int32),
+                                             P(C.c_int32)]),
+        "orbg_pnp_solve": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+        "orbg_pnp_solve_batch_device": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp,
+                                              vp, vp, i32]),
         "orbg_optimize_sim3": (i32, [vp, vp, vp, vp, i32, vp, vp]),
         "orbg_optimize_sim3_batch_device": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, i32]),
     }

@@ -47,6 +47,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <list>
 #include <map>
@@ -1288,6 +1289,162 @@ int DistinctiveDescriptorIndex(orbg_ctx *ctx, const std::vector<Mat> &vDescripto
     check(orbg_distinctive_descriptor(ctx, d.data(), n, &best), "orbg_distinctive_descriptor");
     return best;
 }
+
+// PnPsolver(F, vpMapPointMatches) + SetRansacParameters + iterate / find (PnPsolver.cc:67-340;
+// Tracking::Relocalization, Tracking.cc:2010-2080).  The constructor compacts the matches as
+// :79-101 does (the pointer test and isBad() stay on the host); the first iterate() draws
+// mRansacMaxIts samples from rand() as the reference does (RandomInt with the swap-remove of
+// :191-201), evaluates every iteration and every Refine() in one orbg_pnp_solve, and serves
+// this and later calls from the downloaded records by the sequential rule.  The reference's
+// loop runs while `mnIterations < mRansacMaxIts || nCurrentIterations < nIterations` (an OR),
+// so the first iterate(5) already runs to mRansacMaxIts unless it hits; here the evaluated
+// iterations are all there are, and bNoMore is set once they are used up.
+//
+// MatT: cv::Mat (MatT::eye(4, 4, CV_32F), at<float>, empty()).
+template <class FrameT, class MapPointT, class MatT>
+class PnPsolver {
+public:
+    PnPsolver(orbg_ctx *ctx, const FrameT &F, const std::vector<MapPointT *> &vpMapPointMatches)
+        : ctx_(ctx), n1_((int)vpMapPointMatches.size())
+    {
+        for (size_t i = 0; i < vpMapPointMatches.size(); i++) {
+            MapPointT *pMP = vpMapPointMatches[i];
+            if (!pMP || pMP->isBad()) continue;
+            const auto &kp = F.mvKeysUn[i];
+            const MatT Pos = pMP->GetWorldPos();
+            orbg_pnp_corr c;
+            for (int d = 0; d < 3; d++) c.Xw[d] = Pos.template at<float>(d);
+            c.uv[0] = kp.pt.x;
+            c.uv[1] = kp.pt.y;
+            c.sigma2 = F.mvLevelSigma2[kp.octave];
+            c.index = (int32_t)i;
+            corrs_.push_back(c);
+        }
+        prob_.fx = F.fx, prob_.fy = F.fy, prob_.cx = F.cx, prob_.cy = F.cy;
+        prob_.n = (int32_t)corrs_.size();
+        SetRansacParameters();
+    }
+
+    void SetRansacParameters(double probability = 0.99, int minInliers = 8, int maxIterations = 300,
+                             int minSet = 4, float epsilon = 0.4f, float th2 = 5.991f)
+    {
+        prob_.min_set = minSet;
+        prob_.th2 = th2;
+        int mi = std::max(minInliers, minSet), its = std::max(1, maxIterations);
+        if (prob_.n > 0)
+            check(orbg_pnp_ransac_parameters(probability, minInliers, maxIterations, minSet, epsilon,
+                                             prob_.n, &mi, &its),
+                  "orbg_pnp_ransac_parameters");
+        prob_.min_inliers = mi;
+        prob_.iterations = its;
+        evaluated_ = false;
+    }
+
+    MatT find(std::vector<bool> &vbInliers, int &nInliers)
+    {
+        bool bFlag;
+        return iterate(prob_.iterations, bFlag, vbInliers, nInliers);
+    }
+
+    MatT iterate(int nIterations, bool &bNoMore, std::vector<bool> &vbInliers, int &nInliers)
+    {
+        bNoMore = false;
+        vbInliers.clear();
+        nInliers = 0;
+        const int N = prob_.n, its = prob_.iterations;
+        if (N < prob_.min_inliers || N < prob_.min_set) {
+            bNoMore = true;
+            return MatT();
+        }
+        if (!evaluated_) evaluate();
+        int cur = 0;
+        while ((mnIterations_ < its || cur < nIterations) && mnIterations_ < (int)counts_.size()) {
+            const int i = mnIterations_;
+            cur++;
+            mnIterations_++;
+            if (counts_[i] < prob_.min_inliers) continue;
+            if (counts_[i] > mnBestInliers_) {
+                mnBestInliers_ = counts_[i];
+                best_ = i;
+            }
+            const orbg_pnp_refine &r = refines_[best_];  // Refine() on the best set so far
+            if (r.ok) {
+                nInliers = r.count;
+                scatter(&rmasks_[(size_t)best_ * words_], vbInliers);
+                return pose(r.hyp);
+            }
+        }
+        if (mnIterations_ >= its) {
+            bNoMore = true;
+            if (best_ >= 0) {
+                nInliers = mnBestInliers_;
+                scatter(&masks_[(size_t)best_ * words_], vbInliers);
+                return pose(hyps_[best_]);
+            }
+        }
+        return MatT();
+    }
+
+private:
+    void evaluate()
+    {
+        const int N = prob_.n, its = prob_.iterations, m = prob_.min_set;
+        std::vector<int32_t> samples((size_t)its * m), avail;
+        for (int it = 0; it < its; it++) {
+            avail.resize(N);
+            for (int i = 0; i < N; i++) avail[i] = i;
+            for (int k = 0; k < m; k++) {
+                const int d = (int)avail.size();
+                const int randi = (int)(((double)rand() / ((double)RAND_MAX + 1.0)) * d);
+                samples[(size_t)it * m + k] = avail[randi];
+                avail[randi] = avail.back();
+                avail.pop_back();
+            }
+        }
+        words_ = (N + 63) / 64;
+        counts_.assign(its, 0);
+        hyps_.resize(its);
+        refines_.resize(its);
+        masks_.assign((size_t)its * words_, 0);
+        rmasks_.assign((size_t)its * words_, 0);
+        std::vector<uint8_t> inl((size_t)std::max(n1_, 1));
+        orbg_pnp_result res;
+        check(orbg_pnp_solve(ctx_, &prob_, corrs_.data(), samples.data(), n1_, counts_.data(),
+                             hyps_.data(), masks_.data(), refines_.data(), rmasks_.data(), &res,
+                             inl.data()),
+              "orbg_pnp_solve");
+        evaluated_ = true;
+        mnIterations_ = 0;
+    }
+
+    void scatter(const uint64_t *mask, std::vector<bool> &vbInliers) const
+    {
+        vbInliers.assign((size_t)n1_, false);
+        for (int i = 0; i < prob_.n; i++)
+            if ((mask[i >> 6] >> (i & 63)) & 1u) vbInliers[corrs_[i].index] = true;
+    }
+
+    static MatT pose(const orbg_pnp_hyp &h)
+    {
+        MatT T = MatT::eye(4, 4, CV_32F);
+        for (int r = 0; r < 3; r++) {
+            for (int c = 0; c < 3; c++) T.template at<float>(r, c) = (float)h.R[3 * r + c];
+            T.template at<float>(r, 3) = (float)h.t[r];
+        }
+        return T;
+    }
+
+    orbg_ctx *ctx_;
+    int n1_;
+    orbg_pnp_problem prob_{};
+    std::vector<orbg_pnp_corr> corrs_;
+    bool evaluated_ = false;
+    int mnIterations_ = 0, mnBestInliers_ = 0, best_ = -1, words_ = 0;
+    std::vector<int32_t> counts_;
+    std::vector<orbg_pnp_hyp> hyps_;
+    std::vector<orbg_pnp_refine> refines_;
+    std::vector<uint64_t> masks_, rmasks_;
+};
 
 }  // namespace ref
 }  // namespace orbg_compat

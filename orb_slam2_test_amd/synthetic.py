@@ -565,3 +565,46 @@ def sim3_scene(seed=DEFAULT_SEED, n=100, outlier_frac=0.3, noise=0.02, fix_scale
             "sigma2_1": (1.2 ** (2 * oct1)).astype(f), "sigma2_2": (1.2 ** (2 * oct2)).astype(f),
             "index1": index1.astype(np.int32), "n1": int(n1), "n": int(n),
             "fix_scale": bool(fix_scale), "R12": R, "t12": t, "s12": s, "outlier": outlier}
+
+
+PNP_K = (517.3, 516.5, 318.6, 255.3)
+
+
+def pnp_scene(seed=DEFAULT_SEED, n=100, inliers=60, noise=0.0, K=PNP_K, n1=None,
+              width=640.0, height=480.0):
+    """n 3D-2D correspondences of a lost Frame against a candidate KeyFrame's map points
+    (PnPsolver's input after the constructor's compaction), exactly `inliers` of them true.
+    Points lie in x [-4, 4], y [-3, 3], z [4, 20] of the camera at the planted pose Tcw;
+    their projections get Gaussian `noise` px, and the n - inliers outliers (at random
+    places) are replaced by image points uniform in the frame, at least 40 px from the true
+    projection.  Octaves are uniform in 0..7 with sigma2 = 1.2^(2 octave).
+    n1 = vpMapPointMatches.size(): None gives index = 0..n-1, a number gives n distinct slots
+    of [0, n1) in random order.
+
+    Returns float32 arrays: Xw [n][3], uv [n][2], sigma2, index, n1, n, K, and the planted
+    Tcw (4x4 float64) with the outlier flags."""
+    rng = np.random.default_rng(seed)
+    fx, fy, cx, cy = (float(k) for k in K)
+    Tcw = _random_pose(rng, 0.6, 3.0)
+    Pc = rng.uniform([-4.0, -3.0, 4.0], [4.0, 3.0, 20.0], (n, 3))
+    Xw = ((Pc - Tcw[:3, 3]) @ Tcw[:3, :3]).astype(np.float32)   # rows: R^T (P - t)
+    Pc = Xw.astype(np.float64) @ Tcw[:3, :3].T + Tcw[:3, 3]     # of the float32 points
+    proj = np.stack([fx * Pc[:, 0] / Pc[:, 2] + cx, fy * Pc[:, 1] / Pc[:, 2] + cy], 1)
+    uv = proj + rng.normal(0.0, 1.0, (n, 2)) * noise
+    outlier = np.zeros(n, bool)
+    outlier[rng.permutation(n)[:n - int(inliers)]] = True
+    for i in np.flatnonzero(outlier):
+        while True:
+            cand = rng.uniform([0.0, 0.0], [width, height])
+            if np.hypot(*(cand - proj[i])) >= 40.0:
+                break
+        uv[i] = cand
+    octave = rng.integers(0, 8, n)
+    if n1 is None:
+        n1, index = n, np.arange(n)
+    else:
+        index = rng.permutation(n1)[:n]
+    f = np.float32
+    return {"Xw": Xw, "uv": uv.astype(f), "sigma2": (1.2 ** (2 * octave)).astype(f),
+            "index": index.astype(np.int32), "n1": int(n1), "n": int(n),
+            "K": tuple(float(k) for k in K), "Tcw": Tcw, "outlier": outlier}
