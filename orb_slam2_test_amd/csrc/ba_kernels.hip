@@ -16,31 +16,13 @@
 
 #include "../../include/orbg.h"
 #include "orbg_internal.h"
+#include "orbg_device.h"
+#include "g2o_math.h"
 
 namespace orbg {
 
 void prof_begin(void *prof, hipStream_t s, const char *n, hipEvent_t *a);
 void prof_end(void *prof, hipStream_t s, const char *n, hipEvent_t a);
-
-// LDS written by some lanes of a wave, then read by others (the hardware keeps one wave's
-// LDS ops in order; the fence keeps the compiler from reordering them)
-__device__ __forceinline__ void wave_sync_lds_ba()
-{
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ void quat_rotate(const double q[4], const double v[3], double o[3])
-{
-    double uv[3] = {q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2],
-                    q[0] * v[1] - q[1] * v[0]};
-    uv[0] += uv[0];
-    uv[1] += uv[1];
-    uv[2] += uv[2];
-    o[0] = v[0] + q[3] * uv[0] + (q[1] * uv[2] - q[2] * uv[1]);
-    o[1] = v[1] + q[3] * uv[1] + (q[2] * uv[0] - q[0] * uv[2]);
-    o[2] = v[2] + q[3] * uv[2] + (q[0] * uv[1] - q[1] * uv[0]);
-}
 
 // computeError (types_six_dof_expmap.h:90-95, 122-127): Xc = q X + t, then the mono
 // projection in double, or the stereo cam_project with its float invz and float bf
@@ -48,7 +30,7 @@ __device__ __forceinline__ void quat_rotate(const double q[4], const double v[3]
 __device__ __forceinline__ void ba_edge_error(const orbg_pose &P, const double X[3],
                                               const orbg_edge &e, double xc[3], double err[3])
 {
-    quat_rotate(P.q, X, xc);
+    q_rotate(P.q, X, xc);
     xc[0] += P.t[0];
     xc[1] += P.t[1];
     xc[2] += P.t[2];
@@ -206,14 +188,8 @@ __device__ __forceinline__ void ba_linearize_edge(const orbg_pose &P, const doub
     const double fx = e.fx, fy = e.fy;
     L.D = e.stereo ? 3 : 2;
     // rotation matrix (Eigen toRotationMatrix)
-    const double *q = P.q;
-    const double tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2];
-    const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
-    const double txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
-    const double tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
-    const double R[3][3] = {{1 - (tyy + tzz), txy - twz, txz + twy},
-                            {txy + twz, 1 - (txx + tzz), tyz - twx},
-                            {txz - twy, tyz + twx, 1 - (txx + tyy)}};
+    double R[3][3];
+    q_to_rot(P.q, R);
     if (!e.stereo) {
         const double t02 = -x / z * fx, t12 = -y / z * fy;
 #pragma unroll
@@ -540,7 +516,7 @@ __device__ __forceinline__ void ba_pose_slice(const orbg_pose &P, const double *
             __builtin_amdgcn_mbcnt_hi((uint32_t)(m3 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m3, 0));
         const int nrow = 2 * __popcll(m2) + __popcll(m3);
         nr16 = (nrow + 15) & ~15;
-        wave_sync_lds_ba();  // the previous slice's reads of rl are done (in-order LDS)
+        wave_sync_lds();  // the previous slice's reads of rl are done (in-order LDS)
 #pragma unroll
         for (int k = 0; k < 3; k++)
             if (k < D)
@@ -552,7 +528,7 @@ __device__ __forceinline__ void ba_pose_slice(const orbg_pose &P, const double *
             for (int c = 0; c < BA_ROW; c += 2)
                 *(double2 *)(rl + (nrow + lane) * BA_ROW + c) = make_double2(0.0, 0.0);
     }
-    wave_sync_lds_ba();
+    wave_sync_lds();
     const int k = lane >> 4, b = (lane >> 2) & 3, t = lane & 3;
     const int ia = 4 * (b >> 1) + t, ib = 4 * (b & 1) + t;  // column 7 is the weight slot: 0
     double c4[4] = {0, 0, 0, 0};
@@ -602,14 +578,14 @@ __device__ __forceinline__ void ba_pose_slice(const orbg_pose &P, const double *
                 }
             }
         }
-        wave_sync_lds_ba();  // the previous slice's reads of rl are done (in-order LDS)
+        wave_sync_lds();  // the previous slice's reads of rl are done (in-order LDS)
 #pragma unroll
         for (int k = 0; k < 3; k++)
 #pragma unroll
             for (int c = 0; c < BA_ROW; c += 2)
                 *(double2 *)(rl + (3 * lane + k) * BA_ROW + c) = make_double2(v[k][c], v[k][c + 1]);
     }
-    wave_sync_lds_ba();
+    wave_sync_lds();
     const int nrow = 3 * ne;
     const int i = lane & 15, k = lane >> 4;  // A: (row i of the 16x4 tile, k); B: (k, column i)
     const int col = i < 7 ? i : 7;           // padded columns read the weight and are zeroed
@@ -749,10 +725,10 @@ __device__ __forceinline__ void ba_special_point(const orbg_pose *__restrict__ p
                 ba_point_share(L, c);
             }
         }
-        wave_sync_lds_ba();
+        wave_sync_lds();
 #pragma unroll
         for (int k = 0; k < 12; k++) sh[k][lane] = c[k];
-        wave_sync_lds_ba();
+        wave_sync_lds();
         const int n = min(64, a1 - c0);
         if (lane < 12)
             for (int j = 0; j < n; j++) acc += sh[lane][j];

@@ -4,7 +4,7 @@
 // (ba_kernels.hip), the error pass and the Schur solve (schur_kernels.hip):
 //   k_ba_update    SparseOptimizer::update (sparse_optimizer.cpp): thread per pose,
 //                  VertexSE3Expmap::oplusImpl (types_six_dof_expmap.h:73-76: estimate =
-//                  SE3Quat::exp(dx) * estimate, se3_device.h; fixed poses untouched), and per
+//                  SE3Quat::exp(dx) * estimate, g2o_math.h; fixed poses untouched), and per
 //                  point coordinate, VertexSBAPointXYZ::oplusImpl (estimate += dx)
 //   k_lm_partial   the scalars the LM reads, each a deterministic two-level reduction:
 //   k_lm_final       activeRobustChi2 (sum of rho over the active edges), computeScale
@@ -17,7 +17,7 @@
 #include "../../include/orbg.h"
 #include "orbg_internal.h"
 #include "orbg_device.h"
-#include "se3_device.h"
+#include "g2o_math.h"
 
 #pragma clang fp contract(off)
 

@@ -3865,17 +3865,6 @@ extern "C" int orbg_ba_graph_errors(orbg_ctx *c, orbg_ba_graph *g, const orbg_po
     return ORBG_OK;
 }
 
-// g2o's pow(2 rho - 1, 3) as the device's lm_cube (se3_device.h): the exact cube as a
-// double-double, rounded once
-static double lm_cube_host(double t)
-{
-    const double h = t * t;
-    const double l = std::fma(t, t, -h);
-    const double ph = h * t;
-    const double pl = std::fma(h, t, -ph);
-    return ph + (pl + l * t);
-}
-
 extern "C" int orbg_ba_update_device(orbg_ctx *c, const orbg_pose *d_poses, int npose,
                                      const double *d_points, int npoint, const double *d_dx_pose,
                                      const double *d_dx_point, orbg_pose *d_poses_out,
@@ -3958,29 +3947,25 @@ extern "C" int orbg_ba_graph_optimize_ctl(orbg_ctx *c, orbg_ba_graph *g, orbg_po
     const orbg_lm_control C0{};
     const orbg_lm_control &K = ctl ? *ctl : C0;
     auto terminate = [&]() { return K.force_stop && *K.force_stop != 0; };
-    double currentChi = 0.0, lambda = 0.0, hs[4];
-    int ni = 2, nBad = 0;
+    LmState lm = {0, 2, 0, 0, 0, 0};  // the step control is g2o_math.h's
+    double hs[4] = {0, 0, 0, 0};
     bool ran = false;
     for (int it = 0; it < iterations && !terminate(); it++) {
         if (it == 0) {  // computeActiveErrors at the start (later: the last accepted trial's)
             if ((rc = chi2(sc)) || (rc = read(hs, 1))) return rc;
-            currentChi = hs[0];
-            R.initial_chi2 = currentChi;
+            lm.currentChi = hs[0];
+            R.initial_chi2 = lm.currentChi;
         }
         ran = true;
-        const double iniChi = currentChi;
         if ((rc = orbg_ba_graph_build_system(c, g, d_poses, d_points, hpl, hp, bp, hq, bq))) return rc;
         if (it == 0) {  // computeLambdaInit: tau * max |H_jj| (before any lambda)
             if (launch_lm_reduce(st, 2, 6 * g->npose, 3 * g->npoint, 0.0, hp, hq, nullptr, nullptr,
                                  nullptr, part, sc + 2) ||
                 (rc = read(hs, 3)))
                 return rc ? rc : fail(ORBG_EIO, "reduction launch");
-            lambda = 1e-5 * hs[2];
-            ni = 2;
-            nBad = 0;
         }
+        lm_begin(&lm, it, hs[2]);
         double rhoLM = 0.0;
-        int qmax = 0;
         do {
             // push
             if (g->npose)
@@ -3990,33 +3975,18 @@ extern "C" int orbg_ba_graph_optimize_ctl(orbg_ctx *c, orbg_ba_graph *g, orbg_po
                 HIPCHK(hipMemcpyAsync(sq, d_points, (size_t)g->npoint * 24, hipMemcpyDeviceToDevice, st));
             // setLambda + solve + update (the Schur solve adds lambda to its own copies of
             // the diagonal: no restoreDiagonal needed)
-            if ((rc = orbg_ba_graph_schur_solve(c, g, lambda, hpl, hp, bp, hq, bq, dxp, dxq,
+            if ((rc = orbg_ba_graph_schur_solve(c, g, lm.lambda, hpl, hp, bp, hq, bq, dxp, dxq,
                                                 (int32_t *)(sc + 3))))
                 return rc;
             if (launch_ba_update(st, d_poses, g->npose, d_points, g->npoint, dxp, dxq, d_poses,
                                  d_points) ||
-                launch_lm_reduce(st, 1, 6 * g->npose, 3 * g->npoint, lambda, dxp, dxq, bp, bq,
+                launch_lm_reduce(st, 1, 6 * g->npose, 3 * g->npoint, lm.lambda, dxp, dxq, bp, bq,
                                  nullptr, part, sc + 1))
                 return fail(ORBG_EIO, "update / reduction launch");
             if ((rc = chi2(sc)) || (rc = read(hs, 4))) return rc;
-            double tempChi = hs[0];
             const bool ok2 = *(const int32_t *)&hs[3] != 0;
-            if (!ok2) tempChi = DBL_MAX;
-            rhoLM = currentChi - tempChi;
-            double scale = hs[1];
-            scale += 1e-3;
-            rhoLM /= scale;
             R.trials++;
-            if (rhoLM > 0 && std::isfinite(tempChi)) {  // the step is good
-                double alpha = 1. - lm_cube_host(2 * rhoLM - 1);
-                alpha = std::min(alpha, 2. / 3.);
-                const double scaleFactor = std::max(1. / 3., alpha);
-                lambda *= scaleFactor;
-                ni = 2;
-                currentChi = tempChi;
-            } else {  // pop
-                lambda *= ni;
-                ni *= 2;
+            if (!lm_trial(&lm, ok2, hs[0], hs[1], &rhoLM)) {  // pop (else: the step is good)
                 if (g->npose)
                     HIPCHK(hipMemcpyAsync(d_poses, sp, (size_t)g->npose * sizeof(orbg_pose),
                                           hipMemcpyDeviceToDevice, st));
@@ -4024,28 +3994,15 @@ extern "C" int orbg_ba_graph_optimize_ctl(orbg_ctx *c, orbg_ba_graph *g, orbg_po
                     HIPCHK(hipMemcpyAsync(d_points, sq, (size_t)g->npoint * 24,
                                           hipMemcpyDeviceToDevice, st));
             }
-            qmax++;
-            if (K.post_trial) K.post_trial(K.user, it, qmax - 1);
-        } while (rhoLM < 0 && qmax < 10 && !terminate());
+            if (K.post_trial) K.post_trial(K.user, it, lm.qmax - 1);
+        } while (lm_retry(&lm, rhoLM) && !terminate());
         R.iterations = it + 1;
-        R.final_chi2 = currentChi;
-        R.lambda = lambda;
-        bool ok = true;  // solve() returned OK (not Terminate)
-        if (qmax == 10 || rhoLM == 0) {
-            R.terminated = 1;
-            ok = false;
-        } else {
-            if ((iniChi - currentChi) * 1e3 < iniChi)
-                nBad++;
-            else
-                nBad = 0;
-            if (nBad >= 3) {
-                R.terminated = 2;
-                ok = false;
-            }
-        }
+        R.final_chi2 = lm.currentChi;
+        R.lambda = lm.lambda;
+        const int term = lm_end(&lm, rhoLM);  // 0: solve() returned OK (not Terminate)
+        if (term) R.terminated = term;
         if (K.post_iteration) K.post_iteration(K.user, it);
-        if (!ok) break;
+        if (term) break;
     }
     if (!ran) {  // no iteration: the report's chi2 at the given estimates (g2o computes none)
         if ((rc = chi2(sc)) || (rc = read(hs, 1))) return rc;

@@ -21,7 +21,7 @@
 #include "../../include/orbg.h"
 #include "orbg_internal.h"
 #include "orbg_device.h"
-#include "se3_device.h"
+#include "g2o_math.h"
 #include "match_device.h"
 
 #pragma clang fp contract(off)
@@ -37,98 +37,6 @@ struct PoseInvSigma2 {
 
 #define PO_T 256
 #define PO_NV 28  // robust chi2, 21 lower-triangle H entries, 6 b entries
-
-// Eigen LDLT (lower, diagonal pivoting) + solve; returns isPositive()
-__device__ bool ldlt_solve6(double m[6][6], const double b[6], double x[6])
-{
-    int tr[6];
-    int sign = 0;  // 0 zero, 1 positive semidef, 2 negative semidef, 3 indefinite
-    double temp[6];
-    for (int k = 0; k < 6; k++) {
-        int big = k;
-        double bv = fabs(m[k][k]);
-        for (int i = k + 1; i < 6; i++)
-            if (fabs(m[i][i]) > bv) {
-                bv = fabs(m[i][i]);
-                big = i;
-            }
-        tr[k] = big;
-        if (k != big) {
-            for (int j = 0; j < k; j++) {
-                const double s = m[k][j];
-                m[k][j] = m[big][j];
-                m[big][j] = s;
-            }
-            for (int i = big + 1; i < 6; i++) {
-                const double s = m[i][k];
-                m[i][k] = m[i][big];
-                m[i][big] = s;
-            }
-            {
-                const double s = m[k][k];
-                m[k][k] = m[big][big];
-                m[big][big] = s;
-            }
-            for (int i = k + 1; i < big; i++) {
-                const double s = m[i][k];
-                m[i][k] = m[big][i];
-                m[big][i] = s;
-            }
-        }
-        if (k > 0) {
-            for (int j = 0; j < k; j++) temp[j] = m[j][j] * m[k][j];
-            double dot = 0;
-            for (int j = 0; j < k; j++) dot += m[k][j] * temp[j];
-            m[k][k] -= dot;
-            for (int i = k + 1; i < 6; i++) {
-                double s = 0;
-                for (int j = 0; j < k; j++) s += m[i][j] * temp[j];
-                m[i][k] -= s;
-            }
-        }
-        const double akk = m[k][k];
-        const bool valid = fabs(akk) > 0.0;
-        if (k == 0 && !valid) {
-            sign = 0;
-            for (int j = 0; j < 6; j++) tr[j] = j;
-            break;
-        }
-        if (k < 5 && valid)
-            for (int i = k + 1; i < 6; i++) m[i][k] /= akk;
-        if (sign == 0 || sign == 1) {
-            if (akk > 0) sign = 1;
-            else if (akk < 0) sign = sign == 0 ? 2 : 3;
-        } else if (sign == 2 && akk > 0) {
-            sign = 3;
-        }
-    }
-    if (!(sign == 1 || sign == 0)) return false;
-    double d[6];
-    for (int i = 0; i < 6; i++) d[i] = b[i];
-    for (int k = 0; k < 6; k++) {
-        const double s = d[k];
-        d[k] = d[tr[k]];
-        d[tr[k]] = s;
-    }
-    for (int i = 0; i < 6; i++) {
-        double s = 0;
-        for (int j = 0; j < i; j++) s += m[i][j] * d[j];
-        d[i] -= s;
-    }
-    for (int i = 0; i < 6; i++) d[i] = fabs(m[i][i]) > DBL_MIN ? d[i] / m[i][i] : 0.0;
-    for (int i = 5; i >= 0; i--) {
-        double s = 0;
-        for (int j = i + 1; j < 6; j++) s += m[j][i] * d[j];
-        d[i] -= s;
-    }
-    for (int k = 5; k >= 0; k--) {
-        const double s = d[k];
-        d[k] = d[tr[k]];
-        d[tr[k]] = s;
-    }
-    for (int i = 0; i < 6; i++) x[i] = d[i];
-    return true;
-}
 
 // ---- the unary edges ----
 __device__ __forceinline__ int pedge_error(const double q[4], const double t[3],
@@ -248,37 +156,6 @@ __device__ void po_partial(const double q[4], const double t[3], const orbg_pose
     }
 }
 
-// pinned reduction: butterfly within each wave, (w0 + w1) + (w2 + w3); result in red[0..27]
-__device__ void po_reduce(double p[PO_NV], double *wred /* [4][PO_NV] */, double *red)
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < PO_NV; j++) {
-        double v = p[j];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
-        if (lane == 0) wred[wv * PO_NV + j] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < PO_NV) {
-        const int j = threadIdx.x;
-        red[j] = (wred[j] + wred[PO_NV + j]) + (wred[2 * PO_NV + j] + wred[3 * PO_NV + j]);
-    }
-    __syncthreads();
-}
-
-__device__ __forceinline__ void unpack_sys(const double *red, double *H, double *b)
-{
-    int hi = 1;
-    for (int r = 0; r < 6; r++)
-        for (int c = 0; c <= r; c++) {
-            H[r * 6 + c] = red[hi];
-            H[c * 6 + r] = red[hi];
-            hi++;
-        }
-    for (int r = 0; r < 6; r++) b[r] = red[22 + r];
-}
-
 struct PoShared {
     double red[PO_NV];
     double wred[4 * PO_NV];
@@ -336,9 +213,7 @@ __global__ __launch_bounds__(PO_T) void k_pose_opt(const orbg_pose_edge *__restr
     bool robust = true;
     int nBad = 0;
     double p[PO_NV];
-    // lane-0 state
-    double lambda = 0, ni = 2, currentChi = 0, iniChi = 0;
-    int nBadLM = 0, qmax = 0;
+    LmState lm = {0, 2, 0, 0, 0, 0};  // lane 0's
     bool have_sys = false;
     for (int round = 0; round < 4; round++) {
         if (tid == 0) {
@@ -355,25 +230,17 @@ __global__ __launch_bounds__(PO_T) void k_pose_opt(const orbg_pose_edge *__restr
                 if (!__syncthreads_or(have_sys)) {
                     // computeActiveErrors + buildSystem at the current estimate
                     po_partial(S.q, S.t, edges, n, outlier, robust, cam, p);
-                    po_reduce(p, S.wred, S.red);
+                    wg_reduce<PO_NV>(p, S.wred, S.red);
                     if (tid == 0) {
                         for (int i = 0; i < 4; i++) S.lq[i] = S.q[i];
                         for (int i = 0; i < 3; i++) S.lt[i] = S.t[i];
-                        currentChi = S.red[0];
-                        unpack_sys(S.red, S.H, S.b);
+                        lm.currentChi = S.red[0];
+                        unpack_sys<6>(S.red, S.H, S.b);
                     }
                 }
                 if (tid == 0) {
                     have_sys = false;
-                    iniChi = currentChi;
-                    if (it == 0) {
-                        double maxd = 0;
-                        for (int j = 0; j < 6; j++) maxd = fmax(fabs(S.H[j * 7]), maxd);
-                        lambda = 1e-5 * maxd;
-                        ni = 2;
-                        nBadLM = 0;
-                    }
-                    qmax = 0;
+                    lm_begin(&lm, it, it == 0 ? lm_max_diag<6>(S.H) : 0.0);
                 }
                 for (;;) {
                     bool ok2 = false;
@@ -382,8 +249,8 @@ __global__ __launch_bounds__(PO_T) void k_pose_opt(const orbg_pose_edge *__restr
                         double Hd[6][6];
                         for (int r = 0; r < 6; r++)
                             for (int c = 0; c < 6; c++) Hd[r][c] = S.H[r * 6 + c];
-                        for (int j = 0; j < 6; j++) Hd[j][j] += lambda;
-                        ok2 = ldlt_solve6(Hd, S.b, S.x);
+                        for (int j = 0; j < 6; j++) Hd[j][j] += lm.lambda;
+                        ok2 = ldlt_solve<6>(Hd, S.b, S.x);
                         for (int i = 0; i < 4; i++) S.tq[i] = S.q[i];
                         for (int i = 0; i < 3; i++) S.tt[i] = S.t[i];
                         se3_oplus(S.tq, S.tt, S.x);
@@ -392,45 +259,18 @@ __global__ __launch_bounds__(PO_T) void k_pose_opt(const orbg_pose_edge *__restr
                     }
                     __syncthreads();
                     po_partial(S.tq, S.tt, edges, n, outlier, robust, cam, p);
-                    po_reduce(p, S.wred, S.red);
+                    wg_reduce<PO_NV>(p, S.wred, S.red);
                     if (tid == 0) {
-                        double tempChi = S.red[0];
-                        if (!ok2) tempChi = DBL_MAX;
-                        double rho = currentChi - tempChi;
-                        double scale = 0;
-                        for (int j = 0; j < 6; j++) scale += S.x[j] * (lambda * S.x[j] + S.b[j]);
-                        scale += 1e-3;
-                        rho /= scale;
-                        if (rho > 0 && isfinite(tempChi)) {
-                            double alpha = 1. - lm_cube(2 * rho - 1);
-                            alpha = fmin(alpha, 2. / 3.);
-                            const double sf = fmax(1. / 3., alpha);
-                            lambda *= sf;
-                            ni = 2;
-                            currentChi = tempChi;
+                        double rho;
+                        if (lm_trial(&lm, ok2, S.red[0], lm_scale<6>(&lm, S.x, S.b), &rho)) {
                             for (int i = 0; i < 4; i++) S.q[i] = S.tq[i];
                             for (int i = 0; i < 3; i++) S.t[i] = S.tt[i];
                             // the system at the accepted pose is the next buildSystem's
-                            unpack_sys(S.red, S.H, S.b);
+                            unpack_sys<6>(S.red, S.H, S.b);
                             have_sys = true;
-                        } else {
-                            lambda *= ni;
-                            ni *= 2;
                         }
-                        qmax++;
-                        int go = 0;
-                        if (rho < 0 && qmax < 10) {
-                            go = 1;  // another trial
-                        } else if (qmax == 10 || rho == 0) {
-                            go = 2;  // Terminate
-                        } else {
-                            if ((iniChi - currentChi) * 1e3 < iniChi)
-                                nBadLM++;
-                            else
-                                nBadLM = 0;
-                            if (nBadLM >= 3) go = 2;
-                        }
-                        S.go = go;
+                        // 1 another trial, 2 Terminate, 0 next iteration
+                        S.go = lm_retry(&lm, rho) ? 1 : (lm_end(&lm, rho) ? 2 : 0);
                     }
                     __syncthreads();
                     if (S.go != 1) break;
@@ -464,14 +304,8 @@ __global__ __launch_bounds__(PO_T) void k_pose_opt(const orbg_pose_edge *__restr
         for (int i = 0; i < 4; i++) q_out[f * 4 + i] = S.q[i];
         for (int i = 0; i < 3; i++) t_out[f * 3 + i] = S.t[i];
         // Converter::toCvMat(SE3Quat)
-        const double *q = S.q;
-        const double tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2];
-        const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
-        const double txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
-        const double tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
-        const double R[3][3] = {{1 - (tyy + tzz), txy - twz, txz + twy},
-                                {txy + twz, 1 - (txx + tzz), tyz - twx},
-                                {txz - twy, tyz + twx, 1 - (txx + tyy)}};
+        double R[3][3];
+        q_to_rot(S.q, R);
         for (int i = 0; i < 3; i++) {
             for (int j = 0; j < 3; j++) tcw_out[f * 12 + 4 * i + j] = (float)R[i][j];
             tcw_out[f * 12 + 4 * i + 3] = (float)S.t[i];

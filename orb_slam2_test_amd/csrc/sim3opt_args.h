@@ -6,9 +6,9 @@
 // functions in fp64 with a fixed operation order (the build has -ffp-contract=off), so a host
 // program runs the very same statements: g2o::Sim3 (exp, product, inverse, map;
 // Thirdparty/g2o/g2o/types/sim3.h), the two projection edges (types_seven_dof_expmap.h:
-// 130-171), Huber (robust_kernel_impl.cpp:65-91), the numeric Jacobian of
-// BaseBinaryEdge::linearizeOplus (base_binary_edge.hpp:131-205), Eigen's pivoted LDLT and
-// the Levenberg-Marquardt step control (optimization_algorithm_levenberg.cpp:61-164).
+// 130-171), Huber (robust_kernel_impl.cpp:65-91) and the numeric Jacobian of
+// BaseBinaryEdge::linearizeOplus (base_binary_edge.hpp:131-205).  The quaternion formulas,
+// Eigen's pivoted LDLT and the Levenberg-Marquardt step control are g2o_math.h's.
 // Quaternions are (x, y, z, w) and, as in g2o::Sim3, never re-normalised.
 #pragma once
 
@@ -19,6 +19,7 @@
 
 #include "../../include/orbg.h"
 #include "orbg_device.h"
+#include "g2o_math.h"
 
 #pragma clang fp contract(off)
 
@@ -49,10 +50,8 @@ __host__ __device__ static inline int sim3opt_n(const orbg_sim3opt_problem &P, i
     return (P.n < 0 || P.n > cap) ? 0 : P.n;
 }
 
-// ---- scalar functions pinned to one polynomial each (host and device agree bit for bit) ----
-// sin / cos: orbg_device.h's pinned polynomial
-__host__ __device__ static inline void so_sincos(double x, double *s, double *c) { pinned_sincos(x, s, c); }
-
+// ---- exp pinned to one polynomial (host and device agree bit for bit; sin / cos are
+// orbg_device.h's pinned_sincos) ----
 // exp: x = k ln2 + r, |r| <= ln2 / 2, Taylor to r^13 / 13! (remainder below 1e-17 relative),
 // scaled by 2^k.  exp(0) is exactly 1.  |x| past 700 is clamped (a scale step never is).
 __host__ __device__ static inline double so_exp(double x)
@@ -70,82 +69,6 @@ __host__ __device__ static inline double so_exp(double x)
     return ldexp(1.0 + r * p, (int)kd);
 }
 
-// g2o's pow(2 rho - 1, 3): the exact cube as a double-double, rounded once (se3_device.h)
-__host__ __device__ static inline double so_cube(double t)
-{
-    const double h = t * t;
-    const double l = __builtin_fma(t, t, -h);
-    const double ph = h * t;
-    const double pl = __builtin_fma(h, t, -ph);
-    return ph + (pl + l * t);
-}
-
-// ---- Eigen's quaternion formulas (as se3_device.h) ----
-__host__ __device__ static inline void so_q_rotate(const double q[4], const double v[3], double out[3])
-{
-    double uv[3] = {q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2],
-                    q[0] * v[1] - q[1] * v[0]};
-    uv[0] += uv[0];
-    uv[1] += uv[1];
-    uv[2] += uv[2];
-    const double c[3] = {q[1] * uv[2] - q[2] * uv[1], q[2] * uv[0] - q[0] * uv[2],
-                         q[0] * uv[1] - q[1] * uv[0]};
-    out[0] = v[0] + q[3] * uv[0] + c[0];
-    out[1] = v[1] + q[3] * uv[1] + c[1];
-    out[2] = v[2] + q[3] * uv[2] + c[2];
-}
-
-__host__ __device__ static inline void so_q_mul(const double a[4], const double b[4], double o[4])
-{
-    o[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
-    o[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
-    o[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
-    o[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
-}
-
-// Quaterniond(Matrix3d): no normalisation
-__host__ __device__ static inline void so_q_from_rot(const double R[3][3], double q[4])
-{
-    const double t = R[0][0] + R[1][1] + R[2][2];
-    if (t > 0) {
-        double s = sqrt(t + 1.0);
-        q[3] = 0.5 * s;
-        s = 0.5 / s;
-        q[0] = (R[2][1] - R[1][2]) * s;
-        q[1] = (R[0][2] - R[2][0]) * s;
-        q[2] = (R[1][0] - R[0][1]) * s;
-    } else {
-        int i = 0;
-        if (R[1][1] > R[0][0]) i = 1;
-        if (R[2][2] > R[i][i]) i = 2;
-        const int j = (i + 1) % 3, k = (j + 1) % 3;
-        double s = sqrt(R[i][i] - R[j][j] - R[k][k] + 1.0);
-        q[i] = 0.5 * s;
-        s = 0.5 / s;
-        q[3] = (R[k][j] - R[j][k]) * s;
-        q[j] = (R[j][i] + R[i][j]) * s;
-        q[k] = (R[k][i] + R[i][k]) * s;
-    }
-}
-
-// Quaterniond::toRotationMatrix
-__host__ __device__ static inline void so_q_to_rot(const double q[4], double R[3][3])
-{
-    const double tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2];
-    const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
-    const double txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
-    const double tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
-    R[0][0] = 1 - (tyy + tzz);
-    R[0][1] = txy - twz;
-    R[0][2] = txz + twy;
-    R[1][0] = txy + twz;
-    R[1][1] = 1 - (txx + tzz);
-    R[1][2] = tyz - twx;
-    R[2][0] = txz - twy;
-    R[2][1] = tyz + twx;
-    R[2][2] = 1 - (txx + tyy);
-}
-
 // ---- g2o::Sim3 ----
 // g2o::Sim3(Converter::toMatrix3d(R12), toVector3d(t12), s12): the float hypothesis widened
 __host__ __device__ static inline void so_init(const orbg_sim3_hyp &h, Sim3d *S)
@@ -155,7 +78,7 @@ __host__ __device__ static inline void so_init(const orbg_sim3_hyp &h, Sim3d *S)
         for (int j = 0; j < 3; j++) R[i][j] = h.R[3 * i + j];
         S->t[i] = h.t[i];
     }
-    so_q_from_rot(R, S->q);
+    q_from_rot(R, S->q);
     S->s = h.s;
 }
 
@@ -174,7 +97,7 @@ __host__ __device__ static inline void so_exp_sim3(const double u[7], Sim3d *S)
     const double eps = 0.00001;
     double A, B, C;
     double sn = 0, cs = 1;
-    if (!(theta < eps)) so_sincos(theta, &sn, &cs);
+    if (!(theta < eps)) pinned_sincos(theta, &sn, &cs);
     if (fabs(sigma) < eps) {
         C = 1;
         if (theta < eps) {
@@ -208,7 +131,7 @@ __host__ __device__ static inline void so_exp_sim3(const double u[7], Sim3d *S)
             for (int j = 0; j < 3; j++)
                 R[i][j] = ((i == j ? 1.0 : 0.0) + ra * O[i][j]) + rb * O2[i][j];
     }
-    so_q_from_rot(R, S->q);
+    q_from_rot(R, S->q);
     for (int i = 0; i < 3; i++) {
         double W[3];
         for (int j = 0; j < 3; j++) W[j] = (A * O[i][j] + B * O2[i][j]) + (i == j ? C : 0.0);
@@ -221,8 +144,8 @@ __host__ __device__ static inline void so_exp_sim3(const double u[7], Sim3d *S)
 __host__ __device__ static inline void so_mul(const Sim3d &a, const Sim3d &b, Sim3d *o)
 {
     double rt[3];
-    so_q_mul(a.q, b.q, o->q);
-    so_q_rotate(a.q, b.t, rt);
+    q_mul(a.q, b.q, o->q);
+    q_rotate(a.q, b.t, rt);
     for (int i = 0; i < 3; i++) o->t[i] = a.s * rt[i] + a.t[i];
     o->s = a.s * b.s;
 }
@@ -236,7 +159,7 @@ __host__ __device__ static inline void so_inverse(const Sim3d &a, Sim3d *o)
     o->q[1] = -a.q[1];
     o->q[2] = -a.q[2];
     o->q[3] = a.q[3];
-    so_q_rotate(o->q, v, o->t);
+    q_rotate(o->q, v, o->t);
     o->s = 1. / a.s;
 }
 
@@ -244,7 +167,7 @@ __host__ __device__ static inline void so_inverse(const Sim3d &a, Sim3d *o)
 __host__ __device__ static inline void so_map(const Sim3d &a, const double x[3], double o[3])
 {
     double r[3];
-    so_q_rotate(a.q, x, r);
+    q_rotate(a.q, x, r);
     for (int i = 0; i < 3; i++) o[i] = a.s * r[i] + a.t[i];
 }
 
@@ -406,177 +329,19 @@ __host__ __device__ static inline void so_add_pair(const Sim3d &S, const Sim3d &
     so_add_edge(e21, J21, e.info2, delta, p);
 }
 
-__host__ __device__ static inline void so_unpack(const double *red, double H[49], double b[7])
-{
-    int hi = 1;
-    for (int r = 0; r < 7; r++)
-        for (int c = 0; c <= r; c++) {
-            H[r * 7 + c] = red[hi];
-            H[c * 7 + r] = red[hi];
-            hi++;
-        }
-    for (int r = 0; r < 7; r++) b[r] = red[29 + r];
-}
-
-// Eigen LDLT (lower, diagonal pivoting) + solve of the 7x7 system; returns isPositive()
-// (pose_kernels.hip's ldlt_solve6 at N = 7)
-__host__ __device__ static inline bool so_ldlt_solve7(double m[7][7], const double b[7], double x[7])
-{
-    const int N = 7;
-    int tr[N];
-    int sign = 0;  // 0 zero, 1 positive semidef, 2 negative semidef, 3 indefinite
-    double temp[N];
-    for (int k = 0; k < N; k++) {
-        int big = k;
-        double bv = fabs(m[k][k]);
-        for (int i = k + 1; i < N; i++)
-            if (fabs(m[i][i]) > bv) {
-                bv = fabs(m[i][i]);
-                big = i;
-            }
-        tr[k] = big;
-        if (k != big) {
-            for (int j = 0; j < k; j++) {
-                const double s = m[k][j];
-                m[k][j] = m[big][j];
-                m[big][j] = s;
-            }
-            for (int i = big + 1; i < N; i++) {
-                const double s = m[i][k];
-                m[i][k] = m[i][big];
-                m[i][big] = s;
-            }
-            {
-                const double s = m[k][k];
-                m[k][k] = m[big][big];
-                m[big][big] = s;
-            }
-            for (int i = k + 1; i < big; i++) {
-                const double s = m[i][k];
-                m[i][k] = m[big][i];
-                m[big][i] = s;
-            }
-        }
-        if (k > 0) {
-            for (int j = 0; j < k; j++) temp[j] = m[j][j] * m[k][j];
-            double dot = 0;
-            for (int j = 0; j < k; j++) dot += m[k][j] * temp[j];
-            m[k][k] -= dot;
-            for (int i = k + 1; i < N; i++) {
-                double s = 0;
-                for (int j = 0; j < k; j++) s += m[i][j] * temp[j];
-                m[i][k] -= s;
-            }
-        }
-        const double akk = m[k][k];
-        const bool valid = fabs(akk) > 0.0;
-        if (k == 0 && !valid) {
-            sign = 0;
-            for (int j = 0; j < N; j++) tr[j] = j;
-            break;
-        }
-        if (k < N - 1 && valid)
-            for (int i = k + 1; i < N; i++) m[i][k] /= akk;
-        if (sign == 0 || sign == 1) {
-            if (akk > 0) sign = 1;
-            else if (akk < 0) sign = sign == 0 ? 2 : 3;
-        } else if (sign == 2 && akk > 0) {
-            sign = 3;
-        }
-    }
-    if (!(sign == 1 || sign == 0)) return false;
-    double d[N];
-    for (int i = 0; i < N; i++) d[i] = b[i];
-    for (int k = 0; k < N; k++) {
-        const double s = d[k];
-        d[k] = d[tr[k]];
-        d[tr[k]] = s;
-    }
-    for (int i = 0; i < N; i++) {
-        double s = 0;
-        for (int j = 0; j < i; j++) s += m[i][j] * d[j];
-        d[i] -= s;
-    }
-    for (int i = 0; i < N; i++) d[i] = fabs(m[i][i]) > DBL_MIN ? d[i] / m[i][i] : 0.0;
-    for (int i = N - 1; i >= 0; i--) {
-        double s = 0;
-        for (int j = i + 1; j < N; j++) s += m[j][i] * d[j];
-        d[i] -= s;
-    }
-    for (int k = N - 1; k >= 0; k--) {
-        const double s = d[k];
-        d[k] = d[tr[k]];
-        d[tr[k]] = s;
-    }
-    for (int i = 0; i < N; i++) x[i] = d[i];
-    return true;
-}
-
-// ---- OptimizationAlgorithmLevenberg::solve's scalars (one owner: lane 0, or the host) ----
-struct SoLm {
-    double lambda, ni, currentChi, iniChi;
-    int nBad, qmax;
-};
-
-// after computeActiveErrors + buildSystem at the estimate: chi = activeRobustChi2
-__host__ __device__ static inline void so_lm_begin(SoLm *L, int it, const double H[49], double chi)
-{
-    L->currentChi = chi;
-    L->iniChi = chi;
-    if (it == 0) {
-        double maxd = 0;
-        for (int j = 0; j < 7; j++) maxd = fmax(fabs(H[j * 8]), maxd);
-        L->lambda = 1e-5 * maxd;
-        L->ni = 2;
-        L->nBad = 0;
-    }
-    L->qmax = 0;
-}
-
+// ---- one LM trial (g2o_math.h has the step control) ----
 // setLambda, the LDLT solve, oplus into *trial, restoreDiagonal; returns the solver's ok
 // (Hd: 49 doubles of workspace for the damped copy; the kernel passes LDS)
-__host__ __device__ static inline bool so_lm_trial(const SoLm *L, const double H[49], const double b[7],
+__host__ __device__ static inline bool so_lm_trial(const LmState *L, const double H[49], const double b[7],
                                                    const Sim3d &est, bool fix_scale, double x[7],
                                                    Sim3d *trial, double (*Hd)[7])
 {
     for (int r = 0; r < 7; r++)
         for (int c = 0; c < 7; c++) Hd[r][c] = H[r * 7 + c];
     for (int j = 0; j < 7; j++) Hd[j][j] += L->lambda;
-    const bool ok = so_ldlt_solve7(Hd, b, x);
+    const bool ok = ldlt_solve<7>(Hd, b, x);
     so_oplus(est, x, fix_scale, trial);
     return ok;
-}
-
-// the trial's verdict: *accepted tells whether the estimate becomes the trial; returns
-// 0 next iteration, 1 another trial, 2 terminate
-__host__ __device__ static inline int so_lm_judge(SoLm *L, bool ok, double tempChi, const double x[7],
-                                                  const double b[7], bool *accepted)
-{
-    if (!ok) tempChi = DBL_MAX;
-    double rho = L->currentChi - tempChi;
-    double scale = 0;
-    for (int j = 0; j < 7; j++) scale += x[j] * (L->lambda * x[j] + b[j]);
-    scale += 1e-3;
-    rho /= scale;
-    *accepted = rho > 0 && tempChi == tempChi && fabs(tempChi) <= DBL_MAX;
-    if (*accepted) {
-        double alpha = 1. - so_cube(2 * rho - 1);
-        alpha = fmin(alpha, 2. / 3.);
-        L->lambda *= fmax(1. / 3., alpha);
-        L->ni = 2;
-        L->currentChi = tempChi;
-    } else {
-        L->lambda *= L->ni;
-        L->ni *= 2;
-    }
-    L->qmax++;
-    if (rho < 0 && L->qmax < 10) return 1;
-    if (L->qmax == 10 || rho == 0) return 2;
-    if ((L->iniChi - L->currentChi) * 1e3 < L->iniChi)
-        L->nBad++;
-    else
-        L->nBad = 0;
-    return L->nBad >= 3 ? 2 : 0;
 }
 
 // the result record from the estimate: R / tf / sf = toRotationMatrix, t, s rounded once
@@ -584,7 +349,7 @@ __host__ __device__ static inline void so_result(const Sim3d &S, int nin, int nb
                                                  int it1, orbg_sim3opt_result *r)
 {
     double R[3][3];
-    so_q_to_rot(S.q, R);
+    q_to_rot(S.q, R);
     for (int i = 0; i < 4; i++) r->q[i] = S.q[i];
     for (int i = 0; i < 3; i++) {
         r->t[i] = S.t[i];

@@ -1,5 +1,5 @@
 // sim3opt_host.hip -- Optimizer::OptimizeSim3 on one host core, through the very
-// __host__ __device__ statements k_sim3_opt runs (sim3opt_args.h) and in the kernel's
+// __host__ __device__ statements k_sim3_opt runs (sim3opt_args.h, g2o_math.h) and in the kernel's
 // summation order (256 strided partial sums, butterfly per 64, (w0 + w1) + (w2 + w3)), so its
 // records equal the device's bit for bit.  No kernel and no GPU: tools/sim3opt_bench.py times
 // it, and tests/test_sim3opt_ref.py checks the shared arithmetic with it.
@@ -23,7 +23,7 @@ using namespace orbg;
 
 #define SO_T 256
 
-// the kernel's so_reduce on the 256 per-thread values v[t * nv + j]
+// the kernel's wg_reduce on the 256 per-thread values v[t * nv + j]
 static void reduce(const std::vector<double> &v, int nv, double *red)
 {
     for (int j = 0; j < nv; j++) {
@@ -59,7 +59,7 @@ static void optimize_one(const orbg_sim3opt_problem &P, const orbg_sim3opt_corr 
     so_inverse(est, &last_inv);
     int nBad = 0, nIn = 0, its[2] = {0, 0};
     bool give_input = true;
-    SoLm lm = {0, 2, 0, 0, 0, 0};
+    LmState lm = {0, 2, 0, 0, 0, 0};
     std::vector<double> part((size_t)SO_T * SO_NV), part1(SO_T);
     double red[SO_NV], H[49], b[7], x[7], Hd[7][7];
     for (int round = 0; round < 2 && n > 0; round++) {
@@ -75,8 +75,9 @@ static void optimize_one(const orbg_sim3opt_problem &P, const orbg_sim3opt_corr 
             reduce(part, SO_NV, red);
             last = est;
             last_inv = est_inv;
-            so_unpack(red, H, b);
-            so_lm_begin(&lm, it, H, red[0]);
+            unpack_sys<7>(red, H, b);
+            lm.currentChi = red[0];
+            lm_begin(&lm, it, it == 0 ? lm_max_diag<7>(H) : 0.0);
             for (;;) {
                 const bool ok = so_lm_trial(&lm, H, b, est, fix_scale, x, &trial, Hd);
                 so_inverse(trial, &trial_inv);
@@ -87,9 +88,9 @@ static void optimize_one(const orbg_sim3opt_problem &P, const orbg_sim3opt_corr 
                     if (!dead[e]) part1[e % SO_T] += so_pair_chi(trial, trial_inv, P, E[e], delta);
                 double chi;
                 reduce(part1, 1, &chi);
-                bool accepted;
-                go = so_lm_judge(&lm, ok, chi, x, b, &accepted);
-                if (accepted) est = trial;
+                double rho;
+                if (lm_trial(&lm, ok, chi, lm_scale<7>(&lm, x, b), &rho)) est = trial;
+                go = lm_retry(&lm, rho) ? 1 : (lm_end(&lm, rho) ? 2 : 0);
                 if (go != 1) break;
             }
             its[round]++;

@@ -20,7 +20,7 @@
 // LDLT and the Sim3 exp update (state in LDS); barriers hand estimates out and sums back.
 // The dropped-pair flags live in LDS too, so the kernel needs no scratch buffer.
 //
-// The arithmetic is sim3opt_args.h's __host__ __device__ functions.  fp64 throughout; no FMA
+// The arithmetic is sim3opt_args.h's and g2o_math.h's __host__ __device__ functions.  fp64 throughout; no FMA
 // contraction; sin / cos / exp pinned.
 #include <hip/hip_runtime.h>
 
@@ -52,26 +52,6 @@ struct SoShared {
     uint8_t dead[ORBG_SIM3OPT_MAX_N];
 };
 
-// fixed-order sum of NV per-thread values into red[0 .. NV)
-template <int NV>
-__device__ __forceinline__ void so_reduce(const double *p, double *wred, double *red)
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < NV; j++) {
-        double v = p[j];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
-        if (lane == 0) wred[wv * NV + j] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < NV) {
-        const int j = threadIdx.x;
-        red[j] = (wred[j] + wred[NV + j]) + (wred[2 * NV + j] + wred[3 * NV + j]);
-    }
-    __syncthreads();
-}
-
 __global__ __launch_bounds__(SO_T) void k_sim3_opt(Sim3OptArgs A)
 {
     __shared__ SoShared S;
@@ -92,7 +72,7 @@ __global__ __launch_bounds__(SO_T) void k_sim3_opt(Sim3OptArgs A)
     __syncthreads();
     int nBad = 0, nIn = 0, its[2] = {0, 0};
     bool give_input = true;  // g2oS12 is written back only after the second optimize
-    SoLm lm = {0, 2, 0, 0, 0, 0};  // lane 0's
+    LmState lm = {0, 2, 0, 0, 0, 0};  // lane 0's
     for (int round = 0; round < 2 && n > 0; round++) {
         // ---- optimize(iters): OptimizationAlgorithmLevenberg::solve per iteration ----
         const int iters = round == 0 ? 5 : (nBad > 0 ? 10 : 5);
@@ -110,12 +90,13 @@ __global__ __launch_bounds__(SO_T) void k_sim3_opt(Sim3OptArgs A)
                 so_pair(P, corrs[e], &E);
                 so_add_pair(S.est, S.est_inv, S.P, S.Pinv, P, E, delta, p);
             }
-            so_reduce<SO_NV>(p, S.wred, S.red);
+            wg_reduce<SO_NV>(p, S.wred, S.red);
             if (tid == 0) {
                 S.last = S.est;
                 S.last_inv = S.est_inv;
-                so_unpack(S.red, S.H, S.b);
-                so_lm_begin(&lm, it, S.H, S.red[0]);
+                unpack_sys<7>(S.red, S.H, S.b);
+                lm.currentChi = S.red[0];
+                lm_begin(&lm, it, it == 0 ? lm_max_diag<7>(S.H) : 0.0);
             }
             for (;;) {
                 bool ok = false;
@@ -133,11 +114,12 @@ __global__ __launch_bounds__(SO_T) void k_sim3_opt(Sim3OptArgs A)
                     so_pair(P, corrs[e], &E);
                     chi += so_pair_chi(S.trial, S.trial_inv, P, E, delta);
                 }
-                so_reduce<1>(&chi, S.wred, S.red);
+                wg_reduce<1>(&chi, S.wred, S.red);
                 if (tid == 0) {
-                    bool accepted;
-                    S.go = so_lm_judge(&lm, ok, S.red[0], S.x, S.b, &accepted);
-                    if (accepted) S.est = S.trial;
+                    double rho;
+                    if (lm_trial(&lm, ok, S.red[0], lm_scale<7>(&lm, S.x, S.b), &rho)) S.est = S.trial;
+                    // 1 another trial, 2 Terminate, 0 next iteration
+                    S.go = lm_retry(&lm, rho) ? 1 : (lm_end(&lm, rho) ? 2 : 0);
                 }
                 __syncthreads();
                 if (S.go != 1) break;
