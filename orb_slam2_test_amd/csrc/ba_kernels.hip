@@ -18,11 +18,9 @@
 #include "orbg_internal.h"
 #include "orbg_device.h"
 #include "g2o_math.h"
+#include "orbg_launch.h"
 
 namespace orbg {
-
-void prof_begin(void *prof, hipStream_t s, const char *n, hipEvent_t *a);
-void prof_end(void *prof, hipStream_t s, const char *n, hipEvent_t a);
 
 // computeError (types_six_dof_expmap.h:90-95, 122-127): Xc = q X + t, then the mono
 // projection in double, or the stereo cam_project with its float invz and float bf
@@ -137,7 +135,7 @@ __global__ __launch_bounds__(256) void k_ba_errors(const orbg_pose *__restrict__
 template <class ES>
 static int launch_ba_errors_t(hipStream_t st, const orbg_pose *poses, const double *points,
                               ES edges, int nedge, double *err, double *chi2, double *rho0,
-                              uint8_t *depth_ok, void *prof)
+                              uint8_t *depth_ok, Prof *prof)
 {
     if (nedge <= 0) return 0;
     hipEvent_t a = nullptr;
@@ -150,7 +148,7 @@ static int launch_ba_errors_t(hipStream_t st, const orbg_pose *poses, const doub
 
 int launch_ba_errors(hipStream_t st, const orbg_pose *poses, const double *points,
                      const orbg_edge *edges, int nedge, double *err, double *chi2, double *rho0,
-                     uint8_t *depth_ok, void *prof)
+                     uint8_t *depth_ok, Prof *prof)
 {
     return launch_ba_errors_t(st, poses, points, BaEdgeRecords{edges}, nedge, err, chi2, rho0,
                               depth_ok, prof);
@@ -159,7 +157,7 @@ int launch_ba_errors(hipStream_t st, const orbg_pose *poses, const double *point
 int launch_ba_errors_packed(hipStream_t st, const orbg_pose *poses, const double *points,
                             const BaPackedEdge *edges, const BaCam *cam, const BaInfo *info,
                             int nedge, double *err, double *chi2, double *rho0,
-                            uint8_t *depth_ok, void *prof)
+                            uint8_t *depth_ok, Prof *prof)
 {
     return launch_ba_errors_t(st, poses, points, BaEdgePacked{edges, cam, info}, nedge, err,
                               chi2, rho0, depth_ok, prof);
@@ -884,7 +882,7 @@ static int launch_ba_device_t(hipStream_t st, const orbg_pose *poses, int npose,
                               const int32_t *pose_off, const int32_t *pose_edges,
                               const int32_t *point_off, const int32_t *point_edges,
                               orbg_edge_out *eout, double *hpose, double *bpose, double *hpoint,
-                              double *bpoint, double *scr, void *prof, bool jacobians,
+                              double *bpoint, double *scr, Prof *prof, bool jacobians,
                               bool errors, double *hpl)
 {
     BaEdgeOut o = eout_fields(eout, jacobians, errors);
@@ -938,7 +936,7 @@ int launch_ba_device(hipStream_t st, const orbg_pose *poses, int npose, const do
                      int npoint, const orbg_edge *edges, int nedge, const int32_t *pose_off,
                      const int32_t *pose_edges, const int32_t *point_off,
                      const int32_t *point_edges, orbg_edge_out *eout, double *hpose,
-                     double *bpose, double *hpoint, double *bpoint, double *scr, void *prof,
+                     double *bpose, double *hpoint, double *bpoint, double *scr, Prof *prof,
                      bool jacobians, bool errors, double *hpl)
 {
     return launch_ba_device_t(st, poses, npose, points, npoint, BaEdgeRecords{edges}, nedge,
@@ -956,7 +954,7 @@ int launch_ba_graph(hipStream_t st, const orbg_pose *poses, int npose, const dou
                     int nedge, const int32_t *pose_off, const int32_t *pose_edges,
                     const int32_t *point_off, const int32_t *point_edges, const BaGraphDev &gd,
                     double *hpl, double *hpose, double *bpose, double *hpoint, double *bpoint,
-                    void *prof)
+                    Prof *prof)
 {
     const BaEdgePacked es{edges, cam, info};
     BaEdgeOut o{};
@@ -1001,7 +999,7 @@ int launch_ba(hipStream_t st, const orbg_pose *poses, int npose, const double *p
               int npoint, const orbg_edge *edges, int nedge, const int32_t *pose_off,
               const int32_t *pose_edges, const int32_t *point_off, const int32_t *point_edges,
               orbg_edge_out *eout, double *hpose, double *bpose, double *hpoint, double *bpoint,
-              void *scratch, void *prof)
+              void *scratch, Prof *prof)
 {
     uint8_t *s = (uint8_t *)scratch;
     const size_t np = (size_t)(npose > 0 ? npose : 1), nq = (size_t)(npoint > 0 ? npoint : 1),

@@ -28,6 +28,7 @@
 #include "orbg_internal.h"
 #include "orbg_device.h"
 #include "blur_device.h"
+#include "orbg_launch.h"
 
 #pragma clang fp contract(off)
 

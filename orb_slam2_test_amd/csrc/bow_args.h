@@ -44,7 +44,8 @@ struct BowArgs {
     int32_t *nfv;               // [nframes]
 };
 
-int launch_bow(hipStream_t st, const BowArgs &A, void *prof);
+struct Prof;  // the context's profiler (orbg_ctx.h)
+int launch_bow(hipStream_t st, const BowArgs &A, Prof *prof);
 size_t bow_vectors_lds(int cap);
 
 }  // namespace orbg

@@ -20,13 +20,11 @@
 
 #include "../../include/orbg.h"
 #include "bow_args.h"
+#include "orbg_launch.h"
 
 #pragma clang fp contract(off)
 
 namespace orbg {
-
-void prof_begin(void *prof, hipStream_t s, const char *n, hipEvent_t *a);
-void prof_end(void *prof, hipStream_t s, const char *n, hipEvent_t a);
 
 #define BOW_THREADS 256
 
@@ -262,7 +260,7 @@ __global__ __launch_bounds__(BOW_THREADS) void k_bow_vectors(BowArgs A)
     }
 }
 
-int launch_bow(hipStream_t st, const BowArgs &A, void *prof)
+int launch_bow(hipStream_t st, const BowArgs &A, Prof *prof)
 {
     if (A.nframes <= 0) return ORBG_OK;
     hipEvent_t ev = nullptr;

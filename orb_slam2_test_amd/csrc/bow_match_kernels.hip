@@ -27,6 +27,7 @@
 #include "../../include/orbg.h"
 #include "orbg_internal.h"
 #include "orbg_device.h"
+#include "orbg_launch.h"
 
 #pragma clang fp contract(off)
 

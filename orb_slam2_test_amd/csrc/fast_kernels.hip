@@ -24,6 +24,7 @@
 #include "orbg_device.h"
 #include "fast_device.h"
 #include "blur_device.h"
+#include "orbg_launch.h"
 
 #pragma clang fp contract(off)
 
@@ -231,7 +232,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FC2_WPE, 8)
     }
     wave_sync_lds();
     if (dbg == 11) continue;
-
 
     // unit u = ry * RG + gg walked as u = lane + 64 k: (ry, gg) advance by (64 / RG, 64 % RG)
     const int rstep = RG > 0 ? 64 / RG : 0, gstep = RG > 0 ? 64 - rstep * RG : 0;

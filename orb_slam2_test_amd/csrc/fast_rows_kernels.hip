@@ -31,6 +31,7 @@
 #include "orbg_internal.h"
 #include "orbg_device.h"
 #include "fast_device.h"
+#include "orbg_launch.h"
 
 #pragma clang fp contract(off)
 

@@ -18,6 +18,7 @@
 #include "orbg_internal.h"
 #include "orbg_device.h"
 #include "g2o_math.h"
+#include "orbg_launch.h"
 
 #pragma clang fp contract(off)
 

@@ -22,14 +22,11 @@
 #include "orbg_internal.h"
 #include "orbg_device.h"
 #include "match_device.h"
+#include "orbg_launch.h"
 
 #pragma clang fp contract(off)
 
 namespace orbg {
-
-void prof_begin(void *prof, hipStream_t s, const char *n, hipEvent_t *a);
-void prof_end(void *prof, hipStream_t s, const char *n, hipEvent_t a);
-bool prof_skip_name(const char *n);
 
 // reductions over a 16-lane row (the query groups of init_cands_block): every lane gets the
 // row's result by DPP row_ror 8 / 4 and quad_perm [2,3,0,1] / [1,0,3,2] (in the ALU; a
@@ -1008,7 +1005,7 @@ int launch_match_export(hipStream_t st, const int32_t *m12, const int32_t *f1,
 }
 
 int launch_knn2(hipStream_t st, const uint8_t *q, int nq, const uint8_t *t, int nt, int32_t *out,
-                void *prof)
+                Prof *prof)
 {
     if (nt >= KNN_MAX_TRAIN) return ORBG_ENOTSUP;  // caller chunks the train set
     PL(prof, st, "knn2",
@@ -1022,7 +1019,7 @@ int launch_match_pairs(hipStream_t st, hipStream_t aux, hipEvent_t evf, hipEvent
                        const int32_t *counts, int fc, const int32_t *d_f1, const int32_t *d_f2,
                        int npairs, orbg_bounds b, int window, float nnratio, int check_ori,
                        int32_t *knn, int32_t *m12, int32_t *nm, uint32_t *topk, int32_t *topk_n,
-                       void *prof, int serial, int cap0)
+                       Prof *prof, int serial, int cap0)
 {
     // cap0 = level-0 capacity: every index SearchForInitialization touches is below it
     if (fc > RESOLVE_N2_CAP || fc > (1 << 20) || cap0 > fc) return ORBG_ENOTSUP;
@@ -1084,7 +1081,7 @@ int launch_init_match_single(hipStream_t st, const orbg_keypoint *k1, const uint
                              const orbg_keypoint *k2, const uint8_t *d2, int n2, orbg_bounds b,
                              const float *prev, float *prev_out, int32_t *m12, int32_t *nm,
                              int window, float nnratio,
-                             int check_ori, uint32_t *topk, int32_t *topk_n, void *prof, int cap)
+                             int check_ori, uint32_t *topk, int32_t *topk_n, Prof *prof, int cap)
 {
     const int nq = std::min(n1, cap), n2c = std::min(n2, cap);  // indices below cap
     if (n1 > RESOLVE_N2_CAP || n2 > RESOLVE_N2_CAP || n2 > INIT_F2_CAP) return ORBG_ENOTSUP;

@@ -17,6 +17,7 @@
 #include "orbg_device.h"
 #include "orbg_internal.h"
 #include "octree_args.h"
+#include "orbg_launch.h"
 
 #pragma clang fp contract(off)
 

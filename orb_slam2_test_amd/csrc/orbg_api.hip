@@ -2,186 +2,15 @@
 // and kernel launches.  All reference tables are computed here exactly as the
 // ORBextractor ctor does (ORBextractor.cc:432-521); geometry (levels, cells, quadtree
 // roots) as ComputePyramid / ComputeKeyPointsOctTree / DistributeOctTree do.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <atomic>
-#include <cmath>
-#include <cstdarg>
-#include <cfloat>
-#include <cstddef>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <array>
-#include <map>
-#include <vector>
-
-#include "../../include/orbg.h"
-#include "orbg_internal.h"
-#include "octree_args.h"
+#include "orbg_ctx.h"
 #include "track_args.h"
 #include "schur_args.h"
 #include "bow_args.h"
 #include "place_args.h"
-#include "sim3_args.h"
-#include "sim3opt_args.h"
-#include "pnp_args.h"
-#include "pyramid_args.h"
 #include "frame_device.h"
+#include "g2o_math.h"
 
 #pragma clang fp contract(off)
-
-namespace orbg {
-__global__ void k_resize(const uint8_t *, int64_t, int, int, uint8_t *, int64_t, int, int, int,
-                         const int2 *, const int2 *, int, int);
-__global__ void k_octree(const OrbgGeom *, const int32_t *, const uint2 *, uint32_t *,
-                         uint32_t *, uint32_t *, uint8_t *, int4 *, uint32_t *, uint16_t *,
-                         int32_t *, int32_t *, int);
-hipError_t launch_octree_lds(bool small, dim3 grid, size_t lds, hipStream_t st, const OrbgGeom *g,
-                             const int32_t *cell_cnt, const uint2 *cell_kp, uint32_t *lvl_kp,
-                             uint16_t *lvl_idx, int32_t *lvl_cnt, int32_t *err_flag, OctLdsDims D);
-hipError_t octree_lds_attr(int bytes);
-// fast_kernels.hip
-bool fast2_pitch_ok(int p4);
-__global__ void k_pyramid(PyrArgs, const OrbgGeom *, const uint4 *, const int4 *, const int4 *,
-                          const uint8_t *, int64_t, int, const uint8_t *, uint8_t *, uint8_t *,
-                          int);
-// blur_kernels.hip
-int blur2_seg();
-int blur2_tw(bool tiled);
-hipError_t launch_blur2(hipStream_t st, const OrbgGeom *g, const int32_t *task_base,
-                        const uint8_t *img0, int64_t img_fs, int img_pitch, const uint8_t *pyr,
-                        uint8_t *blur, int t_begin, int t_count, int nframes);
-// fast_rows_kernels.hip
-int fast_rows_wave_bytes();
-hipError_t launch_fast_rows(hipStream_t st, const OrbgGeom *g, const OrbgFastTile *tiles,
-                            const uint8_t *img0, int64_t img_fs, int img_pitch,
-                            const uint8_t *pyr, const uint32_t *ctab, int32_t *cell_cnt,
-                            uint2 *cell_kp, int nframes, int t_begin, int t_count);
-hipError_t launch_fast2(int p4, size_t lds, hipStream_t st, const OrbgGeom *g,
-                        const OrbgCell *cells, const uint8_t *img0, int64_t img_fs,
-                        int img_pitch, const uint8_t *pyr, const uint32_t *ctab,
-                        int32_t *cell_cnt, uint2 *cell_kp, uint8_t *blur, int nframes,
-                        int c_begin, int c_count);
-hipError_t launch_blur_border(hipStream_t st, const OrbgGeom *g, int tasks_per_frame,
-                              const uint8_t *img0, int64_t img_fs, int img_pitch,
-                              const uint8_t *pyr, uint8_t *blur, int l0, int l1, int nframes);
-struct OrbgKeypointDev;
-hipError_t launch_orient_desc(bool bfma, bool tiled, dim3 grid, hipStream_t st, const OrbgGeom *g,
-                              const uint8_t *img0, int64_t img_fs, int img_pitch,
-                              const uint8_t *pyr, const uint8_t *blur, const uint4 *odtab,
-                              const uint32_t *lvl_kp, const uint16_t *lvl_idx,
-                              const int32_t *lvl_cnt, OrbgKeypointDev *kps, uint8_t *desc,
-                              int32_t *counts, uint8_t *hc_base = nullptr,
-                              const int32_t *hc_err = nullptr, size_t hc_okp = 0,
-                              size_t hc_ods = 0, int32_t hc_tag = 0);
-// match_kernels.hip
-int launch_match_pairs(hipStream_t st, hipStream_t aux, hipEvent_t evf, hipEvent_t evj,
-                       const uint8_t *desc, const orbg_keypoint *kps,
-                       const int32_t *counts, int frame_cap, const int32_t *d_f1,
-                       const int32_t *d_f2, int npairs, orbg_bounds b, int window, float nnratio,
-                       int check_ori, int32_t *knn, int32_t *m12, int32_t *nm, uint32_t *topk,
-                       int32_t *topk_n, void *prof, int serial, int cap0);
-int launch_undistort(hipStream_t st, const orbg_camera &cam, const orbg_keypoint *kps,
-                     const int32_t *counts, int fc, int nframes, orbg_keypoint *out);
-int launch_frustum(hipStream_t st, const orbg_frustum_camera *cams, const orbg_map_point *mps,
-                   const int32_t *counts, int cap, int nframes, float cos_limit,
-                   orbg_map_projection *out, int32_t *nvisible);
-int launch_tri_match(hipStream_t st, const orbg_keyframes &K, int cap, const int32_t *kf1,
-                     const int32_t *kf2, const orbg_triangulation_pair *geo, int npairs,
-                     const float *scale, const float *sigma2, int nlevels, int only_stereo,
-                     int check_ori, int32_t *match, int32_t *nmatch);
-int launch_ba_update(hipStream_t st, const orbg_pose *poses, int npose, const double *points,
-                     int npoint, const double *dxp, const double *dxq, orbg_pose *pout,
-                     double *qout);
-int launch_lm_reduce(hipStream_t st, int mode, int n1, int n2, double lambda, const double *a1,
-                     const double *a2, const double *b1, const double *b2,
-                     const BaPackedEdge *edges, double *part, double *out);
-int lm_reduce_groups();
-int launch_tri_geometry(hipStream_t st, const orbg_kf_camera *cams, const int32_t *kf1,
-                        const int32_t *kf2, int npairs, orbg_triangulation_pair *geo);
-int launch_triangulate(hipStream_t st, const orbg_keyframes &K, const orbg_keypoint *kps_raw,
-                       const float *depth, int cap, const orbg_kf_camera *cams, const int32_t *kf1,
-                       const int32_t *kf2, const int32_t *m12, int npairs, const float *scale,
-                       const float *sigma2, int nlevels, float scale_factor, float *x3d,
-                       int8_t *status, int32_t *nnew);
-int launch_fuse(hipStream_t st, const orbg_keyframes &K, int cap, const int32_t *kf,
-                const orbg_frustum_camera *cams, const orbg_map_point *mps, const uint8_t *mdesc,
-                const int32_t *mcounts, int mcap, int npairs, float th, const float *scale,
-                const float *inv_sigma2, int nlevels, int sim3, int32_t *best_idx,
-                int32_t *best_dist, int32_t *nfused, int32_t *err_flag);
-int launch_search_by_sim3(hipStream_t st, const orbg_keyframes &K, int cap, const int32_t *kf1,
-                          const int32_t *kf2, const orbg_sim3_pair *pairs,
-                          const orbg_map_point *mps, const uint8_t *mdesc,
-                          const uint8_t *matched1, const uint8_t *matched2, int npairs, float th,
-                          const float *scale, int nlevels, int32_t *vn, int32_t *match12,
-                          int32_t *nfound, int32_t *err_flag);
-int launch_rgbd(hipStream_t st, const void *depth, int u16, float factor, int w, int h,
-                size_t pitch, size_t istride, const orbg_keypoint *kps,
-                const orbg_keypoint *kps_un, const int32_t *counts, int fc, int nframes,
-                float mbf, float *uright, float *dout);
-int launch_distinctive(hipStream_t st, const uint8_t *pool, const int32_t *rows,
-                       const int32_t *off, int npoints, int32_t *best, uint8_t *desc_out);
-int launch_pose_opt(hipStream_t st, const orbg_pose_edge *edges, const int32_t *counts, int cap,
-                    const orbg_pose_camera *cams, const float *tcw_in, double *q_out,
-                    double *t_out, float *tcw_out, uint8_t *outlier, int32_t *ninliers,
-                    int nframes, void *prof);
-int launch_match_pose(hipStream_t st, const orbg_keypoint *kps, const int32_t *counts, int fc,
-                      const int32_t *f1, const int32_t *f2, const int32_t *m12, int npairs,
-                      const orbg_pose_camera &cam, float depth, const float *inv_sigma2, int nlev,
-                      orbg_pose_edge *edges, int32_t *ecount, orbg_pose_camera *cams,
-                      float *tcw0, float *tcw_out, uint8_t *outlier, double *q_out,
-                      double *t_out, int32_t *ninliers, void *prof);
-int launch_match_export(hipStream_t st, const int32_t *m12, const int32_t *f1,
-                        const int32_t *counts, int frame_cap, int npairs, int32_t *out);
-int launch_knn2(hipStream_t st, const uint8_t *q, int nq, const uint8_t *t, int nt, int32_t *out,
-                void *prof);
-int launch_init_match_single(hipStream_t st, const orbg_keypoint *k1, const uint8_t *d1, int n1,
-                             const orbg_keypoint *k2, const uint8_t *d2, int n2,
-                             orbg_bounds b, const float *prev, float *prev_out, int32_t *m12,
-                             int32_t *nm, int window, float nnratio, int check_ori, uint32_t *topk,
-                             int32_t *topk_n, void *prof, int cap);
-// bow_match_kernels.hip
-int launch_bow_match(hipStream_t st, const orbg_bow_frames &kf, const orbg_bow_frames &f, int cap,
-                     const int32_t *kf_index, const int32_t *f_index, int npairs, float nnratio,
-                     int check_ori, int32_t *match, int32_t *nmatch, bool kfkf = false);
-// ba_kernels.hip
-int launch_ba(hipStream_t st, const orbg_pose *poses, int npose, const double *points,
-              int npoint, const orbg_edge *edges, int nedge, const int32_t *pose_off,
-              const int32_t *pose_edges, const int32_t *point_off, const int32_t *point_edges,
-              orbg_edge_out *eout, double *hpose, double *bpose, double *hpoint, double *bpoint,
-              void *scratch, void *prof);
-int launch_ba_device(hipStream_t st, const orbg_pose *poses, int npose, const double *points,
-                     int npoint, const orbg_edge *edges, int nedge, const int32_t *pose_off,
-                     const int32_t *pose_edges, const int32_t *point_off,
-                     const int32_t *point_edges, orbg_edge_out *eout, double *hpose,
-                     double *bpose, double *hpoint, double *bpoint, double *scr, void *prof,
-                     bool jacobians, bool errors, double *hpl);
-size_t ba_rows_bytes(int nedge, int npose);
-// stereo_kernels.hip
-size_t stereo_scratch_bytes(int npairs, int frame_cap);
-int launch_stereo(hipStream_t st, const OrbgGeom &g, const orbg_keypoint *kps,
-                  const uint8_t *desc, const int32_t *counts, const int32_t *d_left,
-                  const int32_t *d_right, int npairs, const uint8_t *img0, int64_t img_fs,
-                  int img_pitch, const uint8_t *pyr, float bf, float min_z, void *scratch,
-                  float *uright, float *depth, int32_t *nvalid, void *prof);
-size_t ba_scratch_bytes(int npose, int npoint, int nedge);
-int launch_ba_errors(hipStream_t st, const orbg_pose *poses, const double *points,
-                     const orbg_edge *edges, int nedge, double *err, double *chi2, double *rho0,
-                     uint8_t *depth_ok, void *prof);
-int launch_ba_errors_packed(hipStream_t st, const orbg_pose *poses, const double *points,
-                            const BaPackedEdge *edges, const BaCam *cam, const BaInfo *info,
-                            int nedge, double *err, double *chi2, double *rho0,
-                            uint8_t *depth_ok, void *prof);
-int launch_ba_graph(hipStream_t st, const orbg_pose *poses, int npose, const double *points,
-                    int npoint, const BaPackedEdge *edges, const BaCam *cam, const BaInfo *info,
-                    int nedge, const int32_t *pose_off, const int32_t *pose_edges,
-                    const int32_t *point_off, const int32_t *point_edges, const BaGraphDev &gd,
-                    double *hpl, double *hpose, double *bpose, double *hpoint, double *bpoint,
-                    void *prof);
-}  // namespace orbg
 
 using namespace orbg;
 
@@ -189,7 +18,7 @@ using namespace orbg;
 // errors
 // ---------------------------------------------------------------------------
 static thread_local std::string g_err;
-static int set_err(int code, const char *fmt, ...)
+int orbg::set_err(int code, const char *fmt, ...)
 {
     char buf[512];
     va_list ap;
@@ -199,92 +28,15 @@ static int set_err(int code, const char *fmt, ...)
     g_err = buf;
     return code;
 }
-#define HIPCHK(x)                                                                          \
-    do {                                                                                   \
-        hipError_t e_ = (x);                                                               \
-        if (e_ != hipSuccess)                                                              \
-            return set_err(ORBG_EIO, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_),   \
-                           __FILE__, __LINE__);                                            \
-    } while (0)
-
 extern "C" const char *orbg_last_error(void) { return g_err.c_str(); }
 extern "C" int orbg_abi_version(void) { return ORBG_ABI_VERSION; }
 
 // ---------------------------------------------------------------------------
-// profiling: HIP events around every launch on the context stream
+// profiling: the ORBG_SKIP knob (orbg_ctx.h) and the hooks of the kernel files' launchers
 // ---------------------------------------------------------------------------
-namespace orbg {
-struct ProfKind {
-    const char *name;
-    double total_ms = 0;
-    int64_t launches = 0;
-};
-struct Prof {
-    bool on = false;
-    std::vector<ProfKind> kinds;
-    struct Pending {
-        int kind;
-        hipEvent_t a, b;
-    };
-    std::vector<Pending> pending;
-    std::vector<hipEvent_t> pool;
-    hipEvent_t get()
-    {
-        if (!pool.empty()) {
-            hipEvent_t e = pool.back();
-            pool.pop_back();
-            return e;
-        }
-        hipEvent_t e;
-        hipEventCreate(&e);
-        return e;
-    }
-    int kind(const char *n)
-    {
-        for (size_t i = 0; i < kinds.size(); i++)
-            if (!strcmp(kinds[i].name, n)) return (int)i;
-        kinds.push_back(ProfKind{n});
-        return (int)kinds.size() - 1;
-    }
-    void begin(hipStream_t s, const char *n, hipEvent_t *a)
-    {
-        if (!on) return;
-        *a = get();
-        hipEventRecord(*a, s);
-        (void)n;
-    }
-    void end(hipStream_t s, const char *n, hipEvent_t a)
-    {
-        if (!on) return;
-        hipEvent_t b = get();
-        hipEventRecord(b, s);
-        pending.push_back(Pending{kind(n), a, b});
-    }
-    void collect()
-    {
-        for (auto &p : pending) {
-            hipEventSynchronize(p.b);
-            float ms = 0;
-            hipEventElapsedTime(&ms, p.a, p.b);
-            kinds[p.kind].total_ms += ms;
-            kinds[p.kind].launches++;
-            pool.push_back(p.a);
-            pool.push_back(p.b);
-        }
-        pending.clear();
-    }
-};
-}  // namespace orbg
-
-// events on `st`, the stream the kernel is launched on (a local in every caller)
-// Developer what-if knob ORBG_SKIP=<names> (developer builds only, `make DEV=1` defines
-// ORBG_DEV_KNOBS): launches whose profile name is listed are not issued (their consumers
-// read the previous batch's buffers), so a bench run shows what a kernel costs inside the
-// overlapped pipeline.  Wrong results: a production build compiles it out and orbg_create
-// warns when the variable is set.
 #ifdef ORBG_DEV_KNOBS
-static std::atomic<int> g_extract_batches{0};  // batches issued, all contexts (ORBG_SKIP_AFTER)
-static bool prof_skip(const char *name)
+std::atomic<int> orbg::g_extract_batches{0};
+bool orbg::prof_skip(const char *name)
 {
     static const char *skip = getenv("ORBG_SKIP");
     static const int after = getenv("ORBG_SKIP_AFTER") ? atoi(getenv("ORBG_SKIP_AFTER")) : 0;
@@ -294,235 +46,18 @@ static bool prof_skip(const char *name)
         if ((p == skip || p[-1] == ',') && (p[n] == 0 || p[n] == ',')) return true;
     return false;
 }
-#else
-static inline bool prof_skip(const char *) { return false; }
 #endif
-#define PROF_LAUNCH(ctxp, name, ...)                                                       \
-    do {                                                                                   \
-        if (prof_skip(name)) break;                                                        \
-        hipEvent_t ev_a_ = nullptr;                                                        \
-        (ctxp)->prof.begin(st, name, &ev_a_);                                              \
-        __VA_ARGS__;                                                                       \
-        (ctxp)->prof.end(st, name, ev_a_);                                                 \
-    } while (0)
-
-// ---------------------------------------------------------------------------
-// context
-// ---------------------------------------------------------------------------
-struct orbg_ctx {
-    int device = 0;
-    orbg_params p{};
-    hipStream_t stream = nullptr;
-    hipStream_t own_stream = nullptr;
-    // second stream for independent work inside one call (blur beside FAST+quadtree, knn2
-    // beside SearchForInitialization); forked from / joined into `stream` with events
-    hipStream_t aux_stream = nullptr;
-    // quadtree stream (high priority, its own hardware queue): the quadtree runs beside the
-    // GaussianBlur, fork after the FAST cells (ev_fast), join before k_octree (ev_oct).
-    // oct_mode 0: everything on the extraction stream, 1: level 0 only, 2: all levels.
-    hipStream_t ostream = nullptr;
-    hipEvent_t ev_fast = nullptr, ev_oct = nullptr;
-    // pipelined front, level 0 (FAST cells + GaussianBlur need only the input images) on
-    // `fstream` beside the pyramid (ORBG_SIDE: 0 off, 1 normal priority, 2 high)
-    hipStream_t fstream = nullptr;
-    int side_mode = 1;
-    hipEvent_t ev_f0[2] = {nullptr, nullptr}, ev_b0[2] = {nullptr, nullptr},
-               ev_pfork[2] = {nullptr, nullptr}, ev_pyr[2] = {nullptr, nullptr};
-    bool blur_side = false;  // ORBG_BLUR_SIDE
-    // non-pipelined batches (the single-frame drop-in): k_octree, the fallback quadtree for
-    // levels past k_octree_lds' capacity, on `fstream` beside the k_octree_lds launches once
-    // every level's FAST cells are written (ev_big_a: level 0 on the quadtree stream, ev_big_b:
-    // levels 1.. on the extraction stream), joined before k_orient_desc (ev_big); it only scans
-    // the cell counts unless a level overflows.  ORBG_BIG_SIDE=1 (off by default: the single
-    // frame measured 0.26 -> 0.32-0.36 ms, the level-1.. FAST launch 15 -> 51 us behind the
-    // extra stream's waits, profiles/r05q_single_ab.txt)
-    bool big_side = false;
-    hipEvent_t ev_big_a = nullptr, ev_big_b = nullptr, ev_big = nullptr;
-    // small batches: the side blur on `fstream` right behind k_pyramid (ORBG_BLUR_Q3), joined
-    // before k_orient_desc
-    bool blur_q3 = false;
-    bool sblur = true;  // ORBG_SBLUR=0: small batches blur on the extraction stream (A/B)
-    hipEvent_t ev_sblur = nullptr;
-    // ORBG_OCT_GATE (read at orbg_create, default 1): the quadtree fallback launches of a
-    // pipelined batch (the split level-0 pair's second launch, k_octree) exit at once unless an
-    // earlier launch of the batch flagged a level for them (d_err[3], d_err[2]); 0 = they
-    // always scan (A/B, and the parity test's ungated twin)
-    bool oct_gate = true;
-    bool fast_blur_env = false;  // ORBG_FAST_BLUR (read at orbg_create): the fused blur plan
-    bool blur_tiled_env = true;  // ORBG_BLUR_TILED (read at orbg_create; 0: row-major blur)
-    bool serial = false;     // orbg_set_serial: no stream overlap (isolated kernel timing)
-    // orbg_extract's single-frame hipGraphs: the whole frame (H2D of the pinned input, the
-    // extraction's launches on the context and quadtree streams, k_pack_frame, D2H of the
-    // packed outputs) captured once per output slot and image size, then replayed with one
-    // hipGraphLaunch.  ORBG_GRAPH=1|2|3 (graph_mode below); 0, the default, launches eagerly.
-    int graph_mode = 0;
-    hipGraphExec_t gexec[2] = {nullptr, nullptr};
-    uint64_t gkey[2] = {0, 0};   // (plan generation, w, h) the graph was captured for
-    int gwarm[2] = {0, 0};       // eager frames seen for gkey_next (capture after one)
-    uint64_t gkey_seen[2] = {0, 0};
-    uint64_t plan_gen = 0;
-    uint8_t *h_gin = nullptr, *h_gout = nullptr;  // pinned graph input / output
-    size_t gin_bytes = 0, gout_bytes = 0;
-    bool ba_jacobians = true;  // orbg_ba_set_jacobians
-    bool ba_edge_errors = true;  // orbg_ba_set_edge_errors
-    int oct_mode = 0;
-    int blur0_mode = 0;  // measured: 2.013 vs 2.025 ms per 256 frames with it on
-    int fast0_mode = 1;  // level-0 FAST cells on `ostream` beside the resize chain (ORBG_FAST0)
-    // Pipelined batches (orbg_set_pipeline): the front of a batch (pyramid, FAST cells,
-    // GaussianBlur: image work) runs on `stream`, its back (quadtree, orientation +
-    // descriptors, stereo: keypoint work) on `ostream`, so the front of batch k+1 overlaps
-    // the back of batch k.  The per-batch intermediates (pyramid, blur, FAST cells) alternate
-    // between two slots with the outputs: ev_cells[s] / ev_front[s] = slot s's FAST cells /
-    // whole front written (on `stream`), ev_back[s] = slot s's last back reader done (on
-    // `ostream`); the front into slot s waits for ev_back[s].
-    int pipelined = 0;
-    bool last_piped = false;  // the last batch took the pipelined path (back_stream)
-    // stereo summary (orbg_stereo_summary) on the match stream: ev_sback = stereo outputs
-    // written (back stream), ev_ssum = the summary's reads done (match stream; the next
-    // stereo batch waits for it before overwriting d_snvalid / d_spairs)
-    hipEvent_t ev_sback = nullptr, ev_ssum = nullptr;
-    bool ssum_pending = false;
-    // caller reads of the outputs (orbg_batch_acquire / orbg_batch_release): ev_rel[s] = the
-    // caller's reads of output slot s issued so far, ev_srel = of the stereo outputs; the
-    // slot's next extraction / the next stereo pass waits for them
-    hipEvent_t ev_rel[2] = {nullptr, nullptr}, ev_srel = nullptr;
-    bool rel_pending[2] = {false, false}, srel_pending = false;
-    // entry points that write caller buffers on `mstream` (orbg_batch_summary /
-    // orbg_batch_matches / orbg_match_pose_batch_device / orbg_stereo_summary) first order
-    // `mstream` after the work queued on the context stream so far (ev_caller): a fill the
-    // caller queued there before the call can never land after liborbg's write
-    hipEvent_t ev_caller = nullptr;
-    hipEvent_t ev_cells[2] = {nullptr, nullptr}, ev_front[2] = {nullptr, nullptr};
-    hipEvent_t ev_back[2] = {nullptr, nullptr};
-    bool back_pending[2] = {false, false};
-    hipEvent_t ev_fork[2] = {nullptr, nullptr}, ev_join[2] = {nullptr, nullptr};
-    // Batch matching and the trajectory summary run on `mstream`, so the matching of batch k
-    // overlaps the extraction of batch k+1 on `stream`.  The per-frame outputs (kps, desc,
-    // counts) alternate between two slots: ev_ext[s] = slot s written (on `stream`),
-    // ev_mat[s] = slot s no longer read (on `mstream`); extraction into slot s waits for
-    // ev_mat[s], matching of slot s waits for ev_ext[s].
-    hipStream_t mstream = nullptr;
-    hipEvent_t ev_ext[2] = {nullptr, nullptr}, ev_mat[2] = {nullptr, nullptr};
-    bool mat_pending[2] = {false, false};
-    int slot = 0;  // slot of the last extraction
-    float scale[16], inv_scale[16], sigma2[16], inv_sigma2[16];
-    int32_t fpl[16], umax[16];
-    // plan
-    int gw = 0, gh = 0, gbatch = 0;
-    OrbgGeom geom{};
-    std::vector<OrbgCell> cells;
-    std::vector<int32_t> tile_base;  // k_blur2 tile bases (L + 1)
-    // k_fast_rows strips (fast_rows_kernels.hip): fr_ok = every level's cells fit a strip
-    // (wCell <= 32); ftile_base[l] = first strip of level l (L + 1 entries); fr_mode 0 forces
-    // k_fast2 (ORBG_FAST_ROWS=0, developer A/B)
-    OrbgFastTile *d_ftiles = nullptr;
-    std::vector<int32_t> ftile_base;
-    bool fr_ok = false;
-    int fr_mode = 0;  // k_fast_rows opt-in (ORBG_FAST_ROWS=1) until it beats k_fast2
-    OctLdsDims oct_dims[3] = {};  // levels 0, 1.., and level 0's batch first launch (kcap 0: none)
-    // device
-    OrbgGeom *d_geom = nullptr;
-    OrbgCell *d_cells = nullptr;
-    int32_t *d_tile_base = nullptr;
-    int2 *d_rtab = nullptr;
-    // k_pyramid (all levels in one launch): octet / row records and band closures; pyr_ok
-    // = the plan passed k_pyramid's checks (else the k_resize chain)
-    uint4 *d_ptab = nullptr;
-    int4 *d_ytab4 = nullptr;
-    int4 *d_bands = nullptr;
-    PyrArgs pyr_args{};
-    bool pyr_ok = false;
-    int pyr_wg = 512;  // k_pyramid workgroup size (ORBG_PYR_WG)
-    uint32_t *d_ctab = nullptr;  // quadtree path-code tables (xs | ys per level)
-    uint4 *d_odtab = nullptr;    // k_orient_desc IC_Angle byte tables (make_od_tab)
-    uint8_t *d_img = nullptr;
-    size_t img_bytes = 0;
-    uint8_t *d_pack = nullptr;  // orbg_download_frame: error word, count, kps, desc
-    size_t pack_bytes = 0;
-    // zero-copy host block (coherent pinned, device-mapped; ORBG_ZC, default 1): k_pack_frame
-    // stores orbg_download_frame's packed outputs straight into it, and the
-    // SearchForInitialization host entry's inputs are read from it by one copy kernel and its
-    // outputs written into it by the resolver -- kernels instead of DMA submissions, whose
-    // start latency (6-9 us each) the single-frame path otherwise waits for
-    uint8_t *h_zc = nullptr, *h_zc_dev = nullptr;
-    size_t zc_bytes = 0;
-    // orbg_extract's image in coherent host memory, pulled by k_copy16 (ORBG_IMG_PULL)
-    uint8_t *h_imz = nullptr, *h_imz_dev = nullptr;
-    size_t imz_bytes = 0;
-    int zc_mode = -1;  // -1: read ORBG_ZC on first use
-    // orbg_extract's zero-copy outputs written by k_orient_desc itself (the packed block's
-    // device pointer while launch_extract runs; null otherwise)
-    uint8_t *hc_dst = nullptr;
-    bool hc_done = false;  // the last extraction's frame 0 is already in the packed block
-    // with hc_dst: k_octree (the fallback quadtree) not launched; a level it would have taken
-    // shows in the packed header's word 3 and the frame is extracted again with it
-    bool skip_big = false;
-    // the single-frame skip path's fallback tag (OctLdsDims::tag; 0 = off) and its counter
-    int32_t oct_tag = 0;
-    int32_t sf_seq = 0;
-    uint8_t *d_pyr = nullptr, *d_blur = nullptr;  // = pyr_slot[slot], blur_slot[slot]
-    int32_t *d_cell_cnt = nullptr;                 // = cnt_slot[slot]
-    uint2 *d_cell_kp = nullptr;                    // = ckp_slot[slot]
-    uint8_t *pyr_slot[2] = {nullptr, nullptr}, *blur_slot[2] = {nullptr, nullptr};
-    int32_t *cnt_slot[2] = {nullptr, nullptr};
-    uint2 *ckp_slot[2] = {nullptr, nullptr};
-    uint32_t *d_keys = nullptr, *d_knode = nullptr, *d_act = nullptr;
-    uint8_t *d_qk = nullptr;
-    int4 *d_nodes = nullptr;
-    uint32_t *d_lvl_kp = nullptr;
-    uint16_t *d_lvl_idx = nullptr;  // slot -> winner list position (octree -> orient)
-    int32_t *d_lvl_cnt = nullptr;
-    orbg_keypoint *d_kps = nullptr;  // = kps_slot[slot]
-    uint8_t *d_desc = nullptr;        // = desc_slot[slot]
-    int32_t *d_counts = nullptr;      // = counts_slot[slot]
-    orbg_keypoint *kps_slot[2] = {nullptr, nullptr};
-    uint8_t *desc_slot[2] = {nullptr, nullptr};
-    int32_t *counts_slot[2] = {nullptr, nullptr};
-    int32_t *d_err = nullptr;
-    // last batch
-    const uint8_t *last_img = nullptr;
-    int64_t last_fs = 0;
-    int last_pitch = 0;
-    int last_n = 0;
-    // matching (batch)
-    int32_t *d_pairs = nullptr;
-    int pair_cap = 0;
-    std::vector<int32_t> h_pairs;  // last uploaded (f1, f2) lists
-    int32_t *d_knn = nullptr, *d_m12 = nullptr, *d_nm = nullptr;
-    uint32_t *d_topk = nullptr;
-    int32_t *d_topk_n = nullptr;
-    int last_npairs = 0;
-    // stereo (ComputeStereoMatches) of the last batch
-    int32_t *d_spairs = nullptr;
-    std::vector<int32_t> h_spairs;  // last uploaded (left, right) lists
-    float *d_uright = nullptr, *d_depth = nullptr;
-    int32_t *d_snvalid = nullptr;
-    void *d_sscr = nullptr;
-    int stereo_cap = 0, last_nstereo = 0;
-    // single-pair / host-data scratch
-    void *d_scr = nullptr;
-    size_t scr_bytes = 0;
-    // pinned host staging of the host-data entry points (orbg_extract, orbg_download_frame,
-    // orbg_search_for_initialization): one DMA per direction instead of pageable copies
-    uint8_t *h_stage = nullptr;
-    size_t stage_bytes = 0;
-    // tracking matchers: K-lists of the queries
-    void *d_trk = nullptr;
-    size_t trk_bytes = 0;
-    void *d_sim3 = nullptr;  // SearchBySim3's vnMatch1 / vnMatch2 scratch
-    size_t sim3_bytes = 0;
-    // batched-sequence pose stub (orbg_match_pose_batch_device): edges, counts, cameras, poses
-    void *d_mpose = nullptr;
-    size_t mpose_bytes = 0;
-    // orbg_set_camera: distorted camera of the batched-sequence mode (has_cam: k1 != 0);
-    // the batch matching undistorts into d_kps_un ([kps_un_frames][frame_cap], match stream)
-    bool has_cam = false;
-    orbg_camera cam{};
-    orbg_keypoint *d_kps_un = nullptr;
-    size_t kps_un_n = 0;
-    bool kps_un_valid = false;
-    Prof prof;
-};
+namespace orbg {
+void prof_begin(Prof *prof, hipStream_t s, const char *n, hipEvent_t *a)
+{
+    prof->begin(s, n, a);
+}
+void prof_end(Prof *prof, hipStream_t s, const char *n, hipEvent_t a)
+{
+    prof->end(s, n, a);
+}
+bool prof_skip_name(const char *n) { return prof_skip(n); }
+}  // namespace orbg
 
 extern "C" void orbg_params_default(orbg_params *p)
 {
@@ -682,19 +217,8 @@ static std::vector<uint4> make_od_tab(const int32_t *umax)
     return t;
 }
 
-template <typename T>
-static int dalloc(T **p, size_t n)
-{
-    if (n == 0) n = 1;
-    hipError_t e = hipMalloc((void **)p, n * sizeof(T));
-    if (e != hipSuccess)
-        return set_err(ORBG_ENOMEM, "hipMalloc(%zu bytes): %s", n * sizeof(T),
-                       hipGetErrorString(e));
-    return ORBG_OK;
-}
-
 // pinned host staging buffer of at least `bytes` (grown on demand)
-static int stage(orbg_ctx *c, size_t bytes, uint8_t **out)
+int orbg::stage(orbg_ctx *c, size_t bytes, uint8_t **out)
 {
     if (c->stage_bytes < bytes) {
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -707,6 +231,21 @@ static int stage(orbg_ctx *c, size_t bytes, uint8_t **out)
         c->stage_bytes = nb;
     }
     *out = c->h_stage;
+    return ORBG_OK;
+}
+
+// device scratch of at least `bytes` (grown on demand; one block, shared by every such entry)
+int orbg::scratch(orbg_ctx *c, size_t bytes, void **p)
+{
+    if (c->scr_bytes < bytes) {
+        if (c->d_scr) hipFree(c->d_scr);
+        c->d_scr = nullptr;
+        c->scr_bytes = 0;
+        hipError_t e = hipMalloc(&c->d_scr, bytes);
+        if (e != hipSuccess) return set_err(ORBG_ENOMEM, "scratch %zu bytes", bytes);
+        c->scr_bytes = bytes;
+    }
+    *p = c->d_scr;
     return ORBG_OK;
 }
 
@@ -2000,11 +1539,6 @@ static int launch_extract_pipe(orbg_ctx *c, const uint8_t *d_imgs, int B, int pi
     return ORBG_OK;
 }
 
-// stream the last batch's per-frame outputs were written on (and stereo runs on): the back
-// stream only if that batch actually took the pipelined path (orbg_set_serial on a
-// pipelined context runs everything on the context stream)
-static hipStream_t back_stream(orbg_ctx *c) { return c->last_piped ? c->ostream : c->stream; }
-
 static int launch_extract(orbg_ctx *c, const uint8_t *d_imgs, int B, int pitch, int64_t fs)
 {
     const OrbgGeom &G = c->geom;
@@ -2854,22 +2388,6 @@ extern "C" int orbg_descriptor_distance(const uint8_t *a, const uint8_t *b)
     return d;
 }
 
-static int scratch(orbg_ctx *c, size_t bytes, void **p)
-{
-    if (c->scr_bytes < bytes) {
-        if (c->d_scr) hipFree(c->d_scr);
-        c->d_scr = nullptr;
-        c->scr_bytes = 0;
-        hipError_t e = hipMalloc(&c->d_scr, bytes);
-        if (e != hipSuccess) return set_err(ORBG_ENOMEM, "scratch %zu bytes", bytes);
-        c->scr_bytes = bytes;
-    }
-    *p = c->d_scr;
-    return ORBG_OK;
-}
-
-static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 extern "C" int orbg_match_batch_device(orbg_ctx *c, const int32_t *f1, const int32_t *f2,
                                        int npairs, int window, float nnratio, int check_ori)
 {
@@ -2967,19 +2485,11 @@ extern "C" int orbg_match_pose_batch_device(orbg_ctx *c, const orbg_pose_camera 
     HIPCHK(hipSetDevice(c->device));
     const int P = c->last_npairs;
     const size_t fc = (size_t)c->geom.frame_cap;
-    size_t o = 0;
-    const size_t oe = o;
-    o += al256((size_t)P * fc * sizeof(orbg_pose_edge));
-    const size_t on = o;
-    o += al256((size_t)P * 4);
-    const size_t oc = o;
-    o += al256((size_t)P * sizeof(orbg_pose_camera));
-    const size_t ot0 = o;
-    o += al256((size_t)P * 48);
-    const size_t ot1 = o;
-    o += al256((size_t)P * 48);
-    const size_t ool = o;
-    o += al256((size_t)P * fc);
+    Layout L;
+    const size_t oe = L.take((size_t)P * fc * sizeof(orbg_pose_edge)), on = L.take((size_t)P * 4),
+                 oc = L.take((size_t)P * sizeof(orbg_pose_camera)), ot0 = L.take((size_t)P * 48),
+                 ot1 = L.take((size_t)P * 48), ool = L.take((size_t)P * fc);
+    const size_t o = L.total();
     if (c->mpose_bytes < o) {
         HIPCHK(hipStreamSynchronize(c->mstream));  // a previous pass may still read it
         if (c->d_mpose) hipFree(c->d_mpose);
@@ -2995,9 +2505,9 @@ extern "C" int orbg_match_pose_batch_device(orbg_ctx *c, const orbg_pose_camera 
     HIPCHK(hipStreamWaitEvent(c->mstream, c->ev_ext[s], 0));  // (the matching already does)
     const int rc = launch_match_pose(
         c->mstream, c->kps_un_valid ? c->d_kps_un : c->d_kps, c->d_counts, (int)fc, c->d_pairs,
-        c->d_pairs + c->pair_cap, c->d_m12, P, *cam, depth, c->inv_sigma2, c->p.nlevels, (orbg_pose_edge *)(b + oe),
-        (int32_t *)(b + on), (orbg_pose_camera *)(b + oc), (float *)(b + ot0),
-        (float *)(b + ot1), b + ool, d_q, d_t, d_ninliers, &c->prof);
+        c->d_pairs + c->pair_cap, c->d_m12, P, *cam, depth, c->inv_sigma2, c->p.nlevels, L.at<orbg_pose_edge>(b, oe),
+        L.at<int32_t>(b, on), L.at<orbg_pose_camera>(b, oc), L.at<float>(b, ot0),
+        L.at<float>(b, ot1), b + ool, d_q, d_t, d_ninliers, &c->prof);
     if (rc) return set_err(rc, "pose stub launch failed");
     HIPCHK(hipEventRecord(c->ev_mat[s], c->mstream));
     c->mat_pending[s] = true;
@@ -3277,27 +2787,14 @@ extern "C" int orbg_search_for_initialization(orbg_ctx *c, const orbg_keypoint *
     last0 = std::max(last0, 1);
     const size_t m1 = (size_t)n1, l1 = (size_t)std::min(n1, last0);
     const size_t l2 = (size_t)std::max(std::min(n2, last0), 1);
-    size_t o = 0;
-    const size_t ok1 = o;
-    o += al256(l1 * sizeof(orbg_keypoint));
-    const size_t od1 = o;
-    o += al256(l1 * 32);
-    const size_t ok2 = o;
-    o += al256(l2 * sizeof(orbg_keypoint));
-    const size_t od2 = o;
-    o += al256(l2 * 32);
-    const size_t opv = o;
-    o += al256(l1 * 8);
-    const size_t om = o;
-    o += al256(m1 * 4 + 4);
-    const size_t otk = o;
-    o += al256(l1 * 8 * ORBG_MATCH_TOPK);
-    const size_t otn = o;
-    o += al256(l1 * 4);
-    void *s;
-    int rc = scratch(c, o, &s);
+    Layout L;
+    const size_t ok1 = L.take(l1 * sizeof(orbg_keypoint)), od1 = L.take(l1 * 32),
+                 ok2 = L.take(l2 * sizeof(orbg_keypoint)), od2 = L.take(l2 * 32),
+                 opv = L.take(l1 * 8), om = L.take(m1 * 4 + 4),
+                 otk = L.take(l1 * 8 * ORBG_MATCH_TOPK), otn = L.take(l1 * 4);
+    uint8_t *b;
+    int rc = L.device(c, &b);
     if (rc) return rc;
-    uint8_t *b = (uint8_t *)s;
     // inputs packed into pinned staging with the device layout, one DMA each way; zero-copy:
     // the staging is the coherent host block, uploaded by k_copy16, and the resolver writes
     // vnMatches12, the count and vbPrevMatched straight back into it
@@ -3323,11 +2820,11 @@ extern "C" int orbg_search_for_initialization(orbg_ctx *c, const orbg_keypoint *
     }
     // outputs: device copies behind one D2H, or the host block itself (zc)
     uint8_t *ob = zc ? hd : b;
-    rc = launch_init_match_single(c->stream, (const orbg_keypoint *)(b + ok1), b + od1, n1,
-                                  (const orbg_keypoint *)(b + ok2), b + od2, n2, *bounds2,
-                                  (const float *)(b + opv), (float *)(ob + opv), (int32_t *)(ob + om),
-                                  (int32_t *)(ob + om + m1 * 4), window, nnratio, check_ori,
-                                  (uint32_t *)(b + otk), (int32_t *)(b + otn), &c->prof, last0);
+    rc = launch_init_match_single(c->stream, L.at<orbg_keypoint>(b, ok1), b + od1, n1,
+                                  L.at<orbg_keypoint>(b, ok2), b + od2, n2, *bounds2,
+                                  L.at<float>(b, opv), L.at<float>(ob, opv), L.at<int32_t>(ob, om),
+                                  L.at<int32_t>(ob, om + m1 * 4), window, nnratio, check_ori,
+                                  L.at<uint32_t>(b, otk), L.at<int32_t>(b, otn), &c->prof, last0);
     if (rc) return rc;
     int32_t nm = 0;
     if (!zc) HIPCHK(hipMemcpyAsync(hs + opv, b + opv, otk - opv, hipMemcpyDeviceToHost, c->stream));
@@ -3403,33 +2900,22 @@ extern "C" int orbg_ba_errors(orbg_ctx *c, const orbg_pose *poses, int npose, co
     if (nedge == 0) return ORBG_OK;
     HIPCHK(hipSetDevice(c->device));
     const size_t ne = (size_t)nedge;
-    size_t o = 0;
-    const size_t opo = o;
-    o += al256((size_t)npose * sizeof(orbg_pose));
-    const size_t opt = o;
-    o += al256((size_t)npoint * 24);
-    const size_t oed = o;
-    o += al256(ne * sizeof(orbg_edge));
-    const size_t oer = o;  // outputs: err, chi2, rho0, depth_ok (one D2H copy)
-    o += al256(ne * 24);
-    const size_t och = o;
-    o += al256(ne * 8);
-    const size_t orh = o;
-    o += al256(ne * 8);
-    const size_t odk = o;
-    o += al256(ne);
-    void *sp;
-    if ((rc = scratch(c, o, &sp))) return rc;
-    uint8_t *b = (uint8_t *)sp;
+    Layout L;
+    const size_t opo = L.take((size_t)npose * sizeof(orbg_pose)), opt = L.take((size_t)npoint * 24),
+                 oed = L.take(ne * sizeof(orbg_edge));
+    // outputs: err, chi2, rho0, depth_ok (one D2H copy)
+    const size_t oer = L.take(ne * 24), och = L.take(ne * 8), orh = L.take(ne * 8), odk = L.take(ne);
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
     HIPCHK(hipMemcpyAsync(b + opo, poses, (size_t)npose * sizeof(orbg_pose), hipMemcpyHostToDevice,
                           c->stream));
     HIPCHK(hipMemcpyAsync(b + opt, points, (size_t)npoint * 24, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(b + oed, edges, ne * sizeof(orbg_edge), hipMemcpyHostToDevice, c->stream));
-    if ((rc = launch_ba_errors(c->stream, (const orbg_pose *)(b + opo), (const double *)(b + opt),
-                               (const orbg_edge *)(b + oed), nedge, (double *)(b + oer),
-                               (double *)(b + och), (double *)(b + orh), b + odk, &c->prof)))
+    if ((rc = launch_ba_errors(c->stream, L.at<orbg_pose>(b, opo), L.at<double>(b, opt),
+                               L.at<orbg_edge>(b, oed), nedge, L.at<double>(b, oer),
+                               L.at<double>(b, och), L.at<double>(b, orh), b + odk, &c->prof)))
         return set_err(ORBG_EIO, "k_ba_errors launch failed");
-    std::vector<uint8_t> h(o - oer);
+    std::vector<uint8_t> h(L.total() - oer);
     HIPCHK(hipMemcpyAsync(h.data(), b + oer, h.size(), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     c->prof.collect();
@@ -3563,9 +3049,79 @@ struct orbg_ba_graph {
     uint8_t *d_lm = nullptr;
 };
 
+// Device layout of a SchurPlanHost (structure) followed by the solve's scratch, from `base`
+// (nullptr: sizes only); returns the bytes.  The structure arrays are uploaded once per plan.
 static size_t schur_layout(const SchurPlanHost &P, int nedge, uint8_t *base, SchurArgs &A,
-                           size_t *structure_bytes);
-static int schur_upload(const SchurPlanHost &P, const SchurArgs &A, hipStream_t st);
+                           size_t *structure_bytes)
+{
+    size_t off = 0;
+    auto take = [&](size_t bytes) -> uint8_t * {
+        uint8_t *q = base ? base + off : nullptr;
+        off += al256(std::max(bytes, (size_t)1));
+        return q;
+    };
+    (void)nedge;
+    A.pidx = (const int32_t *)take(P.pidx.size() * 4);
+    A.free_pose = (const int32_t *)take(P.free_pose.size() * 4);
+    A.pt_off = (const int32_t *)take(P.pt_off.size() * 4);
+    A.pt_edges = (const int32_t *)take(P.pt_edges.size() * 4);
+    A.slot_point = (const int32_t *)take(P.slot_point.size() * 4);
+    A.slot_fidx = (const int32_t *)take(P.slot_fidx.size() * 4);
+    A.edge_pose = (const int32_t *)take(P.edge_pose.size() * 4);
+    A.blk_off = (const int32_t *)take(P.blk_off.size() * 4);
+    A.blk_pairs = (const int2 *)take(P.blk_pairs.size() * 8);
+    A.blk_i1 = (const int32_t *)take(P.blk_i1.size() * 4);
+    A.blk_i2 = (const int32_t *)take(P.blk_i2.size() * 4);
+    A.blk_seg = (const int32_t *)take(P.blk_seg.size() * 4);
+    A.blk_order = (const int32_t *)take(P.blk_order.size() * 4);
+    A.pose_off = (const int32_t *)take(P.pose_off.size() * 4);
+    A.pose_slots = (const int32_t *)take(P.pose_slots.size() * 4);
+    A.seg_lo = (const int32_t *)take(P.seg_lo.size() * 4);
+    A.seg_soff = (const int64_t *)take(P.seg_soff.size() * 8);
+    if (structure_bytes) *structure_bytes = off;
+    const size_t nslot = (size_t)std::max(P.pt_off.back(), 1);
+    A.rec = (double *)take((nslot + 256) * 24 * 8);  // k_schur_points' records (+ a workgroup's tail)
+    A.S = (double *)take((size_t)std::max<int64_t>(P.seg_soff.back(), 1) * 8);
+    A.x = (double *)take((size_t)std::max(6 * P.nfree, 1) * 8);
+    A.nslot = P.pt_off.back();
+    A.npose = P.npose;
+    A.npoint = P.npoint;
+    A.nfree = P.nfree;
+    A.nblk = P.nblk;
+    A.nseg = P.nseg;
+    A.max_seg = P.max_seg;
+    A.s_total = P.seg_soff.back();
+    return off;
+}
+
+// the structure arrays of P to their places in A (stream-ordered copies from host memory)
+static int schur_upload(const SchurPlanHost &P, const SchurArgs &A, hipStream_t st)
+{
+    auto up = [&](const void *dst, const void *src, size_t bytes) -> int {
+        if (bytes) HIPCHK(hipMemcpyAsync((void *)dst, src, bytes, hipMemcpyHostToDevice, st));
+        return ORBG_OK;
+    };
+    int rc;
+    if ((rc = up(A.pidx, P.pidx.data(), P.pidx.size() * 4)) ||
+        (rc = up(A.free_pose, P.free_pose.data(), P.free_pose.size() * 4)) ||
+        (rc = up(A.pt_off, P.pt_off.data(), P.pt_off.size() * 4)) ||
+        (rc = up(A.pt_edges, P.pt_edges.data(), P.pt_edges.size() * 4)) ||
+        (rc = up(A.slot_point, P.slot_point.data(), P.slot_point.size() * 4)) ||
+        (rc = up(A.slot_fidx, P.slot_fidx.data(), P.slot_fidx.size() * 4)) ||
+        (rc = up(A.edge_pose, P.edge_pose.data(), P.edge_pose.size() * 4)) ||
+        (rc = up(A.blk_off, P.blk_off.data(), P.blk_off.size() * 4)) ||
+        (rc = up(A.blk_pairs, P.blk_pairs.data(), P.blk_pairs.size() * 8)) ||
+        (rc = up(A.blk_i1, P.blk_i1.data(), P.blk_i1.size() * 4)) ||
+        (rc = up(A.blk_i2, P.blk_i2.data(), P.blk_i2.size() * 4)) ||
+        (rc = up(A.blk_seg, P.blk_seg.data(), P.blk_seg.size() * 4)) ||
+        (rc = up(A.blk_order, P.blk_order.data(), P.blk_order.size() * 4)) ||
+        (rc = up(A.pose_off, P.pose_off.data(), P.pose_off.size() * 4)) ||
+        (rc = up(A.pose_slots, P.pose_slots.data(), P.pose_slots.size() * 4)) ||
+        (rc = up(A.seg_lo, P.seg_lo.data(), P.seg_lo.size() * 4)) ||
+        (rc = up(A.seg_soff, P.seg_soff.data(), P.seg_soff.size() * 8)))
+        return rc;
+    return ORBG_OK;
+}
 
 // (re)build an orbg_ba_graph's Schur structure from its host edges and the stored fixed
 // flags, and upload it in stream order (no host synchronisation unless the buffer grows)
@@ -3905,27 +3461,22 @@ extern "C" int orbg_ba_graph_optimize_ctl(orbg_ctx *c, orbg_ba_graph *g, orbg_po
     HIPCHK(hipSetDevice(c->device));
     const size_t ne = (size_t)std::max(g->nedge, 1), np = (size_t)std::max(g->npose, 1),
                  nq = (size_t)std::max(g->npoint, 1);
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t r = o;
-        o += al256(bytes);
-        return r;
-    };
-    const size_t o_hpl = take(ne * 18 * 8), o_hp = take(np * 36 * 8), o_bp = take(np * 6 * 8),
-                 o_hq = take(nq * 9 * 8), o_bq = take(nq * 3 * 8), o_chi = take(ne * 8),
-                 o_rho = take(ne * 8), o_dxp = take(np * 6 * 8), o_dxq = take(nq * 3 * 8),
-                 o_sp = take(np * sizeof(orbg_pose)), o_sq = take(nq * 3 * 8),
-                 o_part = take((size_t)lm_reduce_groups() * 8), o_sc = take(4 * 8);
+    Layout L;
+    const size_t o_hpl = L.take(ne * 18 * 8), o_hp = L.take(np * 36 * 8), o_bp = L.take(np * 6 * 8),
+                 o_hq = L.take(nq * 9 * 8), o_bq = L.take(nq * 3 * 8), o_chi = L.take(ne * 8),
+                 o_rho = L.take(ne * 8), o_dxp = L.take(np * 6 * 8), o_dxq = L.take(nq * 3 * 8),
+                 o_sp = L.take(np * sizeof(orbg_pose)), o_sq = L.take(nq * 3 * 8),
+                 o_part = L.take((size_t)lm_reduce_groups() * 8), o_sc = L.take(4 * 8);
     if (!g->d_lm) {
-        hipError_t e = hipMalloc((void **)&g->d_lm, o);
-        if (e != hipSuccess) return set_err(ORBG_ENOMEM, "LM workspace %zu bytes", o);
+        hipError_t e = hipMalloc((void **)&g->d_lm, L.total());
+        if (e != hipSuccess) return set_err(ORBG_ENOMEM, "LM workspace %zu bytes", L.total());
     }
     uint8_t *b = g->d_lm;
-    double *hpl = (double *)(b + o_hpl), *hp = (double *)(b + o_hp), *bp = (double *)(b + o_bp),
-           *hq = (double *)(b + o_hq), *bq = (double *)(b + o_bq), *chi = (double *)(b + o_chi),
-           *rho = (double *)(b + o_rho), *dxp = (double *)(b + o_dxp), *dxq = (double *)(b + o_dxq),
-           *sq = (double *)(b + o_sq), *part = (double *)(b + o_part), *sc = (double *)(b + o_sc);
-    orbg_pose *sp = (orbg_pose *)(b + o_sp);
+    double *hpl = L.at<double>(b, o_hpl), *hp = L.at<double>(b, o_hp), *bp = L.at<double>(b, o_bp),
+           *hq = L.at<double>(b, o_hq), *bq = L.at<double>(b, o_bq), *chi = L.at<double>(b, o_chi),
+           *rho = L.at<double>(b, o_rho), *dxp = L.at<double>(b, o_dxp), *dxq = L.at<double>(b, o_dxq),
+           *sq = L.at<double>(b, o_sq), *part = L.at<double>(b, o_part), *sc = L.at<double>(b, o_sc);
+    orbg_pose *sp = L.at<orbg_pose>(b, o_sp);
     // sc[0] active robust chi2, sc[1] computeScale, sc[2] max |H_jj|, sc[3] the solver's ok
     hipStream_t st = c->stream;
     int rc;
@@ -4133,19 +3684,6 @@ extern "C" int orbg_local_ba_optimize(orbg_ctx *c, orbg_pose *poses, int npose, 
     return ORBG_OK;
 }
 
-// profiling hook used by the other translation units
-namespace orbg {
-void prof_begin(void *prof, hipStream_t s, const char *n, hipEvent_t *a)
-{
-    ((Prof *)prof)->begin(s, n, a);
-}
-void prof_end(void *prof, hipStream_t s, const char *n, hipEvent_t a)
-{
-    ((Prof *)prof)->end(s, n, a);
-}
-bool prof_skip_name(const char *n) { return prof_skip(n); }
-}  // namespace orbg
-
 // ---------------------------------------------------------------------------
 // tracking matchers (ORBmatcher::SearchByProjection x 2)
 // ---------------------------------------------------------------------------
@@ -4238,22 +3776,16 @@ static int track_host(orbg_ctx *c, int mode, const orbg_keypoint *kps, const uin
     if (n == 0 || nq == 0) return ORBG_OK;
     HIPCHK(hipSetDevice(c->device));
     const size_t fc = (size_t)n, qc = (size_t)nq;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += al256(bytes);
-        return o;
-    };
-    const size_t o_kps = take(fc * sizeof(orbg_keypoint)), o_desc = take(fc * 32);
-    const size_t o_ur = uright ? take(fc * 4) : 0, o_tk = taken0 ? take(fc) : 0;
-    const size_t o_cnt = take(8), o_b = take(sizeof(orbg_bounds)), o_q = take(qc * qrec);
-    const size_t o_qd = take(qc * 32), o_cam = take(sizeof(orbg_track_camera));
-    const size_t o_fcam = take(sizeof(orbg_frustum_camera));
-    const size_t o_match = take(fc * 4), o_nm = take(4);
-    void *s;
-    int rc = scratch(c, off, &s);
+    Layout L;
+    const size_t o_kps = L.take(fc * sizeof(orbg_keypoint)), o_desc = L.take(fc * 32);
+    const size_t o_ur = uright ? L.take(fc * 4) : 0, o_tk = taken0 ? L.take(fc) : 0;
+    const size_t o_cnt = L.take(8), o_b = L.take(sizeof(orbg_bounds)), o_q = L.take(qc * qrec);
+    const size_t o_qd = L.take(qc * 32), o_cam = L.take(sizeof(orbg_track_camera));
+    const size_t o_fcam = L.take(sizeof(orbg_frustum_camera));
+    const size_t o_match = L.take(fc * 4), o_nm = L.take(4);
+    uint8_t *b;
+    int rc = L.device(c, &b);
     if (rc) return rc;
-    uint8_t *b = (uint8_t *)s;
     const int32_t cnts[2] = {n, nq};
     HIPCHK(hipMemcpyAsync(b + o_kps, kps, fc * sizeof(orbg_keypoint), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(b + o_desc, desc, fc * 32, hipMemcpyHostToDevice, c->stream));
@@ -4268,24 +3800,24 @@ static int track_host(orbg_ctx *c, int mode, const orbg_keypoint *kps, const uin
     if (fcam)
         HIPCHK(hipMemcpyAsync(b + o_fcam, fcam, sizeof(*fcam), hipMemcpyHostToDevice, c->stream));
     orbg_track_batch tb{};
-    tb.kps = (const orbg_keypoint *)(b + o_kps);
+    tb.kps = L.at<orbg_keypoint>(b, o_kps);
     tb.desc = b + o_desc;
-    tb.uright = uright ? (const float *)(b + o_ur) : nullptr;
+    tb.uright = uright ? L.at<float>(b, o_ur) : nullptr;
     tb.taken0 = taken0 ? b + o_tk : nullptr;
-    tb.counts = (const int32_t *)(b + o_cnt);
-    tb.bounds = (const orbg_bounds *)(b + o_b);
+    tb.counts = L.at<int32_t>(b, o_cnt);
+    tb.bounds = L.at<orbg_bounds>(b, o_b);
     tb.frame_cap = n;
     tb.queries = b + o_q;
     tb.qdesc = b + o_qd;
-    tb.qcounts = (const int32_t *)(b + o_cnt) + 1;
+    tb.qcounts = L.at<int32_t>(b, o_cnt) + 1;
     tb.query_cap = nq;
-    tb.cams = cam ? (const orbg_track_camera *)(b + o_cam) : nullptr;
+    tb.cams = cam ? L.at<orbg_track_camera>(b, o_cam) : nullptr;
     tb.th = th;
     tb.nnratio = nnratio;
     tb.check_ori = check_ori;
-    tb.match = (int32_t *)(b + o_match);
-    tb.nmatches = (int32_t *)(b + o_nm);
-    tb.fcams = fcam ? (const orbg_frustum_camera *)(b + o_fcam) : nullptr;
+    tb.match = L.at<int32_t>(b, o_match);
+    tb.nmatches = L.at<int32_t>(b, o_nm);
+    tb.fcams = fcam ? L.at<orbg_frustum_camera>(b, o_fcam) : nullptr;
     tb.orb_dist = orb_dist;
     if ((rc = track_run(c, mode, &tb, 1))) return rc;
     int32_t nm = 0;
@@ -4379,29 +3911,23 @@ extern "C" int orbg_pose_optimization(orbg_ctx *c, const orbg_pose_edge *edges, 
         return set_err(ORBG_EINVAL, "NULL argument");
     if (n < 0) return set_err(ORBG_EINVAL, "negative size");
     HIPCHK(hipSetDevice(c->device));
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += al256(bytes);
-        return o;
-    };
-    const size_t o_e = take((size_t)std::max(n, 1) * sizeof(orbg_pose_edge)), o_n = take(4);
-    const size_t o_cam = take(sizeof(orbg_pose_camera)), o_tin = take(48), o_q = take(32);
-    const size_t o_t = take(24), o_tout = take(48), o_out = take((size_t)std::max(n, 1));
-    const size_t o_ni = take(4);
-    void *s;
-    int rc = scratch(c, off, &s);
+    Layout L;
+    const size_t o_e = L.take((size_t)std::max(n, 1) * sizeof(orbg_pose_edge)), o_n = L.take(4);
+    const size_t o_cam = L.take(sizeof(orbg_pose_camera)), o_tin = L.take(48), o_q = L.take(32);
+    const size_t o_t = L.take(24), o_tout = L.take(48), o_out = L.take((size_t)std::max(n, 1));
+    const size_t o_ni = L.take(4);
+    uint8_t *b;
+    int rc = L.device(c, &b);
     if (rc) return rc;
-    uint8_t *b = (uint8_t *)s;
     const int32_t cnt = n;
     if (n) HIPCHK(hipMemcpyAsync(b + o_e, edges, (size_t)n * sizeof(orbg_pose_edge), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(b + o_n, &cnt, 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(b + o_cam, cam, sizeof(*cam), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(b + o_tin, tcw_in, 48, hipMemcpyHostToDevice, c->stream));
-    if ((rc = launch_pose_opt(c->stream, (const orbg_pose_edge *)(b + o_e), (const int32_t *)(b + o_n),
-                              std::max(n, 1), (const orbg_pose_camera *)(b + o_cam),
-                              (const float *)(b + o_tin), (double *)(b + o_q), (double *)(b + o_t),
-                              (float *)(b + o_tout), b + o_out, (int32_t *)(b + o_ni), 1,
+    if ((rc = launch_pose_opt(c->stream, L.at<orbg_pose_edge>(b, o_e), L.at<int32_t>(b, o_n),
+                              std::max(n, 1), L.at<orbg_pose_camera>(b, o_cam),
+                              L.at<float>(b, o_tin), L.at<double>(b, o_q), L.at<double>(b, o_t),
+                              L.at<float>(b, o_tout), b + o_out, L.at<int32_t>(b, o_ni), 1,
                               &c->prof)))
         return set_err(rc, "pose optimisation launch failed");
     int32_t ni = 0;
@@ -4419,80 +3945,6 @@ extern "C" int orbg_pose_optimization(orbg_ctx *c, const orbg_pose_edge *edges, 
 // ---------------------------------------------------------------------------
 // LocalBundleAdjustment: BlockSolver<6,3>::solve (Schur complement)
 // ---------------------------------------------------------------------------
-// Device layout of a SchurPlanHost (structure) followed by the solve's scratch, from `base`
-// (nullptr: sizes only); returns the bytes.  The structure arrays are uploaded once per plan.
-static size_t schur_layout(const SchurPlanHost &P, int nedge, uint8_t *base, SchurArgs &A,
-                           size_t *structure_bytes)
-{
-    size_t off = 0;
-    auto take = [&](size_t bytes) -> uint8_t * {
-        uint8_t *q = base ? base + off : nullptr;
-        off += al256(std::max(bytes, (size_t)1));
-        return q;
-    };
-    (void)nedge;
-    A.pidx = (const int32_t *)take(P.pidx.size() * 4);
-    A.free_pose = (const int32_t *)take(P.free_pose.size() * 4);
-    A.pt_off = (const int32_t *)take(P.pt_off.size() * 4);
-    A.pt_edges = (const int32_t *)take(P.pt_edges.size() * 4);
-    A.slot_point = (const int32_t *)take(P.slot_point.size() * 4);
-    A.slot_fidx = (const int32_t *)take(P.slot_fidx.size() * 4);
-    A.edge_pose = (const int32_t *)take(P.edge_pose.size() * 4);
-    A.blk_off = (const int32_t *)take(P.blk_off.size() * 4);
-    A.blk_pairs = (const int2 *)take(P.blk_pairs.size() * 8);
-    A.blk_i1 = (const int32_t *)take(P.blk_i1.size() * 4);
-    A.blk_i2 = (const int32_t *)take(P.blk_i2.size() * 4);
-    A.blk_seg = (const int32_t *)take(P.blk_seg.size() * 4);
-    A.blk_order = (const int32_t *)take(P.blk_order.size() * 4);
-    A.pose_off = (const int32_t *)take(P.pose_off.size() * 4);
-    A.pose_slots = (const int32_t *)take(P.pose_slots.size() * 4);
-    A.seg_lo = (const int32_t *)take(P.seg_lo.size() * 4);
-    A.seg_soff = (const int64_t *)take(P.seg_soff.size() * 8);
-    if (structure_bytes) *structure_bytes = off;
-    const size_t nslot = (size_t)std::max(P.pt_off.back(), 1);
-    A.rec = (double *)take((nslot + 256) * 24 * 8);  // k_schur_points' records (+ a workgroup's tail)
-    A.S = (double *)take((size_t)std::max<int64_t>(P.seg_soff.back(), 1) * 8);
-    A.x = (double *)take((size_t)std::max(6 * P.nfree, 1) * 8);
-    A.nslot = P.pt_off.back();
-    A.npose = P.npose;
-    A.npoint = P.npoint;
-    A.nfree = P.nfree;
-    A.nblk = P.nblk;
-    A.nseg = P.nseg;
-    A.max_seg = P.max_seg;
-    A.s_total = P.seg_soff.back();
-    return off;
-}
-
-// the structure arrays of P to their places in A (stream-ordered copies from host memory)
-static int schur_upload(const SchurPlanHost &P, const SchurArgs &A, hipStream_t st)
-{
-    auto up = [&](const void *dst, const void *src, size_t bytes) -> int {
-        if (bytes) HIPCHK(hipMemcpyAsync((void *)dst, src, bytes, hipMemcpyHostToDevice, st));
-        return ORBG_OK;
-    };
-    int rc;
-    if ((rc = up(A.pidx, P.pidx.data(), P.pidx.size() * 4)) ||
-        (rc = up(A.free_pose, P.free_pose.data(), P.free_pose.size() * 4)) ||
-        (rc = up(A.pt_off, P.pt_off.data(), P.pt_off.size() * 4)) ||
-        (rc = up(A.pt_edges, P.pt_edges.data(), P.pt_edges.size() * 4)) ||
-        (rc = up(A.slot_point, P.slot_point.data(), P.slot_point.size() * 4)) ||
-        (rc = up(A.slot_fidx, P.slot_fidx.data(), P.slot_fidx.size() * 4)) ||
-        (rc = up(A.edge_pose, P.edge_pose.data(), P.edge_pose.size() * 4)) ||
-        (rc = up(A.blk_off, P.blk_off.data(), P.blk_off.size() * 4)) ||
-        (rc = up(A.blk_pairs, P.blk_pairs.data(), P.blk_pairs.size() * 8)) ||
-        (rc = up(A.blk_i1, P.blk_i1.data(), P.blk_i1.size() * 4)) ||
-        (rc = up(A.blk_i2, P.blk_i2.data(), P.blk_i2.size() * 4)) ||
-        (rc = up(A.blk_seg, P.blk_seg.data(), P.blk_seg.size() * 4)) ||
-        (rc = up(A.blk_order, P.blk_order.data(), P.blk_order.size() * 4)) ||
-        (rc = up(A.pose_off, P.pose_off.data(), P.pose_off.size() * 4)) ||
-        (rc = up(A.pose_slots, P.pose_slots.data(), P.pose_slots.size() * 4)) ||
-        (rc = up(A.seg_lo, P.seg_lo.data(), P.seg_lo.size() * 4)) ||
-        (rc = up(A.seg_soff, P.seg_soff.data(), P.seg_soff.size() * 8)))
-        return rc;
-    return ORBG_OK;
-}
-
 extern "C" int orbg_ba_schur_solve(orbg_ctx *c, const orbg_pose *poses, int npose, int npoint,
                                    const orbg_edge *edges, int nedge, const orbg_edge_out *eout,
                                    const double *hpose, const double *bpose,
@@ -4522,21 +3974,15 @@ extern "C" int orbg_ba_schur_solve(orbg_ctx *c, const orbg_pose *poses, int npos
     build_schur_plan(npose, npoint, nedge, ep.data(), eq.data(), ea.data(), fx.data(), P);
     SchurArgs A{};
     const size_t sb = schur_layout(P, nedge, nullptr, A, nullptr);
-    size_t off = sb;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += al256(std::max(bytes, (size_t)1));
-        return o;
-    };
-    const size_t o_eout = take((size_t)nedge * sizeof(orbg_edge_out));
-    const size_t o_hp = take((size_t)npose * 36 * 8), o_bpz = take((size_t)npose * 6 * 8);
-    const size_t o_hq = take((size_t)npoint * 9 * 8), o_bq = take((size_t)npoint * 3 * 8);
-    const size_t o_ok = take(4);
-    const size_t o_dp = take((size_t)npose * 6 * 8), o_dq = take((size_t)npoint * 3 * 8);
-    void *sp;
-    int rc = scratch(c, off, &sp);
+    Layout L = Layout::starting_at(sb);  // behind the Schur structure and its scratch
+    const size_t o_eout = L.take((size_t)nedge * sizeof(orbg_edge_out));
+    const size_t o_hp = L.take((size_t)npose * 36 * 8), o_bpz = L.take((size_t)npose * 6 * 8);
+    const size_t o_hq = L.take((size_t)npoint * 9 * 8), o_bq = L.take((size_t)npoint * 3 * 8);
+    const size_t o_ok = L.take(4);
+    const size_t o_dp = L.take((size_t)npose * 6 * 8), o_dq = L.take((size_t)npoint * 3 * 8);
+    uint8_t *B;
+    int rc = L.device(c, &B);
     if (rc) return rc;
-    uint8_t *B = (uint8_t *)sp;
     schur_layout(P, nedge, B, A, nullptr);
     if ((rc = schur_upload(P, A, c->stream))) return rc;
     auto up = [&](size_t o, const void *src, size_t bytes) -> int {
@@ -4550,14 +3996,14 @@ extern "C" int orbg_ba_schur_solve(orbg_ctx *c, const orbg_pose *poses, int npos
     static_assert(sizeof(orbg_edge_out) % 8 == 0, "edge_out records are whole doubles");
     A.hpl = (const double *)(B + o_eout + offsetof(orbg_edge_out, hpl));
     A.hpl_stride = (int)(sizeof(orbg_edge_out) / 8);
-    A.hpose = (const double *)(B + o_hp);
-    A.bpose = (const double *)(B + o_bpz);
-    A.hpoint = (const double *)(B + o_hq);
-    A.bpoint = (const double *)(B + o_bq);
+    A.hpose = L.at<double>(B, o_hp);
+    A.bpose = L.at<double>(B, o_bpz);
+    A.hpoint = L.at<double>(B, o_hq);
+    A.bpoint = L.at<double>(B, o_bq);
     A.lambda = lambda;
-    A.ok = (int32_t *)(B + o_ok);
-    A.dx_pose = (double *)(B + o_dp);
-    A.dx_point = (double *)(B + o_dq);
+    A.ok = L.at<int32_t>(B, o_ok);
+    A.dx_pose = L.at<double>(B, o_dp);
+    A.dx_point = L.at<double>(B, o_dq);
     if ((rc = launch_schur(c->stream, A, &c->prof))) return set_err(rc, "schur launch failed");
     int32_t okv = 0;
     if (npose) HIPCHK(hipMemcpyAsync(dx_pose, B + o_dp, (size_t)npose * 6 * 8, hipMemcpyDeviceToHost, c->stream));
@@ -4572,13 +4018,6 @@ extern "C" int orbg_ba_schur_solve(orbg_ctx *c, const orbg_pose *poses, int npos
 // ---------------------------------------------------------------------------
 // DBoW2 vocabulary (TemplatedVocabulary::loadFromTextFile) + transform (Frame::ComputeBoW)
 // ---------------------------------------------------------------------------
-struct orbg_vocab {
-    int device = 0;
-    int k = 0, L = 0, scoring = 0, weighting = 0, nnodes = 0, nwords = 0;
-    int group = 16, root_c0 = 0, root_c1 = 0;
-    BowSlot *d_slots = nullptr;
-};
-
 extern "C" int orbg_vocab_create(orbg_ctx *c, int k, int L, int scoring, int weighting,
                                  int nnodes, const int32_t *parent, const uint8_t *is_leaf,
                                  const uint8_t *desc, const double *weight, orbg_vocab **out)
@@ -4783,39 +4222,33 @@ extern "C" int orbg_bow_transform(orbg_ctx *c, const orbg_vocab *v, const uint8_
     fv_off[0] = 0;
     if (n == 0) return ORBG_OK;
     HIPCHK(hipSetDevice(c->device));
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += al256(bytes);
-        return o;
-    };
-    const size_t o_d = take((size_t)n * 32), o_c = take(4), o_fw = take((size_t)n * 4);
-    const size_t o_fn = take((size_t)n * 4), o_fx = take((size_t)n * 8);
-    const size_t o_bw = take((size_t)n * 4), o_bx = take((size_t)n * 8), o_nb = take(4);
-    const size_t o_vn = take((size_t)n * 4), o_vo = take((size_t)(n + 1) * 4);
-    const size_t o_vf = take((size_t)n * 4), o_nf = take(4);
-    void *s;
-    int rc = scratch(c, off, &s);
+    Layout L;
+    const size_t o_d = L.take((size_t)n * 32), o_c = L.take(4), o_fw = L.take((size_t)n * 4);
+    const size_t o_fn = L.take((size_t)n * 4), o_fx = L.take((size_t)n * 8);
+    const size_t o_bw = L.take((size_t)n * 4), o_bx = L.take((size_t)n * 8), o_nb = L.take(4);
+    const size_t o_vn = L.take((size_t)n * 4), o_vo = L.take((size_t)(n + 1) * 4);
+    const size_t o_vf = L.take((size_t)n * 4), o_nf = L.take(4);
+    uint8_t *b;
+    int rc = L.device(c, &b);
     if (rc) return rc;
-    uint8_t *b = (uint8_t *)s;
     const int32_t cnt = n;
     HIPCHK(hipMemcpyAsync(b + o_d, desc, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(b + o_c, &cnt, 4, hipMemcpyHostToDevice, c->stream));
     BowArgs A = bow_args(v, levelsup);
     A.desc = b + o_d;
-    A.counts = (const int32_t *)(b + o_c);
+    A.counts = L.at<int32_t>(b, o_c);
     A.cap = n;
     A.nframes = 1;
-    A.fword = (int32_t *)(b + o_fw);
-    A.fnode = (int32_t *)(b + o_fn);
-    A.fweight = (double *)(b + o_fx);
-    A.bow_words = (int32_t *)(b + o_bw);
-    A.bow_weights = (double *)(b + o_bx);
-    A.nbow = (int32_t *)(b + o_nb);
-    A.fv_nodes = (int32_t *)(b + o_vn);
-    A.fv_off = (int32_t *)(b + o_vo);
-    A.fv_feats = (int32_t *)(b + o_vf);
-    A.nfv = (int32_t *)(b + o_nf);
+    A.fword = L.at<int32_t>(b, o_fw);
+    A.fnode = L.at<int32_t>(b, o_fn);
+    A.fweight = L.at<double>(b, o_fx);
+    A.bow_words = L.at<int32_t>(b, o_bw);
+    A.bow_weights = L.at<double>(b, o_bx);
+    A.nbow = L.at<int32_t>(b, o_nb);
+    A.fv_nodes = L.at<int32_t>(b, o_vn);
+    A.fv_off = L.at<int32_t>(b, o_vo);
+    A.fv_feats = L.at<int32_t>(b, o_vf);
+    A.nfv = L.at<int32_t>(b, o_nf);
     if ((rc = launch_bow(c->stream, A, &c->prof))) return set_err(rc, "bow launch failed");
     int32_t nb = 0, nf = 0;
     HIPCHK(hipMemcpyAsync(&nb, b + o_nb, 4, hipMemcpyDeviceToHost, c->stream));
@@ -4924,27 +4357,21 @@ static int search_by_bow_host(orbg_ctx *c, const uint8_t *kf_desc, const float *
     const int cap = std::max(n_kf, n_f);
     if (cap > 8192) return set_err(ORBG_ENOTSUP, "more than 8192 features");
     const size_t cp = (size_t)cap;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t r = o;
-        o += al256(bytes);
-        return r;
-    };
-    const size_t o_desc = take(2 * cp * 32), o_kps = take(2 * cp * sizeof(orbg_keypoint)),
-                 o_cnt = take(2 * 4), o_nodes = take(2 * cp * 4), o_off = take(2 * (cp + 1) * 4),
-                 o_feats = take(2 * cp * 4), o_nfv = take(2 * 4), o_val = take(2 * cp),
-                 o_idx = take(2 * 4), o_match = take(cp * 4), o_nm = take(4);
-    uint8_t *hs;
-    int rc = stage(c, o, &hs);
+    Layout L;
+    const size_t o_desc = L.take(2 * cp * 32), o_kps = L.take(2 * cp * sizeof(orbg_keypoint)),
+                 o_cnt = L.take(2 * 4), o_nodes = L.take(2 * cp * 4), o_off = L.take(2 * (cp + 1) * 4),
+                 o_feats = L.take(2 * cp * 4), o_nfv = L.take(2 * 4), o_val = L.take(2 * cp),
+                 o_idx = L.take(2 * 4), o_match = L.take(cp * 4), o_nm = L.take(4);
+    uint8_t *hs, *db;
+    int rc = L.host(c, &hs);
     if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    memset(hs, 0, o);
+    memset(hs, 0, L.total());
     memcpy(hs + o_desc, kf_desc, (size_t)n_kf * 32);
     memcpy(hs + o_desc + cp * 32, f_desc, (size_t)n_f * 32);
-    orbg_keypoint *hk = (orbg_keypoint *)(hs + o_kps);
+    orbg_keypoint *hk = L.at<orbg_keypoint>(hs, o_kps);
     for (int i = 0; i < n_kf; i++) hk[i].angle = kf_angle[i];
     for (int i = 0; i < n_f; i++) hk[cp + i].angle = f_angle[i];
-    int32_t *hc = (int32_t *)(hs + o_cnt);
+    int32_t *hc = L.at<int32_t>(hs, o_cnt);
     hc[0] = n_kf;
     hc[1] = n_f;
     memcpy(hs + o_nodes, kf_fv_nodes, (size_t)kf_nfv * 4);
@@ -4953,7 +4380,7 @@ static int search_by_bow_host(orbg_ctx *c, const uint8_t *kf_desc, const float *
     memcpy(hs + o_off + (cp + 1) * 4, f_fv_off, (size_t)(f_nfv + 1) * 4);
     memcpy(hs + o_feats, kf_fv_feats, (size_t)kf_fv_off[kf_nfv] * 4);
     memcpy(hs + o_feats + cp * 4, f_fv_feats, (size_t)f_fv_off[f_nfv] * 4);
-    int32_t *hn = (int32_t *)(hs + o_nfv);
+    int32_t *hn = L.at<int32_t>(hs, o_nfv);
     hn[0] = kf_nfv;
     hn[1] = f_nfv;
     if (kf_valid)
@@ -4964,25 +4391,23 @@ static int search_by_bow_host(orbg_ctx *c, const uint8_t *kf_desc, const float *
         memcpy(hs + o_val + cp, f_valid, (size_t)n_f);
     else
         memset(hs + o_val + cp, 1, (size_t)n_f);
-    int32_t *hi = (int32_t *)(hs + o_idx);
+    int32_t *hi = L.at<int32_t>(hs, o_idx);
     hi[0] = 0;
     hi[1] = 1;
-    void *d;
-    if ((rc = scratch(c, o, &d))) return rc;
-    uint8_t *db = (uint8_t *)d;
-    HIPCHK(hipMemcpyAsync(db, hs, o, hipMemcpyHostToDevice, c->stream));
+    if ((rc = L.device(c, &db))) return rc;
+    HIPCHK(hipMemcpyAsync(db, hs, L.total(), hipMemcpyHostToDevice, c->stream));
     orbg_bow_frames K{}, F{};
     K.desc = F.desc = db + o_desc;
-    K.kps = F.kps = (const orbg_keypoint *)(db + o_kps);
-    K.counts = F.counts = (const int32_t *)(db + o_cnt);
-    K.fv_nodes = F.fv_nodes = (const int32_t *)(db + o_nodes);
-    K.fv_off = F.fv_off = (const int32_t *)(db + o_off);
-    K.fv_feats = F.fv_feats = (const int32_t *)(db + o_feats);
-    K.nfv = F.nfv = (const int32_t *)(db + o_nfv);
+    K.kps = F.kps = L.at<orbg_keypoint>(db, o_kps);
+    K.counts = F.counts = L.at<int32_t>(db, o_cnt);
+    K.fv_nodes = F.fv_nodes = L.at<int32_t>(db, o_nodes);
+    K.fv_off = F.fv_off = L.at<int32_t>(db, o_off);
+    K.fv_feats = F.fv_feats = L.at<int32_t>(db, o_feats);
+    K.nfv = F.nfv = L.at<int32_t>(db, o_nfv);
     K.valid = F.valid = db + o_val;  // frame 0 (KF / pKF1) and frame 1 (F / pKF2) at + cap
-    const int32_t *di = (const int32_t *)(db + o_idx);
+    const int32_t *di = L.at<int32_t>(db, o_idx);
     rc = launch_bow_match(c->stream, K, F, cap, di, di + 1, 1, nnratio, check_ori,
-                          (int32_t *)(db + o_match), (int32_t *)(db + o_nm), kfkf);
+                          L.at<int32_t>(db, o_match), L.at<int32_t>(db, o_nm), kfkf);
     if (rc == ORBG_ENOTSUP) return set_err(ORBG_ENOTSUP, "SearchByBoW: more than 4096 features per frame");
     if (rc) return set_err(ORBG_EIO, "k_bow_match launch failed");
     HIPCHK(hipMemcpyAsync(hs + o_match, db + o_match, cp * 4 + 256, hipMemcpyDeviceToHost, c->stream));
@@ -5133,17 +4558,14 @@ extern "C" int orbg_rgbd_stereo(orbg_ctx *c, const void *depth, int depth_type, 
     if (pitch < (size_t)w * px) return set_err(ORBG_EINVAL, "pitch below the row width");
     HIPCHK(hipSetDevice(c->device));
     // only the keypoints' pixels are read: upload the image rows once (w x h), packed
-    const size_t ib = al256((size_t)w * px * h), kb = al256((size_t)n * sizeof(orbg_keypoint));
-    const size_t ob = al256((size_t)n * 4);
-    const size_t o_img = 0, o_k = ib, o_ku = ib + kb, o_cnt = ib + 2 * kb, o_ur = o_cnt + 256,
-                 o_d = o_ur + ob, tot = o_d + ob;
-    uint8_t *hs;
-    int rc = stage(c, tot, &hs);
+    Layout L;
+    const size_t o_img = L.take((size_t)w * px * h), o_k = L.take((size_t)n * sizeof(orbg_keypoint)),
+                 o_ku = L.take((size_t)n * sizeof(orbg_keypoint)), o_cnt = L.take(4),
+                 o_ur = L.take((size_t)n * 4), o_d = L.take((size_t)n * 4);
+    uint8_t *hs, *db;
+    int rc = L.host(c, &hs);
     if (rc) return rc;
-    void *dv;
-    if ((rc = scratch(c, tot, &dv))) return rc;
-    uint8_t *db = (uint8_t *)dv;
-    HIPCHK(hipStreamSynchronize(c->stream));
+    if ((rc = L.device(c, &db))) return rc;
     for (int y = 0; y < h; y++)
         memcpy(hs + o_img + (size_t)y * w * px, (const uint8_t *)depth + (size_t)y * pitch, (size_t)w * px);
     memcpy(hs + o_k, kps, (size_t)n * sizeof(orbg_keypoint));
@@ -5152,11 +4574,11 @@ extern "C" int orbg_rgbd_stereo(orbg_ctx *c, const void *depth, int depth_type, 
     memcpy(hs + o_cnt, &cnt, 4);
     HIPCHK(hipMemcpyAsync(db, hs, o_ur, hipMemcpyHostToDevice, c->stream));
     rc = launch_rgbd(c->stream, db + o_img, depth_type == ORBG_DEPTH_U16, factor, w, h,
-                     (size_t)w * px, 0, (const orbg_keypoint *)(db + o_k),
-                     (const orbg_keypoint *)(db + o_ku), (const int32_t *)(db + o_cnt), n, 1, mbf,
-                     (float *)(db + o_ur), (float *)(db + o_d));
+                     (size_t)w * px, 0, L.at<orbg_keypoint>(db, o_k),
+                     L.at<orbg_keypoint>(db, o_ku), L.at<int32_t>(db, o_cnt), n, 1, mbf,
+                     L.at<float>(db, o_ur), L.at<float>(db, o_d));
     if (rc) return set_err(ORBG_EIO, "k_rgbd launch failed");
-    HIPCHK(hipMemcpyAsync(hs + o_ur, db + o_ur, tot - o_ur, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(hs + o_ur, db + o_ur, L.total() - o_ur, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     memcpy(uright, hs + o_ur, (size_t)n * 4);
     memcpy(depth_out, hs + o_d, (size_t)n * 4);
@@ -5172,25 +4594,24 @@ extern "C" int orbg_undistort_keypoints(orbg_ctx *c, const orbg_camera *cam,
     if (!kps || !kps_un) return set_err(ORBG_EINVAL, "NULL array");
     if (cam->k1 != 0.0f && !cam_ok(cam)) return set_err(ORBG_EINVAL, "fx / fy must be finite and nonzero");
     HIPCHK(hipSetDevice(c->device));
-    const size_t kb = al256((size_t)n * sizeof(orbg_keypoint));
-    uint8_t *hs;
-    int rc = stage(c, 2 * kb, &hs);
+    Layout L;
+    const size_t o_k = L.take((size_t)n * sizeof(orbg_keypoint)), o_cnt = L.take(4),
+                 o_un = L.take((size_t)n * sizeof(orbg_keypoint));
+    uint8_t *hs, *db;
+    int rc = L.host(c, &hs);
     if (rc) return rc;
-    void *d;
-    if ((rc = scratch(c, 2 * kb + 256, &d))) return rc;
-    uint8_t *db = (uint8_t *)d;
-    HIPCHK(hipStreamSynchronize(c->stream));  // the staging buffer may still feed a copy
-    memcpy(hs, kps, (size_t)n * sizeof(orbg_keypoint));
+    if ((rc = L.device(c, &db))) return rc;
+    memcpy(hs + o_k, kps, (size_t)n * sizeof(orbg_keypoint));
     const int32_t cnt = n;
-    memcpy(hs + kb, &cnt, 4);
-    HIPCHK(hipMemcpyAsync(db, hs, kb + 4, hipMemcpyHostToDevice, c->stream));
-    rc = launch_undistort(c->stream, *cam, (const orbg_keypoint *)db, (const int32_t *)(db + kb),
-                          n, 1, (orbg_keypoint *)(db + kb + 256));
+    memcpy(hs + o_cnt, &cnt, 4);
+    HIPCHK(hipMemcpyAsync(db, hs, o_cnt + 4, hipMemcpyHostToDevice, c->stream));
+    rc = launch_undistort(c->stream, *cam, L.at<orbg_keypoint>(db, o_k), L.at<int32_t>(db, o_cnt),
+                          n, 1, L.at<orbg_keypoint>(db, o_un));
     if (rc) return set_err(ORBG_EIO, "k_undistort launch failed");
-    HIPCHK(hipMemcpyAsync(hs, db + kb + 256, (size_t)n * sizeof(orbg_keypoint),
+    HIPCHK(hipMemcpyAsync(hs + o_un, db + o_un, (size_t)n * sizeof(orbg_keypoint),
                           hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    memcpy(kps_un, hs, (size_t)n * sizeof(orbg_keypoint));
+    memcpy(kps_un, hs + o_un, (size_t)n * sizeof(orbg_keypoint));
     return ORBG_OK;
 }
 
@@ -5225,22 +4646,14 @@ extern "C" int orbg_is_in_frustum(orbg_ctx *c, const orbg_frustum_camera *cam,
     if (n == 0) return ORBG_OK;
     if (!mps || !proj) return set_err(ORBG_EINVAL, "NULL array");
     HIPCHK(hipSetDevice(c->device));
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t r = o;
-        o += al256(bytes);
-        return r;
-    };
-    const size_t o_cam = take(sizeof(orbg_frustum_camera)), o_cnt = take(4),
-                 o_mp = take((size_t)n * sizeof(orbg_map_point)),
-                 o_pr = take((size_t)n * sizeof(orbg_map_projection)), o_nv = take(4);
-    uint8_t *hs;
-    int rc = stage(c, o, &hs);
+    Layout L;
+    const size_t o_cam = L.take(sizeof(orbg_frustum_camera)), o_cnt = L.take(4),
+                 o_mp = L.take((size_t)n * sizeof(orbg_map_point)),
+                 o_pr = L.take((size_t)n * sizeof(orbg_map_projection)), o_nv = L.take(4);
+    uint8_t *hs, *db;
+    int rc = L.host(c, &hs);
     if (rc) return rc;
-    void *d;
-    if ((rc = scratch(c, o, &d))) return rc;
-    uint8_t *db = (uint8_t *)d;
-    HIPCHK(hipStreamSynchronize(c->stream));
+    if ((rc = L.device(c, &db))) return rc;
     memcpy(hs + o_cam, cam, sizeof(orbg_frustum_camera));
     const int32_t cnt = n;
     memcpy(hs + o_cnt, &cnt, 4);
@@ -5248,12 +4661,12 @@ extern "C" int orbg_is_in_frustum(orbg_ctx *c, const orbg_frustum_camera *cam,
     // the projections a point not in view keeps (only its flags are written)
     memcpy(hs + o_pr, proj, (size_t)n * sizeof(orbg_map_projection));
     HIPCHK(hipMemcpyAsync(db, hs, o_nv, hipMemcpyHostToDevice, c->stream));
-    rc = launch_frustum(c->stream, (const orbg_frustum_camera *)(db + o_cam),
-                        (const orbg_map_point *)(db + o_mp), (const int32_t *)(db + o_cnt), n, 1,
-                        viewing_cos_limit, (orbg_map_projection *)(db + o_pr),
-                        (int32_t *)(db + o_nv));
+    rc = launch_frustum(c->stream, L.at<orbg_frustum_camera>(db, o_cam),
+                        L.at<orbg_map_point>(db, o_mp), L.at<int32_t>(db, o_cnt), n, 1,
+                        viewing_cos_limit, L.at<orbg_map_projection>(db, o_pr),
+                        L.at<int32_t>(db, o_nv));
     if (rc) return set_err(ORBG_EIO, "k_frustum launch failed");
-    HIPCHK(hipMemcpyAsync(hs + o_pr, db + o_pr, o - o_pr, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(hs + o_pr, db + o_pr, L.total() - o_pr, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     memcpy(proj, hs + o_pr, (size_t)n * sizeof(orbg_map_projection));
     memcpy(nvisible, hs + o_nv, 4);
@@ -5286,30 +4699,22 @@ extern "C" int orbg_distinctive_descriptor(orbg_ctx *c, const uint8_t *desc, int
     if (n == 0) return ORBG_OK;  // observations empty: the reference returns (MapPoint.cc:356)
     if (!desc) return set_err(ORBG_EINVAL, "NULL array");
     HIPCHK(hipSetDevice(c->device));
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t r = o;
-        o += al256(bytes);
-        return r;
-    };
-    const size_t o_d = take((size_t)n * 32), o_r = take((size_t)n * 4), o_off = take(8),
-                 o_b = take(4);
-    uint8_t *hs;
-    int rc = stage(c, o, &hs);
+    Layout L;
+    const size_t o_d = L.take((size_t)n * 32), o_r = L.take((size_t)n * 4), o_off = L.take(8),
+                 o_b = L.take(4);
+    uint8_t *hs, *db;
+    int rc = L.host(c, &hs);
     if (rc) return rc;
-    void *d;
-    if ((rc = scratch(c, o, &d))) return rc;
-    uint8_t *db = (uint8_t *)d;
-    HIPCHK(hipStreamSynchronize(c->stream));
+    if ((rc = L.device(c, &db))) return rc;
     memcpy(hs + o_d, desc, (size_t)n * 32);
-    int32_t *hr = (int32_t *)(hs + o_r);
+    int32_t *hr = L.at<int32_t>(hs, o_r);
     for (int i = 0; i < n; i++) hr[i] = i;
-    int32_t *ho = (int32_t *)(hs + o_off);
+    int32_t *ho = L.at<int32_t>(hs, o_off);
     ho[0] = 0;
     ho[1] = n;
     HIPCHK(hipMemcpyAsync(db, hs, o_b, hipMemcpyHostToDevice, c->stream));
-    rc = launch_distinctive(c->stream, db + o_d, (const int32_t *)(db + o_r),
-                            (const int32_t *)(db + o_off), 1, (int32_t *)(db + o_b), nullptr);
+    rc = launch_distinctive(c->stream, db + o_d, L.at<int32_t>(db, o_r),
+                            L.at<int32_t>(db, o_off), 1, L.at<int32_t>(db, o_b), nullptr);
     if (rc) return set_err(ORBG_EIO, "k_distinctive launch failed");
     HIPCHK(hipMemcpyAsync(hs + o_b, db + o_b, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -5371,58 +4776,51 @@ extern "C" int orbg_search_for_triangulation(orbg_ctx *c, const orbg_keyframe *k
     const int cap = std::max(kf1->n, kf2->n);
     if (cap > 65535) return set_err(ORBG_ENOTSUP, "more than 65535 features");
     const size_t cp = (size_t)cap;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t r = o;
-        o += al256(bytes);
-        return r;
-    };
-    const size_t o_desc = take(2 * cp * 32), o_kps = take(2 * cp * sizeof(orbg_keypoint)),
-                 o_ur = take(2 * cp * 4), o_mp = take(2 * cp), o_cnt = take(8),
-                 o_nodes = take(2 * cp * 4), o_off = take(2 * (cp + 1) * 4),
-                 o_feats = take(2 * cp * 4), o_nfv = take(8), o_idx = take(8),
-                 o_geo = take(sizeof(orbg_triangulation_pair)), o_m = take(cp * 4), o_nm = take(4);
-    uint8_t *hs;
-    int rc = stage(c, o, &hs);
+    Layout L;
+    const size_t o_desc = L.take(2 * cp * 32), o_kps = L.take(2 * cp * sizeof(orbg_keypoint)),
+                 o_ur = L.take(2 * cp * 4), o_mp = L.take(2 * cp), o_cnt = L.take(8),
+                 o_nodes = L.take(2 * cp * 4), o_off = L.take(2 * (cp + 1) * 4),
+                 o_feats = L.take(2 * cp * 4), o_nfv = L.take(8), o_idx = L.take(8),
+                 o_geo = L.take(sizeof(orbg_triangulation_pair)), o_m = L.take(cp * 4),
+                 o_nm = L.take(4);
+    uint8_t *hs, *db;
+    int rc = L.host(c, &hs);
     if (rc) return rc;
-    void *d;
-    if ((rc = scratch(c, o, &d))) return rc;
-    uint8_t *db = (uint8_t *)d;
-    HIPCHK(hipStreamSynchronize(c->stream));
+    if ((rc = L.device(c, &db))) return rc;
     memset(hs, 0, o_m);
     const orbg_keyframe *ks[2] = {kf1, kf2};
     for (int s = 0; s < 2; s++) {
         const orbg_keyframe *k = ks[s];
         memcpy(hs + o_desc + s * cp * 32, k->desc, (size_t)k->n * 32);
         memcpy(hs + o_kps + s * cp * sizeof(orbg_keypoint), k->kps, (size_t)k->n * sizeof(orbg_keypoint));
-        float *ur = (float *)(hs + o_ur) + s * cp;
+        float *ur = L.at<float>(hs, o_ur) + s * cp;
         for (int i = 0; i < k->n; i++) ur[i] = k->uright ? k->uright[i] : -1.0f;
         if (k->has_mp) memcpy(hs + o_mp + s * cp, k->has_mp, (size_t)k->n);
-        ((int32_t *)(hs + o_cnt))[s] = k->n;
+        L.at<int32_t>(hs, o_cnt)[s] = k->n;
         memcpy(hs + o_nodes + s * cp * 4, k->fv_nodes, (size_t)k->nfv * 4);
         memcpy(hs + o_off + s * (cp + 1) * 4, k->fv_off, (size_t)(k->nfv + 1) * 4);
         memcpy(hs + o_feats + s * cp * 4, k->fv_feats, (size_t)k->fv_off[k->nfv] * 4);
-        ((int32_t *)(hs + o_nfv))[s] = k->nfv;
-        ((int32_t *)(hs + o_idx))[s] = s;
+        L.at<int32_t>(hs, o_nfv)[s] = k->nfv;
+        L.at<int32_t>(hs, o_idx)[s] = s;
     }
     memcpy(hs + o_geo, geo, sizeof(orbg_triangulation_pair));
     HIPCHK(hipMemcpyAsync(db, hs, o_m, hipMemcpyHostToDevice, c->stream));
     orbg_keyframes K{};
     K.desc = db + o_desc;
-    K.kps = (const orbg_keypoint *)(db + o_kps);
-    K.uright = (const float *)(db + o_ur);
+    K.kps = L.at<orbg_keypoint>(db, o_kps);
+    K.uright = L.at<float>(db, o_ur);
     K.has_mp = db + o_mp;
-    K.counts = (const int32_t *)(db + o_cnt);
-    K.fv_nodes = (const int32_t *)(db + o_nodes);
-    K.fv_off = (const int32_t *)(db + o_off);
-    K.fv_feats = (const int32_t *)(db + o_feats);
-    K.nfv = (const int32_t *)(db + o_nfv);
-    const int32_t *di = (const int32_t *)(db + o_idx);
-    rc = launch_tri_match(c->stream, K, cap, di, di + 1, (const orbg_triangulation_pair *)(db + o_geo),
+    K.counts = L.at<int32_t>(db, o_cnt);
+    K.fv_nodes = L.at<int32_t>(db, o_nodes);
+    K.fv_off = L.at<int32_t>(db, o_off);
+    K.fv_feats = L.at<int32_t>(db, o_feats);
+    K.nfv = L.at<int32_t>(db, o_nfv);
+    const int32_t *di = L.at<int32_t>(db, o_idx);
+    rc = launch_tri_match(c->stream, K, cap, di, di + 1, L.at<orbg_triangulation_pair>(db, o_geo),
                           1, c->scale, c->sigma2, c->p.nlevels, only_stereo, check_ori,
-                          (int32_t *)(db + o_m), (int32_t *)(db + o_nm));
+                          L.at<int32_t>(db, o_m), L.at<int32_t>(db, o_nm));
     if (rc) return set_err(ORBG_EIO, "k_tri_match launch failed");
-    HIPCHK(hipMemcpyAsync(hs + o_m, db + o_m, o - o_m, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(hs + o_m, db + o_m, L.total() - o_m, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     memcpy(matches12, hs + o_m, (size_t)kf1->n * 4);
     memcpy(nmatches, hs + o_nm, 4);
@@ -5451,23 +4849,21 @@ extern "C" int orbg_triangulation_geometry(orbg_ctx *c, const orbg_kf_camera *ca
 {
     if (!c || !cam1 || !cam2 || !geo) return set_err(ORBG_EINVAL, "NULL argument");
     HIPCHK(hipSetDevice(c->device));
-    const size_t o_cam = 0, o_idx = al256(2 * sizeof(orbg_kf_camera)), o_geo = o_idx + 256,
-                 o = o_geo + al256(sizeof(orbg_triangulation_pair));
-    uint8_t *hs;
-    int rc = stage(c, o, &hs);
+    Layout L;
+    const size_t o_cam = L.take(2 * sizeof(orbg_kf_camera)), o_idx = L.take(8),
+                 o_geo = L.take(sizeof(orbg_triangulation_pair));
+    uint8_t *hs, *db;
+    int rc = L.host(c, &hs);
     if (rc) return rc;
-    void *d;
-    if ((rc = scratch(c, o, &d))) return rc;
-    uint8_t *db = (uint8_t *)d;
-    HIPCHK(hipStreamSynchronize(c->stream));
+    if ((rc = L.device(c, &db))) return rc;
     memcpy(hs + o_cam, cam1, sizeof(orbg_kf_camera));
     memcpy(hs + o_cam + sizeof(orbg_kf_camera), cam2, sizeof(orbg_kf_camera));
-    ((int32_t *)(hs + o_idx))[0] = 0;
-    ((int32_t *)(hs + o_idx))[1] = 1;
+    L.at<int32_t>(hs, o_idx)[0] = 0;
+    L.at<int32_t>(hs, o_idx)[1] = 1;
     HIPCHK(hipMemcpyAsync(db, hs, o_geo, hipMemcpyHostToDevice, c->stream));
-    const int32_t *di = (const int32_t *)(db + o_idx);
-    rc = launch_tri_geometry(c->stream, (const orbg_kf_camera *)(db + o_cam), di, di + 1, 1,
-                             (orbg_triangulation_pair *)(db + o_geo));
+    const int32_t *di = L.at<int32_t>(db, o_idx);
+    rc = launch_tri_geometry(c->stream, L.at<orbg_kf_camera>(db, o_cam), di, di + 1, 1,
+                             L.at<orbg_triangulation_pair>(db, o_geo));
     if (rc) return set_err(ORBG_EIO, "k_tri_geometry launch failed");
     HIPCHK(hipMemcpyAsync(hs + o_geo, db + o_geo, sizeof(orbg_triangulation_pair),
                           hipMemcpyDeviceToHost, c->stream));
@@ -5519,24 +4915,16 @@ extern "C" int orbg_triangulate(orbg_ctx *c, const orbg_keyframe_geo *kf1,
     HIPCHK(hipSetDevice(c->device));
     const int cap = std::max(kf1->n, kf2->n);
     const size_t cp = (size_t)cap;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t r = o;
-        o += al256(bytes);
-        return r;
-    };
-    const size_t o_kps = take(2 * cp * sizeof(orbg_keypoint)),
-                 o_raw = take(2 * cp * sizeof(orbg_keypoint)), o_ur = take(2 * cp * 4),
-                 o_dp = take(2 * cp * 4), o_cnt = take(8), o_idx = take(8),
-                 o_cam = take(2 * sizeof(orbg_kf_camera)), o_m = take(cp * 4),
-                 o_x = take(cp * 12), o_st = take(cp), o_nn = take(4);
-    uint8_t *hs;
-    int rc = stage(c, o, &hs);
+    Layout L;
+    const size_t o_kps = L.take(2 * cp * sizeof(orbg_keypoint)),
+                 o_raw = L.take(2 * cp * sizeof(orbg_keypoint)), o_ur = L.take(2 * cp * 4),
+                 o_dp = L.take(2 * cp * 4), o_cnt = L.take(8), o_idx = L.take(8),
+                 o_cam = L.take(2 * sizeof(orbg_kf_camera)), o_m = L.take(cp * 4),
+                 o_x = L.take(cp * 12), o_st = L.take(cp), o_nn = L.take(4);
+    uint8_t *hs, *db;
+    int rc = L.host(c, &hs);
     if (rc) return rc;
-    void *d;
-    if ((rc = scratch(c, o, &d))) return rc;
-    uint8_t *db = (uint8_t *)d;
-    HIPCHK(hipStreamSynchronize(c->stream));
+    if ((rc = L.device(c, &db))) return rc;
     memset(hs, 0, o_x);
     for (int s = 0; s < 2; s++) {
         const orbg_keyframe_geo *k = ks[s];
@@ -5544,31 +4932,31 @@ extern "C" int orbg_triangulate(orbg_ctx *c, const orbg_keyframe_geo *kf1,
         memcpy(hs + o_kps + s * cp * sizeof(orbg_keypoint), k->kps, n * sizeof(orbg_keypoint));
         memcpy(hs + o_raw + s * cp * sizeof(orbg_keypoint), k->kps_raw ? k->kps_raw : k->kps,
                n * sizeof(orbg_keypoint));
-        float *ur = (float *)(hs + o_ur) + s * cp, *dp = (float *)(hs + o_dp) + s * cp;
+        float *ur = L.at<float>(hs, o_ur) + s * cp, *dp = L.at<float>(hs, o_dp) + s * cp;
         for (size_t i = 0; i < n; i++) {
             ur[i] = k->uright ? k->uright[i] : -1.0f;
             dp[i] = k->uright ? k->depth[i] : 0.0f;
         }
-        ((int32_t *)(hs + o_cnt))[s] = k->n;
-        ((int32_t *)(hs + o_idx))[s] = s;
+        L.at<int32_t>(hs, o_cnt)[s] = k->n;
+        L.at<int32_t>(hs, o_idx)[s] = s;
     }
     memcpy(hs + o_cam, cam1, sizeof(orbg_kf_camera));
     memcpy(hs + o_cam + sizeof(orbg_kf_camera), cam2, sizeof(orbg_kf_camera));
     memcpy(hs + o_m, matches12, (size_t)kf1->n * 4);
-    for (int i = kf1->n; i < cap; i++) ((int32_t *)(hs + o_m))[i] = -1;
+    for (int i = kf1->n; i < cap; i++) L.at<int32_t>(hs, o_m)[i] = -1;
     HIPCHK(hipMemcpyAsync(db, hs, o_x, hipMemcpyHostToDevice, c->stream));
     orbg_keyframes K{};
-    K.kps = (const orbg_keypoint *)(db + o_kps);
-    K.uright = (const float *)(db + o_ur);
-    K.counts = (const int32_t *)(db + o_cnt);
-    const int32_t *di = (const int32_t *)(db + o_idx);
-    rc = launch_triangulate(c->stream, K, (const orbg_keypoint *)(db + o_raw),
-                            (const float *)(db + o_dp), cap, (const orbg_kf_camera *)(db + o_cam),
-                            di, di + 1, (const int32_t *)(db + o_m), 1, c->scale, c->sigma2,
-                            c->p.nlevels, c->p.scale_factor, (float *)(db + o_x),
-                            (int8_t *)(db + o_st), (int32_t *)(db + o_nn));
+    K.kps = L.at<orbg_keypoint>(db, o_kps);
+    K.uright = L.at<float>(db, o_ur);
+    K.counts = L.at<int32_t>(db, o_cnt);
+    const int32_t *di = L.at<int32_t>(db, o_idx);
+    rc = launch_triangulate(c->stream, K, L.at<orbg_keypoint>(db, o_raw),
+                            L.at<float>(db, o_dp), cap, L.at<orbg_kf_camera>(db, o_cam),
+                            di, di + 1, L.at<int32_t>(db, o_m), 1, c->scale, c->sigma2,
+                            c->p.nlevels, c->p.scale_factor, L.at<float>(db, o_x),
+                            L.at<int8_t>(db, o_st), L.at<int32_t>(db, o_nn));
     if (rc) return set_err(ORBG_EIO, "k_triangulate launch failed");
-    HIPCHK(hipMemcpyAsync(hs + o_x, db + o_x, o - o_x, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(hs + o_x, db + o_x, L.total() - o_x, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     memcpy(x3d, hs + o_x, (size_t)kf1->n * 12);
     memcpy(status, hs + o_st, (size_t)kf1->n);
@@ -5644,47 +5032,39 @@ static int fuse_host(orbg_ctx *c, const orbg_keyframe *kf, const orbg_frustum_ca
     const int cap = std::max(kf->n, 1);
     if (cap > 8192) return set_err(ORBG_ENOTSUP, "more than 8192 keypoints");
     const size_t cp = (size_t)cap, nm = (size_t)nmp;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t r = o;
-        o += al256(bytes);
-        return r;
-    };
-    const size_t o_desc = take(cp * 32), o_kps = take(cp * sizeof(orbg_keypoint)),
-                 o_ur = take(cp * 4), o_cnt = take(4), o_idx = take(4),
-                 o_cam = take(sizeof(orbg_frustum_camera)), o_mp = take(nm * sizeof(orbg_map_point)),
-                 o_md = take(nm * 32), o_mc = take(4), o_bi = take(nm * 4), o_bd = take(nm * 4),
-                 o_nf = take(4);
-    uint8_t *hs;
-    int rc = stage(c, o, &hs);
+    Layout L;
+    const size_t o_desc = L.take(cp * 32), o_kps = L.take(cp * sizeof(orbg_keypoint)),
+                 o_ur = L.take(cp * 4), o_cnt = L.take(4), o_idx = L.take(4),
+                 o_cam = L.take(sizeof(orbg_frustum_camera)), o_mp = L.take(nm * sizeof(orbg_map_point)),
+                 o_md = L.take(nm * 32), o_mc = L.take(4), o_bi = L.take(nm * 4), o_bd = L.take(nm * 4),
+                 o_nf = L.take(4);
+    uint8_t *hs, *db;
+    int rc = L.host(c, &hs);
     if (rc) return rc;
-    void *d;
-    if ((rc = scratch(c, o, &d))) return rc;
-    uint8_t *db = (uint8_t *)d;
-    HIPCHK(hipStreamSynchronize(c->stream));
+    if ((rc = L.device(c, &db))) return rc;
     memcpy(hs + o_desc, kf->desc, (size_t)kf->n * 32);
     memcpy(hs + o_kps, kf->kps, (size_t)kf->n * sizeof(orbg_keypoint));
-    float *ur = (float *)(hs + o_ur);
+    float *ur = L.at<float>(hs, o_ur);
     for (int i = 0; i < kf->n; i++) ur[i] = kf->uright ? kf->uright[i] : -1.0f;
-    ((int32_t *)(hs + o_cnt))[0] = kf->n;
-    ((int32_t *)(hs + o_idx))[0] = 0;
+    L.at<int32_t>(hs, o_cnt)[0] = kf->n;
+    L.at<int32_t>(hs, o_idx)[0] = 0;
     memcpy(hs + o_cam, cam, sizeof(orbg_frustum_camera));
     memcpy(hs + o_mp, mps, nm * sizeof(orbg_map_point));
     memcpy(hs + o_md, mdesc, nm * 32);
-    ((int32_t *)(hs + o_mc))[0] = nmp;
+    L.at<int32_t>(hs, o_mc)[0] = nmp;
     HIPCHK(hipMemcpyAsync(db, hs, o_bi, hipMemcpyHostToDevice, c->stream));
     orbg_keyframes K{};
     K.desc = db + o_desc;
-    K.kps = (const orbg_keypoint *)(db + o_kps);
-    K.uright = (const float *)(db + o_ur);
-    K.counts = (const int32_t *)(db + o_cnt);
-    rc = launch_fuse(c->stream, K, cap, (const int32_t *)(db + o_idx),
-                     (const orbg_frustum_camera *)(db + o_cam), (const orbg_map_point *)(db + o_mp),
-                     db + o_md, (const int32_t *)(db + o_mc), nmp, 1, th, c->scale, c->inv_sigma2,
-                     c->p.nlevels, sim3, (int32_t *)(db + o_bi), (int32_t *)(db + o_bd),
-                     (int32_t *)(db + o_nf), c->d_err);
+    K.kps = L.at<orbg_keypoint>(db, o_kps);
+    K.uright = L.at<float>(db, o_ur);
+    K.counts = L.at<int32_t>(db, o_cnt);
+    rc = launch_fuse(c->stream, K, cap, L.at<int32_t>(db, o_idx),
+                     L.at<orbg_frustum_camera>(db, o_cam), L.at<orbg_map_point>(db, o_mp),
+                     db + o_md, L.at<int32_t>(db, o_mc), nmp, 1, th, c->scale, c->inv_sigma2,
+                     c->p.nlevels, sim3, L.at<int32_t>(db, o_bi), L.at<int32_t>(db, o_bd),
+                     L.at<int32_t>(db, o_nf), c->d_err);
     if (rc) return set_err(ORBG_EIO, "k_fuse launch failed");
-    HIPCHK(hipMemcpyAsync(hs + o_bi, db + o_bi, o - o_bi, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(hs + o_bi, db + o_bi, L.total() - o_bi, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     memcpy(best_idx, hs + o_bi, nm * 4);
     memcpy(best_dist, hs + o_bd, nm * 4);
@@ -5765,23 +5145,15 @@ extern "C" int orbg_search_by_sim3(orbg_ctx *c, const orbg_keyframe *kf1, const 
     const int cap = std::max(kf1->n, kf2->n);
     if (cap > 8192) return set_err(ORBG_ENOTSUP, "more than 8192 keypoints");
     const size_t cp = (size_t)cap;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t r = o;
-        o += al256(bytes);
-        return r;
-    };
-    const size_t o_desc = take(2 * cp * 32), o_kps = take(2 * cp * sizeof(orbg_keypoint)),
-                 o_cnt = take(8), o_idx = take(8), o_pair = take(sizeof(orbg_sim3_pair)),
-                 o_mp = take(2 * cp * sizeof(orbg_map_point)), o_md = take(2 * cp * 32),
-                 o_am1 = take(cp), o_am2 = take(cp), o_m = take(cp * 4), o_nf = take(4);
-    uint8_t *hs;
-    int rc = stage(c, o, &hs);
+    Layout L;
+    const size_t o_desc = L.take(2 * cp * 32), o_kps = L.take(2 * cp * sizeof(orbg_keypoint)),
+                 o_cnt = L.take(8), o_idx = L.take(8), o_pair = L.take(sizeof(orbg_sim3_pair)),
+                 o_mp = L.take(2 * cp * sizeof(orbg_map_point)), o_md = L.take(2 * cp * 32),
+                 o_am1 = L.take(cp), o_am2 = L.take(cp), o_m = L.take(cp * 4), o_nf = L.take(4);
+    uint8_t *hs, *db;
+    int rc = L.host(c, &hs);
     if (rc) return rc;
-    void *d;
-    if ((rc = scratch(c, o, &d))) return rc;
-    uint8_t *db = (uint8_t *)d;
-    HIPCHK(hipStreamSynchronize(c->stream));
+    if ((rc = L.device(c, &db))) return rc;
     memset(hs, 0, o_m);
     const orbg_map_point *mpp[2] = {mp1, mp2};
     const uint8_t *mdp[2] = {md1, md2}, *amp[2] = {matched1, matched2};
@@ -5789,8 +5161,8 @@ extern "C" int orbg_search_by_sim3(orbg_ctx *c, const orbg_keyframe *kf1, const 
         const size_t n = (size_t)kk[s]->n;
         memcpy(hs + o_desc + s * cp * 32, kk[s]->desc, n * 32);
         memcpy(hs + o_kps + s * cp * sizeof(orbg_keypoint), kk[s]->kps, n * sizeof(orbg_keypoint));
-        ((int32_t *)(hs + o_cnt))[s] = kk[s]->n;
-        ((int32_t *)(hs + o_idx))[s] = s;
+        L.at<int32_t>(hs, o_cnt)[s] = kk[s]->n;
+        L.at<int32_t>(hs, o_idx)[s] = s;
         memcpy(hs + o_mp + s * cp * sizeof(orbg_map_point), mpp[s], n * sizeof(orbg_map_point));
         memcpy(hs + o_md + s * cp * 32, mdp[s], n * 32);
         if (amp[s]) memcpy(hs + (s ? o_am2 : o_am1), amp[s], n);
@@ -5799,18 +5171,18 @@ extern "C" int orbg_search_by_sim3(orbg_ctx *c, const orbg_keyframe *kf1, const 
     HIPCHK(hipMemcpyAsync(db, hs, o_m, hipMemcpyHostToDevice, c->stream));
     orbg_keyframes K{};
     K.desc = db + o_desc;
-    K.kps = (const orbg_keypoint *)(db + o_kps);
-    K.counts = (const int32_t *)(db + o_cnt);
+    K.kps = L.at<orbg_keypoint>(db, o_kps);
+    K.counts = L.at<int32_t>(db, o_cnt);
     void *vn;
     if ((rc = sim3_scratch(c, cp * 2 * 4, &vn))) return rc;
-    rc = launch_search_by_sim3(c->stream, K, cap, (const int32_t *)(db + o_idx),
-                               (const int32_t *)(db + o_idx) + 1,
-                               (const orbg_sim3_pair *)(db + o_pair),
-                               (const orbg_map_point *)(db + o_mp), db + o_md, db + o_am1,
+    rc = launch_search_by_sim3(c->stream, K, cap, L.at<int32_t>(db, o_idx),
+                               L.at<int32_t>(db, o_idx) + 1,
+                               L.at<orbg_sim3_pair>(db, o_pair),
+                               L.at<orbg_map_point>(db, o_mp), db + o_md, db + o_am1,
                                db + o_am2, 1, th, c->scale, c->p.nlevels, (int32_t *)vn,
-                               (int32_t *)(db + o_m), (int32_t *)(db + o_nf), c->d_err);
+                               L.at<int32_t>(db, o_m), L.at<int32_t>(db, o_nf), c->d_err);
     if (rc) return set_err(ORBG_EIO, "k_sim3_match launch failed");
-    HIPCHK(hipMemcpyAsync(hs + o_m, db + o_m, o - o_m, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(hs + o_m, db + o_m, L.total() - o_m, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     memcpy(matches12, hs + o_m, (size_t)kf1->n * 4);
     memcpy(nfound, hs + o_nf, 4);
@@ -5870,17 +5242,6 @@ extern "C" int orbg_bow_score_batch_device(orbg_ctx *c, const orbg_vocab *v,
     return ORBG_OK;
 }
 
-// host BowVectors -> context scratch in orbg_bow_vectors layout (cap rows per vector)
-struct PlaceUpload {
-    size_t off = 0;
-    size_t take(size_t bytes)
-    {
-        const size_t o = off;
-        off += al256(bytes ? bytes : 1);
-        return o;
-    }
-};
-
 extern "C" int orbg_bow_score(orbg_ctx *c, const orbg_vocab *v, const int32_t *words1,
                               const double *weights1, int n1, const int32_t *words2,
                               const double *weights2, int n2, double *score)
@@ -5895,12 +5256,11 @@ extern "C" int orbg_bow_score(orbg_ctx *c, const orbg_vocab *v, const int32_t *w
         return set_err(ORBG_EINVAL, "NULL array");
     HIPCHK(hipSetDevice(c->device));
     const int cap = std::max(std::max(n1, n2), 1);
-    PlaceUpload U;
-    const size_t o_w = U.take((size_t)2 * cap * 4), o_x = U.take((size_t)2 * cap * 8);
-    const size_t o_n = U.take(8), o_i = U.take(8), o_s = U.take(8);
-    void *s;
-    if ((rc = scratch(c, U.off, &s))) return rc;
-    uint8_t *b = (uint8_t *)s;
+    Layout L;
+    const size_t o_w = L.take((size_t)2 * cap * 4), o_x = L.take((size_t)2 * cap * 8);
+    const size_t o_n = L.take(8), o_i = L.take(8), o_s = L.take(8);
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
     const int32_t nb[2] = {n1, n2}, idx[2] = {0, 1};
     if (n1) HIPCHK(hipMemcpyAsync(b + o_w, words1, (size_t)n1 * 4, hipMemcpyHostToDevice, c->stream));
     if (n1) HIPCHK(hipMemcpyAsync(b + o_x, weights1, (size_t)n1 * 8, hipMemcpyHostToDevice, c->stream));
@@ -5908,10 +5268,10 @@ extern "C" int orbg_bow_score(orbg_ctx *c, const orbg_vocab *v, const int32_t *w
     if (n2) HIPCHK(hipMemcpyAsync(b + o_x + (size_t)cap * 8, weights2, (size_t)n2 * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(b + o_n, nb, 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(b + o_i, idx, 8, hipMemcpyHostToDevice, c->stream));
-    orbg_bow_vectors V{(const int32_t *)(b + o_w), (const double *)(b + o_x),
-                       (const int32_t *)(b + o_n)};
-    if ((rc = launch_place_score(c->stream, V, V, cap, (const int32_t *)(b + o_i),
-                                 (const int32_t *)(b + o_i) + 1, 1, (double *)(b + o_s), &c->prof)))
+    orbg_bow_vectors V{L.at<int32_t>(b, o_w), L.at<double>(b, o_x),
+                       L.at<int32_t>(b, o_n)};
+    if ((rc = launch_place_score(c->stream, V, V, cap, L.at<int32_t>(b, o_i),
+                                 L.at<int32_t>(b, o_i) + 1, 1, L.at<double>(b, o_s), &c->prof)))
         return set_err(rc, "k_place_score launch failed");
     HIPCHK(hipMemcpyAsync(score, b + o_s, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -5934,39 +5294,39 @@ extern "C" int orbg_kfdb_create(orbg_ctx *c, const orbg_vocab *v, int max_keyfra
     if (cap > ORBG_KFDB_MAX_CAP) return set_err(ORBG_ENOTSUP, "cap %d (> %d)", cap, ORBG_KFDB_MAX_CAP);
     HIPCHK(hipSetDevice(c->device));
     const size_t K = (size_t)max_keyframes, kc = K * (size_t)cap, nw = (size_t)v->nwords;
-    PlaceUpload U;
-    const size_t o_wt = U.take(kc * 8), o_wd = U.take(kc * 4), o_nb = U.take(K * 4);
-    const size_t o_lv = U.take(K * 4), o_sq = U.take(K * 8), o_rl = U.take(K * 4);
-    const size_t o_ct = U.take(8), o_nl = U.take(4), o_rk = U.take(K * 4);
-    const size_t o_io = U.take((nw + 1) * 4), o_ic = U.take(nw * 4), o_po = U.take(kc * 2);
-    const size_t o_pe = U.take(K * 8), o_pt = U.take((nw / 4096 + 1) * 4);
+    Layout L;
+    const size_t o_wt = L.take(kc * 8), o_wd = L.take(kc * 4), o_nb = L.take(K * 4);
+    const size_t o_lv = L.take(K * 4), o_sq = L.take(K * 8), o_rl = L.take(K * 4);
+    const size_t o_ct = L.take(8), o_nl = L.take(4), o_rk = L.take(K * 4);
+    const size_t o_io = L.take((nw + 1) * 4), o_ic = L.take(nw * 4), o_po = L.take(kc * 2);
+    const size_t o_pe = L.take(K * 8), o_pt = L.take((nw / 4096 + 1) * 4);
     auto *db = new orbg_kfdb();
     db->device = c->device;
-    if (hipMalloc(&db->d_mem, U.off) != hipSuccess) {
+    if (hipMalloc(&db->d_mem, L.total()) != hipSuccess) {
         delete db;
-        return set_err(ORBG_ENOMEM, "KeyFrameDatabase: hipMalloc(%zu bytes)", U.off);
+        return set_err(ORBG_ENOMEM, "KeyFrameDatabase: hipMalloc(%zu bytes)", L.total());
     }
     uint8_t *b = (uint8_t *)db->d_mem;
     PlaceDb &D = db->D;
     D.K = max_keyframes;
     D.cap = cap;
     D.nwords = v->nwords;
-    D.weights = (double *)(b + o_wt);
-    D.words = (int32_t *)(b + o_wd);
-    D.nbow = (int32_t *)(b + o_nb);
-    D.live = (int32_t *)(b + o_lv);
-    D.seq = (int64_t *)(b + o_sq);
-    D.reloc = (float *)(b + o_rl);
-    D.counter = (int64_t *)(b + o_ct);
-    D.nlive = (int32_t *)(b + o_nl);
-    D.rank = (int32_t *)(b + o_rk);
-    D.inv_off = (int32_t *)(b + o_io);
-    D.inv_cur = (int32_t *)(b + o_ic);
-    D.post = (uint16_t *)(b + o_po);
-    D.pending = (unsigned long long *)(b + o_pe);
-    D.part = (int32_t *)(b + o_pt);
+    D.weights = L.at<double>(b, o_wt);
+    D.words = L.at<int32_t>(b, o_wd);
+    D.nbow = L.at<int32_t>(b, o_nb);
+    D.live = L.at<int32_t>(b, o_lv);
+    D.seq = L.at<int64_t>(b, o_sq);
+    D.reloc = L.at<float>(b, o_rl);
+    D.counter = L.at<int64_t>(b, o_ct);
+    D.nlive = L.at<int32_t>(b, o_nl);
+    D.rank = L.at<int32_t>(b, o_rk);
+    D.inv_off = L.at<int32_t>(b, o_io);
+    D.inv_cur = L.at<int32_t>(b, o_ic);
+    D.post = L.at<uint16_t>(b, o_po);
+    D.pending = L.at<unsigned long long>(b, o_pe);
+    D.part = L.at<int32_t>(b, o_pt);
     // everything from nbow on starts at zero (no live slot, counter 0, no pending score)
-    hipError_t e = hipMemsetAsync(b + o_nb, 0, U.off - o_nb, c->stream);
+    hipError_t e = hipMemsetAsync(b + o_nb, 0, L.total() - o_nb, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
         hipFree(db->d_mem);
@@ -6057,20 +5417,19 @@ extern "C" int orbg_kfdb_add(orbg_ctx *c, orbg_kfdb *db, int slot, const int32_t
     }
     if (live) return set_err(ORBG_EINVAL, "slot %d is already live", slot);
     const int cap = std::max(n, 1);
-    PlaceUpload U;
-    const size_t o_w = U.take((size_t)cap * 4), o_x = U.take((size_t)cap * 8), o_n = U.take(4);
-    const size_t o_s = U.take(4);
-    void *s;
-    if ((rc = scratch(c, U.off, &s))) return rc;
-    uint8_t *b = (uint8_t *)s;
+    Layout L;
+    const size_t o_w = L.take((size_t)cap * 4), o_x = L.take((size_t)cap * 8), o_n = L.take(4);
+    const size_t o_s = L.take(4);
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
     const int32_t nb = n, sl = slot;
     if (n) HIPCHK(hipMemcpyAsync(b + o_w, words, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     if (n) HIPCHK(hipMemcpyAsync(b + o_x, weights, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(b + o_n, &nb, 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(b + o_s, &sl, 4, hipMemcpyHostToDevice, c->stream));
-    orbg_bow_vectors V{(const int32_t *)(b + o_w), (const double *)(b + o_x),
-                       (const int32_t *)(b + o_n)};
-    if ((rc = launch_place_add(c->stream, D, (const int32_t *)(b + o_s), V, cap, nullptr, 1, &c->prof)))
+    orbg_bow_vectors V{L.at<int32_t>(b, o_w), L.at<double>(b, o_x),
+                       L.at<int32_t>(b, o_n)};
+    if ((rc = launch_place_add(c->stream, D, L.at<int32_t>(b, o_s), V, cap, nullptr, 1, &c->prof)))
         return set_err(rc, "k_place_add launch failed");
     db->dirty = db->touched = true;
     HIPCHK(hipStreamSynchronize(c->stream));  // the scratch is the next host call's too
@@ -6208,14 +5567,13 @@ static int kfdb_detect_host(orbg_ctx *c, orbg_kfdb *db, const int32_t *words,
     if ((n && (!words || !weights)) || (nconn && !conn) || (cand_cap && !cand))
         return set_err(ORBG_EINVAL, "NULL array");
     const int cap = std::max(n, 1), K = db->D.K;
-    PlaceUpload U;
-    const size_t o_w = U.take((size_t)cap * 4), o_x = U.take((size_t)cap * 8), o_n = U.take(4);
-    const size_t o_ng = U.take((size_t)K * ORBG_KFDB_NEIGH * 4), o_cn = U.take((size_t)nconn * 4);
-    const size_t o_nc = U.take(4), o_ms = U.take(4), o_cd = U.take((size_t)cand_cap * 4);
-    const size_t o_out = U.take(12);
-    void *s;
-    if ((rc = scratch(c, U.off, &s))) return rc;
-    uint8_t *b = (uint8_t *)s;
+    Layout L;
+    const size_t o_w = L.take((size_t)cap * 4), o_x = L.take((size_t)cap * 8), o_n = L.take(4);
+    const size_t o_ng = L.take((size_t)K * ORBG_KFDB_NEIGH * 4), o_cn = L.take((size_t)nconn * 4);
+    const size_t o_nc = L.take(4), o_ms = L.take(4), o_cd = L.take((size_t)cand_cap * 4);
+    const size_t o_out = L.take(12);
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
     const int32_t nb = n, ncn = nconn;
     if (n) HIPCHK(hipMemcpyAsync(b + o_w, words, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     if (n) HIPCHK(hipMemcpyAsync(b + o_x, weights, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
@@ -6225,19 +5583,19 @@ static int kfdb_detect_host(orbg_ctx *c, orbg_kfdb *db, const int32_t *words,
     HIPCHK(hipMemcpyAsync(b + o_nc, &ncn, 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(b + o_ms, &min_score, 4, hipMemcpyHostToDevice, c->stream));
     PlaceQuery Q{};
-    Q.q = orbg_bow_vectors{(const int32_t *)(b + o_w), (const double *)(b + o_x),
-                           (const int32_t *)(b + o_n)};
+    Q.q = orbg_bow_vectors{L.at<int32_t>(b, o_w), L.at<double>(b, o_x),
+                           L.at<int32_t>(b, o_n)};
     Q.qcap = cap;
     Q.nq = 1;
-    Q.neigh = (const int32_t *)(b + o_ng);
-    Q.conn = (const int32_t *)(b + o_cn);
+    Q.neigh = L.at<int32_t>(b, o_ng);
+    Q.conn = L.at<int32_t>(b, o_cn);
     Q.conn_cap = nconn;
-    Q.nconn = (const int32_t *)(b + o_nc);
-    Q.min_score = (const float *)(b + o_ms);
+    Q.nconn = L.at<int32_t>(b, o_nc);
+    Q.min_score = L.at<float>(b, o_ms);
     Q.loop = loop ? 1 : 0;
-    Q.cand = (int32_t *)(b + o_cd);
+    Q.cand = L.at<int32_t>(b, o_cd);
     Q.cand_cap = cand_cap;
-    Q.ncand = (int32_t *)(b + o_out);
+    Q.ncand = L.at<int32_t>(b, o_out);
     Q.max_common = Q.ncand + 1;
     Q.nscored = Q.ncand + 2;
     if ((rc = kfdb_detect(c, db, Q))) return rc;
@@ -6272,366 +5630,3 @@ extern "C" int orbg_kfdb_detect_loop(orbg_ctx *c, orbg_kfdb *db, const int32_t *
                             cand_cap, ncand, max_common, nscored);
 }
 
-// ---------------------------------------------------------------------------
-// Sim3Solver: batched RANSAC of LoopClosing::ComputeSim3 (sim3_kernels.hip)
-// ---------------------------------------------------------------------------
-extern "C" int orbg_sim3_ransac_iterations(double prob, int min_inliers, int max_its, int n)
-{
-    // Sim3Solver::SetRansacParameters (:114-138), type for type
-    const float epsilon = (float)min_inliers / n;
-    int nit;
-    if (min_inliers == n) {
-        nit = 1;
-    } else {
-        // a quotient that is NaN or outside int (n < min_inliers, a tiny epsilon) converts to
-        // INT_MIN in the reference's x86-64 build, so mRansacMaxIts ends as 1
-        const double v = ceil(log(1 - prob) / log(1 - pow(epsilon, 3)));
-        nit = (v > -2147483649.0 && v < 2147483648.0) ? (int)v : INT32_MIN;
-    }
-    return std::max(1, std::min(nit, max_its));
-}
-
-// the prepared-correspondence arrays of `pairs` pairs at `b`
-static size_t sim3_prep_bytes(size_t pairs, size_t cap) { return 3 * al256(pairs * cap * sizeof(float4)); }
-static Sim3Prep sim3_prep_at(uint8_t *b, size_t pairs, size_t cap)
-{
-    const size_t one = al256(pairs * cap * sizeof(float4));
-    return Sim3Prep{(float4 *)b, (float4 *)(b + one), (float4 *)(b + 2 * one)};
-}
-
-extern "C" int orbg_sim3_solve_batch_device(orbg_ctx *c, const orbg_sim3_problem *d_problems,
-                                            const orbg_sim3_corr *d_corrs, const int32_t *d_samples,
-                                            int npairs, int cap, int max_its, int32_t *d_counts,
-                                            orbg_sim3_hyp *d_hyps, uint64_t *d_masks,
-                                            orbg_sim3_result *d_results, uint8_t *d_inliers12,
-                                            int n1cap)
-{
-    if (!c) return set_err(ORBG_EINVAL, "context is NULL");
-    if (npairs < 0 || cap < 64 || (cap & 63) || max_its < 1 || n1cap < 1)
-        return set_err(ORBG_EINVAL, "bad npairs / cap (a multiple of 64) / max_its / n1cap");
-    if (cap > ORBG_SIM3_MAX_N)
-        return set_err(ORBG_ENOTSUP, "cap %d (> %d correspondences per pair)", cap, ORBG_SIM3_MAX_N);
-    if (npairs == 0) return ORBG_OK;
-    if ((int64_t)npairs * ((max_its + 3) / 4) > INT32_MAX)
-        return set_err(ORBG_ENOTSUP, "npairs * max_its too large for one launch");
-    if (!d_problems || !d_corrs || !d_samples || !d_counts || !d_hyps || !d_masks || !d_results ||
-        !d_inliers12)
-        return set_err(ORBG_EINVAL, "NULL device array");
-    HIPCHK(hipSetDevice(c->device));
-    void *s;
-    int rc = scratch(c, sim3_prep_bytes(npairs, cap), &s);
-    if (rc) return rc;
-    Sim3Args A{};
-    A.problems = d_problems;
-    A.corrs = d_corrs;
-    A.samples = d_samples;
-    A.npairs = npairs;
-    A.cap = cap;
-    A.max_its = max_its;
-    A.n1cap = n1cap;
-    A.prep = sim3_prep_at((uint8_t *)s, npairs, cap);
-    A.counts = d_counts;
-    A.hyps = d_hyps;
-    A.masks = (unsigned long long *)d_masks;
-    A.results = d_results;
-    A.inliers12 = d_inliers12;
-    if ((rc = launch_sim3(c->stream, A, &c->prof))) return set_err(rc, "Sim3Solver launch failed");
-    return ORBG_OK;
-}
-
-extern "C" int orbg_sim3_solve(orbg_ctx *c, const orbg_sim3_problem *problem,
-                               const orbg_sim3_corr *corrs, const int32_t *samples, int n1,
-                               int32_t *counts, orbg_sim3_hyp *hyps, uint64_t *masks,
-                               orbg_sim3_result *result, uint8_t *inliers12)
-{
-    if (!c || !problem || !result) return set_err(ORBG_EINVAL, "NULL argument");
-    const orbg_sim3_problem P = *problem;
-    if (P.n < 0 || P.iterations < 0 || n1 < 0) return set_err(ORBG_EINVAL, "negative size");
-    if (P.n > ORBG_SIM3_MAX_N)
-        return set_err(ORBG_ENOTSUP, "%d correspondences (> %d)", P.n, ORBG_SIM3_MAX_N);
-    if (P.iterations > (1 << 20)) return set_err(ORBG_ENOTSUP, "%d iterations", P.iterations);
-    if ((P.n && !corrs) || (n1 && !inliers12)) return set_err(ORBG_EINVAL, "NULL array");
-    for (int i = 0; i < P.n; i++)
-        if (corrs[i].index1 < 0 || corrs[i].index1 >= n1)
-            return set_err(ORBG_EINVAL, "index1 %d of correspondence %d outside [0, %d)",
-                           corrs[i].index1, i, n1);
-    const int cap = std::max(64, (P.n + 63) & ~63), its = std::max(P.iterations, 1);
-    const int run = sim3_iterations(P, cap, its), words = cap / 64;
-    if (run && !samples) return set_err(ORBG_EINVAL, "samples is NULL");
-    for (int it = 0; it < run; it++) {
-        const int32_t *s = samples + 3 * (size_t)it;
-        for (int k = 0; k < 3; k++)
-            if (s[k] < 0 || s[k] >= P.n)
-                return set_err(ORBG_EINVAL, "sample %d of iteration %d outside [0, %d)", s[k], it, P.n);
-        if (s[0] == s[1] || s[0] == s[2] || s[1] == s[2])
-            return set_err(ORBG_EINVAL, "iteration %d repeats a sample index", it);
-    }
-    HIPCHK(hipSetDevice(c->device));
-    PlaceUpload U;
-    const size_t o_p = U.take(sizeof(P)), o_k = U.take((size_t)cap * sizeof(orbg_sim3_corr));
-    const size_t o_s = U.take((size_t)its * 12), o_c = U.take((size_t)its * 4);
-    const size_t o_h = U.take((size_t)its * sizeof(orbg_sim3_hyp));
-    const size_t o_m = U.take((size_t)its * words * 8), o_r = U.take(sizeof(orbg_sim3_result));
-    const size_t o_i = U.take((size_t)std::max(n1, 1)), o_x = U.take(sim3_prep_bytes(1, cap));
-    void *sp;
-    int rc = scratch(c, U.off, &sp);
-    if (rc) return rc;
-    uint8_t *b = (uint8_t *)sp;
-    HIPCHK(hipMemcpyAsync(b + o_p, &P, sizeof(P), hipMemcpyHostToDevice, c->stream));
-    if (P.n) HIPCHK(hipMemcpyAsync(b + o_k, corrs, (size_t)P.n * sizeof(orbg_sim3_corr), hipMemcpyHostToDevice, c->stream));
-    if (run) HIPCHK(hipMemcpyAsync(b + o_s, samples, (size_t)run * 12, hipMemcpyHostToDevice, c->stream));
-    Sim3Args A{};
-    A.problems = (const orbg_sim3_problem *)(b + o_p);
-    A.corrs = (const orbg_sim3_corr *)(b + o_k);
-    A.samples = (const int32_t *)(b + o_s);
-    A.npairs = 1;
-    A.cap = cap;
-    A.max_its = its;
-    A.n1cap = std::max(n1, 1);
-    A.prep = sim3_prep_at(b + o_x, 1, cap);
-    A.counts = (int32_t *)(b + o_c);
-    A.hyps = (orbg_sim3_hyp *)(b + o_h);
-    A.masks = (unsigned long long *)(b + o_m);
-    A.results = (orbg_sim3_result *)(b + o_r);
-    A.inliers12 = b + o_i;
-    if ((rc = launch_sim3(c->stream, A, &c->prof))) return set_err(rc, "Sim3Solver launch failed");
-    const int nout = P.iterations, nw = (P.n + 63) / 64;
-    if (counts && nout) HIPCHK(hipMemcpyAsync(counts, b + o_c, (size_t)nout * 4, hipMemcpyDeviceToHost, c->stream));
-    if (hyps && nout) HIPCHK(hipMemcpyAsync(hyps, b + o_h, (size_t)nout * sizeof(orbg_sim3_hyp), hipMemcpyDeviceToHost, c->stream));
-    if (masks && nout && nw)
-        HIPCHK(hipMemcpy2DAsync(masks, (size_t)nw * 8, b + o_m, (size_t)words * 8, (size_t)nw * 8, nout,
-                                hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(result, b + o_r, sizeof(orbg_sim3_result), hipMemcpyDeviceToHost, c->stream));
-    if (n1) HIPCHK(hipMemcpyAsync(inliers12, b + o_i, (size_t)n1, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    c->prof.collect();
-    return ORBG_OK;
-}
-
-// ---------------------------------------------------------------------------
-// PnPsolver: batched EPnP RANSAC of Tracking::Relocalization (pnp_kernels.hip)
-// ---------------------------------------------------------------------------
-extern "C" int orbg_pnp_ransac_parameters(double prob, int min_inliers, int max_its, int min_set,
-                                          float epsilon, int n, int *min_inliers_out,
-                                          int *iterations_out)
-{
-    if (n < 1) return set_err(ORBG_EINVAL, "PnPsolver: n %d < 1", n);
-    if (!min_inliers_out || !iterations_out) return set_err(ORBG_EINVAL, "NULL output");
-    // PnPsolver::SetRansacParameters (:121-152), type for type
-    const float fn = (float)n * epsilon;  // int * float
-    int nmin = (fn > -2147483904.0f && fn < 2147483648.0f) ? (int)fn : INT32_MIN;
-    if (nmin < min_inliers) nmin = min_inliers;
-    if (nmin < min_set) nmin = min_set;
-    if (epsilon < (float)nmin / n) epsilon = (float)nmin / n;
-    int nit;
-    if (nmin == n) {
-        nit = 1;
-    } else {
-        // a quotient that is NaN or outside int converts to INT_MIN in the reference's x86-64
-        // build, so mRansacMaxIts ends as 1
-        const double v = ceil(log(1 - prob) / log(1 - pow(epsilon, 3)));
-        nit = (v > -2147483649.0 && v < 2147483648.0) ? (int)v : INT32_MIN;
-    }
-    *min_inliers_out = nmin;
-    *iterations_out = std::max(1, std::min(nit, max_its));
-    return ORBG_OK;
-}
-
-extern "C" int orbg_pnp_solve_batch_device(orbg_ctx *c, const orbg_pnp_problem *d_problems,
-                                           const orbg_pnp_corr *d_corrs, const int32_t *d_samples,
-                                           int ncand, int cap, int max_its, int32_t *d_counts,
-                                           orbg_pnp_hyp *d_hyps, uint64_t *d_masks,
-                                           orbg_pnp_refine *d_refines, uint64_t *d_refined_masks,
-                                           orbg_pnp_result *d_results, uint8_t *d_inliers, int n1cap)
-{
-    if (!c) return set_err(ORBG_EINVAL, "context is NULL");
-    if (ncand < 0 || cap < 64 || (cap & 63) || max_its < 1 || n1cap < 1)
-        return set_err(ORBG_EINVAL, "bad ncand / cap (a multiple of 64) / max_its / n1cap");
-    if (cap > ORBG_PNP_MAX_N)
-        return set_err(ORBG_ENOTSUP, "cap %d (> %d correspondences per candidate)", cap, ORBG_PNP_MAX_N);
-    if (ncand == 0) return ORBG_OK;
-    if ((int64_t)ncand * max_its > INT32_MAX)
-        return set_err(ORBG_ENOTSUP, "ncand * max_its too large for one launch");
-    if (!d_problems || !d_corrs || !d_samples || !d_counts || !d_hyps || !d_masks || !d_refines ||
-        !d_refined_masks || !d_results || !d_inliers)
-        return set_err(ORBG_EINVAL, "NULL device array");
-    HIPCHK(hipSetDevice(c->device));
-    PnpArgs A{};
-    A.problems = d_problems;
-    A.corrs = d_corrs;
-    A.samples = d_samples;
-    A.ncand = ncand;
-    A.cap = cap;
-    A.max_its = max_its;
-    A.n1cap = n1cap;
-    A.counts = d_counts;
-    A.hyps = d_hyps;
-    A.masks = (unsigned long long *)d_masks;
-    A.refines = d_refines;
-    A.refined_masks = (unsigned long long *)d_refined_masks;
-    A.results = d_results;
-    A.inliers = d_inliers;
-    int rc;
-    if ((rc = launch_pnp(c->stream, A, &c->prof))) return set_err(rc, "PnPsolver launch failed");
-    return ORBG_OK;
-}
-
-extern "C" int orbg_pnp_solve(orbg_ctx *c, const orbg_pnp_problem *problem, const orbg_pnp_corr *corrs,
-                              const int32_t *samples, int n1, int32_t *counts, orbg_pnp_hyp *hyps,
-                              uint64_t *masks, orbg_pnp_refine *refines, uint64_t *refined_masks,
-                              orbg_pnp_result *result, uint8_t *inliers)
-{
-    if (!c || !problem || !result) return set_err(ORBG_EINVAL, "NULL argument");
-    const orbg_pnp_problem P = *problem;
-    if (P.n < 0 || P.iterations < 0 || n1 < 0) return set_err(ORBG_EINVAL, "negative size");
-    if (P.min_set < 4 || P.min_set > ORBG_PNP_MAX_SET)
-        return set_err(ORBG_EINVAL, "min_set %d outside 4 .. %d", P.min_set, ORBG_PNP_MAX_SET);
-    if (P.n > ORBG_PNP_MAX_N)
-        return set_err(ORBG_ENOTSUP, "%d correspondences (> %d)", P.n, ORBG_PNP_MAX_N);
-    if (P.iterations > (1 << 20)) return set_err(ORBG_ENOTSUP, "%d iterations", P.iterations);
-    if ((P.n && !corrs) || (n1 && !inliers)) return set_err(ORBG_EINVAL, "NULL array");
-    for (int i = 0; i < P.n; i++)
-        if (corrs[i].index < 0 || corrs[i].index >= n1)
-            return set_err(ORBG_EINVAL, "index %d of correspondence %d outside [0, %d)",
-                           corrs[i].index, i, n1);
-    const int cap = std::max(64, (P.n + 63) & ~63), its = std::max(P.iterations, 1);
-    const int run = pnp_iterations(P, cap, its), words = cap / 64, m = P.min_set;
-    if (run && !samples) return set_err(ORBG_EINVAL, "samples is NULL");
-    std::vector<int32_t> padded((size_t)its * ORBG_PNP_MAX_SET, 0);
-    for (int it = 0; it < run; it++) {
-        const int32_t *s = samples + (size_t)m * it;
-        for (int k = 0; k < m; k++) {
-            if (s[k] < 0 || s[k] >= P.n)
-                return set_err(ORBG_EINVAL, "sample %d of iteration %d outside [0, %d)", s[k], it, P.n);
-            for (int j = 0; j < k; j++)
-                if (s[j] == s[k]) return set_err(ORBG_EINVAL, "iteration %d repeats a sample index", it);
-            padded[(size_t)it * ORBG_PNP_MAX_SET + k] = s[k];
-        }
-    }
-    HIPCHK(hipSetDevice(c->device));
-    PlaceUpload U;
-    const size_t o_p = U.take(sizeof(P)), o_k = U.take((size_t)cap * sizeof(orbg_pnp_corr));
-    const size_t o_s = U.take(padded.size() * 4), o_c = U.take((size_t)its * 4);
-    const size_t o_h = U.take((size_t)its * sizeof(orbg_pnp_hyp));
-    const size_t o_m = U.take((size_t)its * words * 8);
-    const size_t o_f = U.take((size_t)its * sizeof(orbg_pnp_refine));
-    const size_t o_g = U.take((size_t)its * words * 8), o_r = U.take(sizeof(orbg_pnp_result));
-    const size_t o_i = U.take((size_t)std::max(n1, 1));
-    void *sp;
-    int rc = scratch(c, U.off, &sp);
-    if (rc) return rc;
-    uint8_t *b = (uint8_t *)sp;
-    HIPCHK(hipMemcpyAsync(b + o_p, &P, sizeof(P), hipMemcpyHostToDevice, c->stream));
-    if (P.n) HIPCHK(hipMemcpyAsync(b + o_k, corrs, (size_t)P.n * sizeof(orbg_pnp_corr), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(b + o_s, padded.data(), padded.size() * 4, hipMemcpyHostToDevice, c->stream));
-    PnpArgs A{};
-    A.problems = (const orbg_pnp_problem *)(b + o_p);
-    A.corrs = (const orbg_pnp_corr *)(b + o_k);
-    A.samples = (const int32_t *)(b + o_s);
-    A.ncand = 1;
-    A.cap = cap;
-    A.max_its = its;
-    A.n1cap = std::max(n1, 1);
-    A.counts = (int32_t *)(b + o_c);
-    A.hyps = (orbg_pnp_hyp *)(b + o_h);
-    A.masks = (unsigned long long *)(b + o_m);
-    A.refines = (orbg_pnp_refine *)(b + o_f);
-    A.refined_masks = (unsigned long long *)(b + o_g);
-    A.results = (orbg_pnp_result *)(b + o_r);
-    A.inliers = b + o_i;
-    if ((rc = launch_pnp(c->stream, A, &c->prof))) return set_err(rc, "PnPsolver launch failed");
-    const int nout = P.iterations, nw = (P.n + 63) / 64;
-    if (counts && nout) HIPCHK(hipMemcpyAsync(counts, b + o_c, (size_t)nout * 4, hipMemcpyDeviceToHost, c->stream));
-    if (hyps && nout) HIPCHK(hipMemcpyAsync(hyps, b + o_h, (size_t)nout * sizeof(orbg_pnp_hyp), hipMemcpyDeviceToHost, c->stream));
-    if (refines && nout) HIPCHK(hipMemcpyAsync(refines, b + o_f, (size_t)nout * sizeof(orbg_pnp_refine), hipMemcpyDeviceToHost, c->stream));
-    if (masks && nout && nw)
-        HIPCHK(hipMemcpy2DAsync(masks, (size_t)nw * 8, b + o_m, (size_t)words * 8, (size_t)nw * 8, nout,
-                                hipMemcpyDeviceToHost, c->stream));
-    if (refined_masks && nout && nw)
-        HIPCHK(hipMemcpy2DAsync(refined_masks, (size_t)nw * 8, b + o_g, (size_t)words * 8, (size_t)nw * 8,
-                                nout, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(result, b + o_r, sizeof(orbg_pnp_result), hipMemcpyDeviceToHost, c->stream));
-    if (n1) HIPCHK(hipMemcpyAsync(inliers, b + o_i, (size_t)n1, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    c->prof.collect();
-    return ORBG_OK;
-}
-
-// ---------------------------------------------------------------------------
-// Optimizer::OptimizeSim3: batched Sim3 refinement of loop candidates (sim3opt_kernels.hip)
-// ---------------------------------------------------------------------------
-extern "C" int orbg_optimize_sim3_batch_device(orbg_ctx *c, const orbg_sim3opt_problem *d_problems,
-                                               const orbg_sim3opt_corr *d_corrs,
-                                               const orbg_sim3_hyp *d_init, int npairs, int cap,
-                                               orbg_sim3opt_result *d_results, uint8_t *d_keep,
-                                               int n1cap)
-{
-    if (!c) return set_err(ORBG_EINVAL, "context is NULL");
-    if (npairs < 0 || cap < 64 || (cap & 63) || n1cap < 1)
-        return set_err(ORBG_EINVAL, "bad npairs / cap (a multiple of 64) / n1cap");
-    if (cap > ORBG_SIM3OPT_MAX_N)
-        return set_err(ORBG_ENOTSUP, "cap %d (> %d correspondences per candidate)", cap,
-                       ORBG_SIM3OPT_MAX_N);
-    if (npairs == 0) return ORBG_OK;
-    if (!d_problems || !d_corrs || !d_init || !d_results || !d_keep)
-        return set_err(ORBG_EINVAL, "NULL device array");
-    HIPCHK(hipSetDevice(c->device));
-    Sim3OptArgs A{};
-    A.problems = d_problems;
-    A.corrs = d_corrs;
-    A.init = d_init;
-    A.npairs = npairs;
-    A.cap = cap;
-    A.n1cap = n1cap;
-    A.results = d_results;
-    A.keep = d_keep;
-    int rc;
-    if ((rc = launch_sim3opt(c->stream, A, &c->prof))) return set_err(rc, "OptimizeSim3 launch failed");
-    return ORBG_OK;
-}
-
-extern "C" int orbg_optimize_sim3(orbg_ctx *c, const orbg_sim3opt_problem *problem,
-                                  const orbg_sim3opt_corr *corrs, const orbg_sim3_hyp *init, int n1,
-                                  orbg_sim3opt_result *result, uint8_t *keep)
-{
-    if (!c || !problem || !init || !result) return set_err(ORBG_EINVAL, "NULL argument");
-    const orbg_sim3opt_problem P = *problem;
-    if (P.n < 0 || n1 < 0) return set_err(ORBG_EINVAL, "negative size");
-    if (!(P.th2 > 0.0f) || !(P.th2 <= FLT_MAX))
-        return set_err(ORBG_EINVAL, "th2 %g is not finite and positive", (double)P.th2);
-    if (P.n > ORBG_SIM3OPT_MAX_N)
-        return set_err(ORBG_ENOTSUP, "%d correspondences (> %d)", P.n, ORBG_SIM3OPT_MAX_N);
-    if ((P.n && !corrs) || (n1 && !keep)) return set_err(ORBG_EINVAL, "NULL array");
-    for (int i = 0; i < P.n; i++)
-        if (corrs[i].index1 < 0 || corrs[i].index1 >= n1)
-            return set_err(ORBG_EINVAL, "index1 %d of correspondence %d outside [0, %d)",
-                           corrs[i].index1, i, n1);
-    const int cap = std::max(64, (P.n + 63) & ~63);
-    HIPCHK(hipSetDevice(c->device));
-    PlaceUpload U;
-    const size_t o_p = U.take(sizeof(P)), o_k = U.take((size_t)cap * sizeof(orbg_sim3opt_corr));
-    const size_t o_h = U.take(sizeof(orbg_sim3_hyp)), o_r = U.take(sizeof(orbg_sim3opt_result));
-    const size_t o_i = U.take((size_t)std::max(n1, 1));
-    void *sp;
-    int rc = scratch(c, U.off, &sp);
-    if (rc) return rc;
-    uint8_t *b = (uint8_t *)sp;
-    HIPCHK(hipMemcpyAsync(b + o_p, &P, sizeof(P), hipMemcpyHostToDevice, c->stream));
-    if (P.n) HIPCHK(hipMemcpyAsync(b + o_k, corrs, (size_t)P.n * sizeof(orbg_sim3opt_corr), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(b + o_h, init, sizeof(orbg_sim3_hyp), hipMemcpyHostToDevice, c->stream));
-    Sim3OptArgs A{};
-    A.problems = (const orbg_sim3opt_problem *)(b + o_p);
-    A.corrs = (const orbg_sim3opt_corr *)(b + o_k);
-    A.init = (const orbg_sim3_hyp *)(b + o_h);
-    A.npairs = 1;
-    A.cap = cap;
-    A.n1cap = std::max(n1, 1);
-    A.results = (orbg_sim3opt_result *)(b + o_r);
-    A.keep = b + o_i;
-    if ((rc = launch_sim3opt(c->stream, A, &c->prof))) return set_err(rc, "OptimizeSim3 launch failed");
-    HIPCHK(hipMemcpyAsync(result, b + o_r, sizeof(orbg_sim3opt_result), hipMemcpyDeviceToHost, c->stream));
-    if (n1) HIPCHK(hipMemcpyAsync(keep, b + o_i, (size_t)n1, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    c->prof.collect();
-    return ORBG_OK;
-}

@@ -7,6 +7,7 @@
 
 #include "orbg_internal.h"
 #include "orbg_device.h"
+#include "orbg_launch.h"
 
 #pragma clang fp contract(off)
 
@@ -18,7 +19,6 @@ __device__ __attribute__((aligned(16))) int8_t od_pattern_i8[1024] = {
 #include "orb_pattern.inc"
 #undef ORBG_PAIR
 };
-
 
 // cv::fastAtan2 (OpenCV 3.4 atan_f32), degrees in [0, 360]
 __device__ __forceinline__ float fast_atan2(float y, float x)

@@ -51,14 +51,15 @@ struct PlaceQuery {
 };
 
 size_t place_query_lds(int K, int qcap);
+struct Prof;  // the context's profiler (orbg_ctx.h)
 int launch_place_score(hipStream_t st, const orbg_bow_vectors &a, const orbg_bow_vectors &b, int cap,
                        const int32_t *a_index, const int32_t *b_index, int npairs, double *score,
-                       void *prof);
+                       Prof *prof);
 int launch_place_add(hipStream_t st, const PlaceDb &D, const int32_t *slots,
-                     const orbg_bow_vectors &v, int vcap, const int32_t *index, int n, void *prof);
+                     const orbg_bow_vectors &v, int vcap, const int32_t *index, int n, Prof *prof);
 int launch_place_erase(hipStream_t st, const PlaceDb &D, int slot);
-int launch_place_rebuild(hipStream_t st, const PlaceDb &D, void *prof);
+int launch_place_rebuild(hipStream_t st, const PlaceDb &D, Prof *prof);
 int launch_place_count(hipStream_t st, const PlaceDb &D);
-int launch_place_query(hipStream_t st, const PlaceDb &D, const PlaceQuery &Q, void *prof);
+int launch_place_query(hipStream_t st, const PlaceDb &D, const PlaceQuery &Q, Prof *prof);
 
 }  // namespace orbg

@@ -37,13 +37,11 @@
 
 #include "../../include/orbg.h"
 #include "place_args.h"
+#include "orbg_launch.h"
 
 #pragma clang fp contract(off)
 
 namespace orbg {
-
-void prof_begin(void *prof, hipStream_t s, const char *n, hipEvent_t *a);
-void prof_end(void *prof, hipStream_t s, const char *n, hipEvent_t a);
 
 #define PLACE_THREADS 256
 #define PLACE_SCAN_THREADS 1024
@@ -488,7 +486,7 @@ static int last_rc() { return hipGetLastError() == hipSuccess ? ORBG_OK : ORBG_E
 
 int launch_place_score(hipStream_t st, const orbg_bow_vectors &a, const orbg_bow_vectors &b, int cap,
                        const int32_t *a_index, const int32_t *b_index, int npairs, double *score,
-                       void *prof)
+                       Prof *prof)
 {
     if (npairs <= 0) return ORBG_OK;
     hipEvent_t ev = nullptr;
@@ -500,7 +498,7 @@ int launch_place_score(hipStream_t st, const orbg_bow_vectors &a, const orbg_bow
 }
 
 int launch_place_add(hipStream_t st, const PlaceDb &D, const int32_t *slots,
-                     const orbg_bow_vectors &v, int vcap, const int32_t *index, int n, void *prof)
+                     const orbg_bow_vectors &v, int vcap, const int32_t *index, int n, Prof *prof)
 {
     if (n <= 0) return ORBG_OK;
     hipEvent_t ev = nullptr;
@@ -523,7 +521,7 @@ int launch_place_count(hipStream_t st, const PlaceDb &D)
     return last_rc();
 }
 
-int launch_place_rebuild(hipStream_t st, const PlaceDb &D, void *prof)
+int launch_place_rebuild(hipStream_t st, const PlaceDb &D, Prof *prof)
 {
     hipEvent_t ev = nullptr;
     if (D.nwords > 0) {
@@ -555,7 +553,7 @@ int launch_place_rebuild(hipStream_t st, const PlaceDb &D, void *prof)
     return last_rc();
 }
 
-int launch_place_query(hipStream_t st, const PlaceDb &D, const PlaceQuery &Q, void *prof)
+int launch_place_query(hipStream_t st, const PlaceDb &D, const PlaceQuery &Q, Prof *prof)
 {
     if (Q.nq <= 0) return ORBG_OK;
     const size_t lds = place_query_lds(D.K, Q.qcap);

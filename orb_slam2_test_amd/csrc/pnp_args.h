@@ -1,5 +1,5 @@
 // pnp_args.h -- launch arguments of PnPsolver (pnp_kernels.hip), shared with the host entry
-// points (orbg_api.hip).  The EPnP arithmetic itself is in pnp_device.h.
+// points (api_solvers.hip).  The EPnP arithmetic itself is in pnp_device.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -39,6 +39,7 @@ __host__ __device__ static inline int pnp_iterations(const orbg_pnp_problem &P, 
     return P.iterations < 0 ? 0 : (P.iterations > max_its ? max_its : P.iterations);
 }
 
-int launch_pnp(hipStream_t st, const PnpArgs &A, void *prof);
+struct Prof;  // the context's profiler (orbg_ctx.h)
+int launch_pnp(hipStream_t st, const PnpArgs &A, Prof *prof);
 
 }  // namespace orbg

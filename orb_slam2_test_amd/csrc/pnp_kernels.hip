@@ -28,11 +28,9 @@
 #include "../../include/orbg.h"
 #include "pnp_args.h"
 #include "pnp_device.h"
+#include "orbg_launch.h"
 
 namespace orbg {
-
-void prof_begin(void *prof, hipStream_t s, const char *n, hipEvent_t *a);
-void prof_end(void *prof, hipStream_t s, const char *n, hipEvent_t a);
 
 #ifndef ORBG_PNP_HYP_LANES
 #define ORBG_PNP_HYP_LANES 16
@@ -403,7 +401,7 @@ __global__ __launch_bounds__(PNP_THREADS) void k_pnp_select(PnpArgs A)
     }
 }
 
-int launch_pnp(hipStream_t st, const PnpArgs &A, void *prof)
+int launch_pnp(hipStream_t st, const PnpArgs &A, Prof *prof)
 {
     hipEvent_t ev;
     const size_t rows = (size_t)A.ncand * A.max_its, words = (size_t)(A.cap >> 6);

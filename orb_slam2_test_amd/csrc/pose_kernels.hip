@@ -23,13 +23,11 @@
 #include "orbg_device.h"
 #include "g2o_math.h"
 #include "match_device.h"
+#include "orbg_launch.h"
 
 #pragma clang fp contract(off)
 
 namespace orbg {
-
-void prof_begin(void *prof, hipStream_t s, const char *n, hipEvent_t *a);
-void prof_end(void *prof, hipStream_t s, const char *n, hipEvent_t a);
 
 struct PoseInvSigma2 {
     float v[16];
@@ -378,17 +376,12 @@ __global__ __launch_bounds__(256) void k_match_pose_edges(
     if (tid < 12) tcw0[12 * (size_t)p + tid] = (tid % 5 == 0) ? 1.f : 0.f;  // [I | 0]
 }
 
-int launch_pose_opt(hipStream_t st, const orbg_pose_edge *edges, const int32_t *counts, int cap,
-                    const orbg_pose_camera *cams, const float *tcw_in, double *q_out,
-                    double *t_out, float *tcw_out, uint8_t *outlier, int32_t *ninliers,
-                    int nframes, void *prof);
-
 int launch_match_pose(hipStream_t st, const orbg_keypoint *kps, const int32_t *counts, int fc,
                       const int32_t *f1, const int32_t *f2, const int32_t *m12, int npairs,
                       const orbg_pose_camera &cam, float depth, const float *inv_sigma2, int nlev,
                       orbg_pose_edge *edges, int32_t *ecount, orbg_pose_camera *cams,
                       float *tcw0, float *tcw_out, uint8_t *outlier, double *q_out,
-                      double *t_out, int32_t *ninliers, void *prof)
+                      double *t_out, int32_t *ninliers, Prof *prof)
 {
     if (npairs <= 0) return ORBG_OK;
     PoseInvSigma2 inv2{};
@@ -403,7 +396,7 @@ int launch_match_pose(hipStream_t st, const orbg_keypoint *kps, const int32_t *c
 int launch_pose_opt(hipStream_t st, const orbg_pose_edge *edges, const int32_t *counts, int cap,
                     const orbg_pose_camera *cams, const float *tcw_in, double *q_out,
                     double *t_out, float *tcw_out, uint8_t *outlier, int32_t *ninliers,
-                    int nframes, void *prof)
+                    int nframes, Prof *prof)
 {
     if (nframes <= 0) return ORBG_OK;
     hipEvent_t ev = nullptr;

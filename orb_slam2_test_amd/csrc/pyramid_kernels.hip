@@ -23,6 +23,7 @@
 #include "orbg_device.h"
 #include "blur_device.h"
 #include "pyramid_args.h"
+#include "orbg_launch.h"
 
 #pragma clang fp contract(off)
 

@@ -65,6 +65,7 @@ struct SchurArgs {
     double *dx_pose, *dx_point;        // outputs [npose][6], [npoint][3]
 };
 
-int launch_schur(hipStream_t st, const SchurArgs &A, void *prof);
+struct Prof;  // the context's profiler (orbg_ctx.h)
+int launch_schur(hipStream_t st, const SchurArgs &A, Prof *prof);
 
 }  // namespace orbg

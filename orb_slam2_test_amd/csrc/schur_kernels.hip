@@ -33,13 +33,11 @@
 #include "../../include/orbg.h"
 #include "orbg_device.h"
 #include "schur_args.h"
+#include "orbg_launch.h"
 
 #pragma clang fp contract(off)
 
 namespace orbg {
-
-void prof_begin(void *prof, hipStream_t s, const char *n, hipEvent_t *a);
-void prof_end(void *prof, hipStream_t s, const char *n, hipEvent_t a);
 
 // (H_ll + lambda I)^-1 by Eigen's cofactor 3x3 inverse (orc inv3_eigen) and D^-1 b_l
 __device__ __forceinline__ void schur_dinv(const SchurArgs &A, int p, double d[9], double db[3])
@@ -505,7 +503,7 @@ __global__ void k_schur_backsub(SchurArgs A)
     for (int r = 0; r < 3; r++) xl[r] = (Di[r * 3] * cl[0] + Di[r * 3 + 1] * cl[1]) + Di[r * 3 + 2] * cl[2];
 }
 
-int launch_schur(hipStream_t st, const SchurArgs &A, void *prof)
+int launch_schur(hipStream_t st, const SchurArgs &A, Prof *prof)
 {
     const int T = 256;
     hipEvent_t ev = nullptr;

@@ -1,5 +1,5 @@
 // sim3_args.h -- launch arguments and the per-hypothesis arithmetic of Sim3Solver
-// (sim3_kernels.hip), shared with the host entry points (orbg_api.hip).
+// (sim3_kernels.hip), shared with the host entry points (api_solvers.hip).
 //
 // The arithmetic is plain fp32 in a fixed operation order (the build has -ffp-contract=off),
 // written as __host__ __device__ functions so that a host program can run the very same
@@ -216,6 +216,7 @@ __host__ __device__ static inline bool sim3_inlier(const float T12[12], const fl
     return e1 < a.w && e2 < b.w;
 }
 
-int launch_sim3(hipStream_t st, const Sim3Args &A, void *prof);
+struct Prof;  // the context's profiler (orbg_ctx.h)
+int launch_sim3(hipStream_t st, const Sim3Args &A, Prof *prof);
 
 }  // namespace orbg

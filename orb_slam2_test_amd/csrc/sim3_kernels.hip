@@ -24,11 +24,9 @@
 
 #include "../../include/orbg.h"
 #include "sim3_args.h"
+#include "orbg_launch.h"
 
 namespace orbg {
-
-void prof_begin(void *prof, hipStream_t s, const char *n, hipEvent_t *a);
-void prof_end(void *prof, hipStream_t s, const char *n, hipEvent_t a);
 
 #define SIM3_THREADS 256
 #define SIM3_WAVES (SIM3_THREADS / 64)
@@ -178,7 +176,7 @@ __global__ __launch_bounds__(SIM3_THREADS) void k_sim3_select(Sim3Args A)
     }
 }
 
-int launch_sim3(hipStream_t st, const Sim3Args &A, void *prof)
+int launch_sim3(hipStream_t st, const Sim3Args &A, Prof *prof)
 {
     hipEvent_t ev;
     if (hipMemsetAsync(A.inliers12, 0, (size_t)A.npairs * A.n1cap, st) != hipSuccess) return ORBG_EIO;

@@ -1,5 +1,5 @@
 // sim3opt_args.h -- launch arguments and the arithmetic of Optimizer::OptimizeSim3
-// (sim3opt_kernels.hip), shared with the host entry points (orbg_api.hip) and with the
+// (sim3opt_kernels.hip), shared with the host entry points (api_solvers.hip) and with the
 // one-core host program of tools/sim3opt_bench.py (sim3opt_host.hip).
 //
 // Everything g2o evaluates for the one free VertexSim3Expmap is here as __host__ __device__
@@ -365,6 +365,7 @@ __host__ __device__ static inline void so_result(const Sim3d &S, int nin, int nb
     r->iterations[1] = it1;
 }
 
-int launch_sim3opt(hipStream_t st, const Sim3OptArgs &A, void *prof);
+struct Prof;  // the context's profiler (orbg_ctx.h)
+int launch_sim3opt(hipStream_t st, const Sim3OptArgs &A, Prof *prof);
 
 }  // namespace orbg

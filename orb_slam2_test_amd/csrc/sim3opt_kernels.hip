@@ -28,13 +28,11 @@
 #include "orbg_internal.h"
 #include "orbg_device.h"
 #include "sim3opt_args.h"
+#include "orbg_launch.h"
 
 #pragma clang fp contract(off)
 
 namespace orbg {
-
-void prof_begin(void *prof, hipStream_t s, const char *n, hipEvent_t *a);
-void prof_end(void *prof, hipStream_t s, const char *n, hipEvent_t a);
 
 #define SO_T 256
 
@@ -160,7 +158,7 @@ __global__ __launch_bounds__(SO_T) void k_sim3_opt(Sim3OptArgs A)
     }
 }
 
-int launch_sim3opt(hipStream_t st, const Sim3OptArgs &A, void *prof)
+int launch_sim3opt(hipStream_t st, const Sim3OptArgs &A, Prof *prof)
 {
     if (A.npairs <= 0) return ORBG_OK;
     hipEvent_t ev = nullptr;

@@ -27,15 +27,13 @@
 #include "../../include/orbg.h"
 #include "orbg_device.h"
 #include "orbg_internal.h"
+#include "orbg_launch.h"
 
 #define ORBG_ST_MAX_DEV 64  // devices whose k_stereo_rows_match LDS attribute is cached
 
 #pragma clang fp contract(off)
 
 namespace orbg {
-
-void prof_begin(void *prof, hipStream_t s, const char *n, hipEvent_t *a);
-void prof_end(void *prof, hipStream_t s, const char *n, hipEvent_t a);
 
 #ifndef ORBG_ST_XCD
 #define ORBG_ST_XCD 1  // XCD-aware pair mapping of k_stereo_match / k_stereo_sad (0: A/B)
@@ -865,7 +863,7 @@ int launch_stereo(hipStream_t st, const OrbgGeom &g, const orbg_keypoint *kps,
                   const uint8_t *desc, const int32_t *counts, const int32_t *d_left,
                   const int32_t *d_right, int npairs, const uint8_t *img0, int64_t img_fs,
                   int img_pitch, const uint8_t *pyr, float bf, float min_z, void *scratch,
-                  float *uright, float *depth, int32_t *nvalid, void *prof)
+                  float *uright, float *depth, int32_t *nvalid, Prof *prof)
 {
     if (g.h > ST_MAX_ROWS || g.frame_cap > 32767) return ORBG_ENOTSUP;
     StereoGeom G{};

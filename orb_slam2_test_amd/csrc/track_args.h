@@ -35,6 +35,7 @@ struct TrackArgs {
 
 enum { TRK_LASTFRAME = 0, TRK_LOCAL = 1, TRK_RELOC = 2, TRK_LOOP = 3 };
 
-int launch_track(hipStream_t st, int mode, const TrackArgs &A, int nframes, void *prof);
+struct Prof;  // the context's profiler (orbg_ctx.h)
+int launch_track(hipStream_t st, int mode, const TrackArgs &A, int nframes, Prof *prof);
 
 }  // namespace orbg

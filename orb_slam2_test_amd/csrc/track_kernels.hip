@@ -40,13 +40,11 @@
 #include "frame_device.h"
 #include "match_device.h"
 #include "track_args.h"
+#include "orbg_launch.h"
 
 #pragma clang fp contract(off)
 
 namespace orbg {
-
-void prof_begin(void *prof, hipStream_t s, const char *n, hipEvent_t *a);
-void prof_end(void *prof, hipStream_t s, const char *n, hipEvent_t a);
 
 #define TH_HIGH 100
 #define TH_LOW 50
@@ -742,7 +740,7 @@ size_t track_resolve_lds_bytes(int fc, int qc) { return track_resolve_lds(fc, qc
 
 template <int MODE>
 static void launch_mode(hipStream_t st, const TrackArgs &A, int nframes, int nbx, size_t l1,
-                        size_t l2, void *prof)
+                        size_t l2, Prof *prof)
 {
     hipFuncSetAttribute((const void *)k_track_cands<MODE>,
                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)l1);
@@ -756,7 +754,7 @@ static void launch_mode(hipStream_t st, const TrackArgs &A, int nframes, int nbx
 
 // mode: TRK_LASTFRAME / TRK_LOCAL / TRK_RELOC / TRK_LOOP.  A's pointers are device pointers;
 // nframes frames.
-int launch_track(hipStream_t st, int mode, const TrackArgs &A, int nframes, void *prof)
+int launch_track(hipStream_t st, int mode, const TrackArgs &A, int nframes, Prof *prof)
 {
     if (A.fc > (1 << 20) || nframes <= 0) return ORBG_EINVAL;
     const size_t l1 = track_cands_lds(A.fc), l2 = track_resolve_lds(A.fc, A.qc);

@@ -21,6 +21,7 @@
 
 #include "../../include/orbg.h"
 #include "orbg_device.h"
+#include "orbg_launch.h"
 
 #pragma clang fp contract(off)
 
