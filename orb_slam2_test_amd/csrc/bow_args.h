@@ -1,5 +1,5 @@
 // bow_args.h -- device layout and launch arguments of the DBoW2 transform (bow_kernels.hip),
-// shared with the host entry points (orbg_api.hip).
+// shared with the host entry points (api_bow.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>

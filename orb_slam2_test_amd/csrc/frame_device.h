@@ -1,5 +1,5 @@
 // frame_device.h -- cv::undistortPoints(src, dst, K, D, noArray(), K) for one point, shared by
-// k_undistort (frame_kernels.hip) and the host-side Frame::ComputeImageBounds (orbg_api.hip)
+// k_undistort (frame_kernels.hip) and the host-side Frame::ComputeImageBounds (api_frame.hip)
 // so both run the same expression tree.  OpenCV 3.4's cvUndistortPointsInternal
 // (modules/imgproc/src/undistort.cpp) with the default criteria TermCriteria(COUNT, 5, 0.01):
 // five fixed-point iterations in double, no EPS test; K, D converted from CV_32F to double;

@@ -2,12 +2,12 @@
 // and kernel launches.  All reference tables are computed here exactly as the
 // ORBextractor ctor does (ORBextractor.cc:432-521); geometry (levels, cells, quadtree
 // roots) as ComputePyramid / ComputeKeyPointsOctTree / DistributeOctTree do.
+// Cut into files of their own: the tracking matchers and PoseOptimization (api_track.hip),
+// the vocabulary and BoW (api_bow.hip), the Frame helpers (api_frame.hip), place recognition
+// (api_place.hip) and the solvers (api_solvers.hip).
 #include "orbg_ctx.h"
-#include "track_args.h"
 #include "schur_args.h"
 #include "bow_args.h"
-#include "place_args.h"
-#include "frame_device.h"
 #include "g2o_math.h"
 
 #pragma clang fp contract(off)
@@ -39,7 +39,7 @@ std::atomic<int> orbg::g_extract_batches{0};
 bool orbg::prof_skip(const char *name)
 {
     static const char *skip = getenv("ORBG_SKIP");
-    static const int after = getenv("ORBG_SKIP_AFTER") ? atoi(getenv("ORBG_SKIP_AFTER")) : 0;
+    static const int after = env_int("ORBG_SKIP_AFTER", 0);
     if (!skip || g_extract_batches.load() <= after) return false;
     const size_t n = strlen(name);  // whole comma-separated names ("octree" != "octree_big")
     for (const char *p = skip; (p = strstr(p, name)); p += n)
@@ -251,10 +251,7 @@ int orbg::scratch(orbg_ctx *c, size_t bytes, void **p)
 
 static bool skip_big_enabled()
 {
-    static const int on = [] {
-        const char *e = getenv("ORBG_SKIP_BIG");
-        return e ? atoi(e) : 1;
-    }();
+    static const int on = env_int("ORBG_SKIP_BIG", 1);
     return on != 0;
 }
 
@@ -262,10 +259,7 @@ static bool skip_big_enabled()
 // the launch); ORBG_SF_TAG=0: d_err[2] cleared by a memset ahead of every frame (A/B)
 static bool sf_tag_enabled()
 {
-    static const int on = [] {
-        const char *e = getenv("ORBG_SF_TAG");
-        return e ? atoi(e) : 1;
-    }();
+    static const int on = env_int("ORBG_SF_TAG", 1);
     return on != 0;
 }
 
@@ -273,28 +267,19 @@ static bool sf_tag_enabled()
 // launch, so the critical chain's first kernel is submitted first (ORBG_PYR_FIRST=0: after, A/B)
 static bool pyr_first_enabled()
 {
-    static const int on = [] {
-        const char *e = getenv("ORBG_PYR_FIRST");
-        return e ? atoi(e) : 1;
-    }();
+    static const int on = env_int("ORBG_PYR_FIRST", 1);
     return on != 0;
 }
 
 static bool hc_enabled()
 {
-    static const int on = [] {
-        const char *e = getenv("ORBG_HC");
-        return e ? atoi(e) : 1;
-    }();
+    static const int on = env_int("ORBG_HC", 1);
     return on != 0;
 }
 
 static bool use_zc(orbg_ctx *c)
 {
-    if (c->zc_mode < 0) {
-        const char *e = getenv("ORBG_ZC");
-        c->zc_mode = e ? atoi(e) != 0 : 1;
-    }
+    if (c->zc_mode < 0) c->zc_mode = env_int("ORBG_ZC", 1) != 0;
     return c->zc_mode != 0;
 }
 
@@ -346,10 +331,7 @@ static int imz_buf(orbg_ctx *c, size_t bytes, uint8_t **h, uint8_t **d)
 // staged DMA
 static bool img_pull_enabled()
 {
-    static const int on = [] {
-        const char *e = getenv("ORBG_IMG_PULL");
-        return e ? atoi(e) : 1;
-    }();
+    static const int on = env_int("ORBG_IMG_PULL", 1);
     return on != 0;
 }
 
@@ -501,7 +483,7 @@ static int plan(orbg_ctx *c, int w, int h, int batch)
     G.brief_fma = p.brief_fma;
     G.sincos_mode = p.sincos_mode;
 #ifdef ORBG_DEV_KNOBS
-    G.dbg = getenv("ORBG_DBG") ? atoi(getenv("ORBG_DBG")) : 0;  // phase-stop timing knob
+    G.dbg = env_int("ORBG_DBG", 0);  // phase-stop timing knob
 #else
     G.dbg = 0;
 #endif
@@ -529,10 +511,10 @@ static int plan(orbg_ctx *c, int w, int h, int batch)
     // tiled blurred levels (blur_device.h blur2_tile TILED; k_orient_desc's rBRIEF loads):
     // k_blur2 must be the only writer -- the k_pyramid blur (ORBG_PYR_BLUR) and the fused
     // FAST-cell blur (opt-in ORBG_FAST_BLUR) write row-major
-    {
-        const char *pb = getenv("ORBG_PYR_BLUR");
-        G.blur_tiled = c->blur_tiled_env && !c->fast_blur_env && !(pb && atoi(pb) != 0);
-    }
+    // ORBG_PYR_BLUR (A/B): 0 k_blur2 launches, 1 every level blurred inside k_pyramid,
+    // 2 levels >= 1 inside k_pyramid and level 0 by k_blur2 (beside it on the side stream)
+    const int pyr_blur = env_int("ORBG_PYR_BLUR", 0);
+    G.blur_tiled = c->blur_tiled_env && !c->fast_blur_env && pyr_blur == 0;
     int64_t pyr_off = 0, blur_off = 0;
     int key_off = 0, node_off = 0, out_off = 0;
     std::vector<int32_t> tile_base, blur2_base;
@@ -846,8 +828,7 @@ static int plan(orbg_ctx *c, int w, int h, int batch)
     G.fast_blur = 0;
     G.bt_total = 0;
     {
-        const char *pb = getenv("ORBG_PYR_BLUR");
-        bool ok = c->fast_blur_env && !(pb && atoi(pb) != 0) && !(fr_ok && c->fr_mode);
+        bool ok = c->fast_blur_env && pyr_blur == 0 && !(fr_ok && c->fr_mode);
         for (int l = 0; l < G.L && ok; l++) {
             OrbgLevel &L = G.lv[l];
             int gx0 = 1 << 30, gy0 = 1 << 30, gx1 = 0, gy1 = 0;
@@ -911,7 +892,7 @@ static int plan(orbg_ctx *c, int w, int h, int batch)
             d.acap2 = (std::max(d.acap, cells) + 7) & ~7;
             d.nbw = 512 * roots;
             d.uni_bytes = std::max(d.nbw * 4, 3 * d.acap * 8);
-            d.tile_sort = getenv("ORBG_OD_SORT") ? atoi(getenv("ORBG_OD_SORT")) != 0 : 0;  // measured: no gain
+            d.tile_sort = env_int("ORBG_OD_SORT", 0) != 0;  // measured: no gain
             if (budget) {
                 const int room = kcap_or_budget - d.uni_bytes - 4 * d.acap2;
                 d.kcap = std::min(OCT_KEY_CAP, std::max(0, room / 7) & ~63);
@@ -934,7 +915,7 @@ static int plan(orbg_ctx *c, int w, int h, int batch)
         // idle), then the frames past that cap at one workgroup per CU.  ORBG_OCT_L0_WPC=n sets
         // the first launch's workgroups per CU (1: no split).  dims[2] first: level 0's
         // oct_kcap (k_octree's threshold) is the second launch's.
-        const int l0_wpc = getenv("ORBG_OCT_L0_WPC") ? std::max(1, atoi(getenv("ORBG_OCT_L0_WPC"))) : 2;
+        const int l0_wpc = std::max(1, env_int("ORBG_OCT_L0_WPC", 2));
         c->oct_dims[2] = OctLdsDims{};
         if (l0_wpc > 1) {
             c->oct_dims[2] = dims(0, 1, 163840 / l0_wpc - (int)sizeof(OctLdsHdr) - 64, true);
@@ -1007,20 +988,16 @@ static int plan(orbg_ctx *c, int w, int h, int batch)
                      hipMemcpyHostToDevice));
     {
         // k_pyramid (ORBG_PYR=0: the k_resize chain, developer A/B; ORBG_PYR_NB: bands)
-        const char *e = getenv("ORBG_PYR"), *nb = getenv("ORBG_PYR_NB");
         std::vector<uint4> pt;
         std::vector<int4> yt4;
         std::vector<int4> bd;
         PyrArgs A{};
-        // ORBG_PYR_BLUR (A/B): 0 k_blur2 launches, 1 every level blurred inside k_pyramid,
-        // 2 levels >= 1 inside k_pyramid and level 0 by k_blur2 (beside it on the side stream)
-        const char *fb = getenv("ORBG_PYR_BLUR");
         // bands per frame: 4 fill the chip at bench batches; a small batch (the single-frame
         // drop-in) takes 16, the B = 1 optimum (profiles/r04k_single_frame_nband.txt: 4 bands
         // 0.247 ms per extraction, 16 0.229, 32 0.230, 48 0.233)
         const int nb_def = want_batch <= ORBG_SIDE_BLUR_B ? 16 : 4;
-        c->pyr_ok = (!e || atoi(e)) && make_pyr_tables(G, rtab, nb ? atoi(nb) : nb_def, pt, yt4, bd,
-                                                       A, fb ? atoi(fb) : 0);
+        c->pyr_ok = env_int("ORBG_PYR", 1) != 0 &&
+                    make_pyr_tables(G, rtab, env_int("ORBG_PYR_NB", nb_def), pt, yt4, bd, A, pyr_blur);
         if (c->pyr_ok) {
             if ((rc = dalloc(&c->d_ptab, pt.size())) || (rc = dalloc(&c->d_ytab4, yt4.size())) ||
                 (rc = dalloc(&c->d_bands, bd.size()))) {
@@ -1031,8 +1008,7 @@ static int plan(orbg_ctx *c, int w, int h, int batch)
             HIPCHK(hipMemcpy(c->d_ytab4, yt4.data(), yt4.size() * sizeof(int4), hipMemcpyHostToDevice));
             HIPCHK(hipMemcpy(c->d_bands, bd.data(), bd.size() * sizeof(int4), hipMemcpyHostToDevice));
             c->pyr_args = A;
-            const char *wg = getenv("ORBG_PYR_WG");
-            c->pyr_wg = wg ? std::min(std::max(atoi(wg) / 64 * 64, 64), 1024) : 512;
+            c->pyr_wg = std::min(std::max(env_int("ORBG_PYR_WG", 512) / 64 * 64, 64), 1024);
         }
     }
     HIPCHK(hipMemset(c->counts_slot[0], 0, B * sizeof(int32_t)));
@@ -1055,6 +1031,17 @@ static int plan(orbg_ctx *c, int w, int h, int batch)
     c->gbatch = want_batch;
     return ORBG_OK;
 }
+
+// The context's events (all hipEventDisableTiming; what each orders: orbg_ctx.h).  orbg_create
+// creates every one of them, orbg_destroy destroys them.
+static hipEvent_t orbg_ctx::*const ctx_events[] = {
+    &orbg_ctx::ev_fast,  &orbg_ctx::ev_oct,   &orbg_ctx::ev_big_a, &orbg_ctx::ev_big_b,
+    &orbg_ctx::ev_big,   &orbg_ctx::ev_sblur, &orbg_ctx::ev_sback, &orbg_ctx::ev_ssum,
+    &orbg_ctx::ev_srel,  &orbg_ctx::ev_caller};
+static hipEvent_t (orbg_ctx::*const ctx_event_pairs[])[2] = {
+    &orbg_ctx::ev_f0,    &orbg_ctx::ev_b0,    &orbg_ctx::ev_pfork, &orbg_ctx::ev_pyr,
+    &orbg_ctx::ev_rel,   &orbg_ctx::ev_cells, &orbg_ctx::ev_front, &orbg_ctx::ev_back,
+    &orbg_ctx::ev_fork,  &orbg_ctx::ev_join,  &orbg_ctx::ev_ext,   &orbg_ctx::ev_mat};
 
 extern "C" int orbg_create(int device, const orbg_params *p, orbg_ctx **out)
 {
@@ -1097,10 +1084,13 @@ extern "C" int orbg_create(int device, const orbg_params *p, orbg_ctx **out)
     c->device = device;
     c->p = prm;
     make_tables(c);
-    if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) {
-        delete c;
-        return set_err(ORBG_EIO, "hipStreamCreate failed");
-    }
+    // a failure from here on releases what exists so far (orbg_destroy takes a partly built context)
+    auto fail = [c](int code, const char *what) {
+        orbg_destroy(c);
+        return set_err(code, "%s", what);
+    };
+    if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess)
+        return fail(ORBG_EIO, "hipStreamCreate failed");
     c->stream = c->own_stream;
     // sticky device error word {flags, first failing frame / pair}: OR of every launch since
     // it was last read (check_err), so a pipelined caller cannot lose an overflow.  It lives
@@ -1112,12 +1102,8 @@ extern "C" int orbg_create(int device, const orbg_params *p, orbg_ctx **out)
     {
         const int32_t e0[8] = {0, INT32_MAX, 0, 0, 0, 0, 0, 0};
         if (hipMalloc(&c->d_err, sizeof(e0)) != hipSuccess ||
-            hipMemcpy(c->d_err, e0, sizeof(e0), hipMemcpyHostToDevice) != hipSuccess) {
-            if (c->d_err) hipFree(c->d_err);
-            hipStreamDestroy(c->own_stream);
-            delete c;
-            return set_err(ORBG_ENOMEM, "device error word");
-        }
+            hipMemcpy(c->d_err, e0, sizeof(e0), hipMemcpyHostToDevice) != hipSuccess)
+            return fail(ORBG_ENOMEM, "device error word");
     }
     // The matching streams run at low priority: a stream of another priority gets its own
     // hardware queue (at normal priority it can share one with the caller's stream and then
@@ -1131,89 +1117,47 @@ extern "C" int orbg_create(int device, const orbg_params *p, orbg_ctx **out)
         if (!strcmp(e, "normal")) mprio = 0;
         if (!strcmp(e, "high")) mprio = prio_hi;
     }
-    if (hipStreamCreateWithPriority(&c->aux_stream, hipStreamNonBlocking, mprio) != hipSuccess) {
-        hipStreamDestroy(c->own_stream);
-        delete c;
-        return set_err(ORBG_EIO, "hipStreamCreate failed");
-    }
+    if (hipStreamCreateWithPriority(&c->aux_stream, hipStreamNonBlocking, mprio) != hipSuccess)
+        return fail(ORBG_EIO, "hipStreamCreate failed");
     {
-        const char *e = getenv("ORBG_OCT_STREAM");
-        c->oct_mode = e ? atoi(e) : 1;
-        const char *f0 = getenv("ORBG_FAST0");
-        c->fast0_mode = f0 ? atoi(f0) : 1;
-        const char *gm = getenv("ORBG_GRAPH");
-        c->graph_mode = gm ? atoi(gm) : 0;
-        const char *b0 = getenv("ORBG_BLUR0");
-        c->blur0_mode = b0 ? atoi(b0) : 0;
+        c->oct_mode = env_int("ORBG_OCT_STREAM", 1);
+        c->fast0_mode = env_int("ORBG_FAST0", 1);
+        c->graph_mode = env_int("ORBG_GRAPH", 0);
+        c->blur0_mode = env_int("ORBG_BLUR0", 0);
         const char *bp = getenv("ORBG_BACK_PRIO");  // developer A/B: normal | high (default)
         const int oprio = (bp && !strcmp(bp, "normal")) ? 0 : prio_hi;
-        if (c->oct_mode &&
-            hipStreamCreateWithPriority(&c->ostream, hipStreamNonBlocking, oprio) == hipSuccess) {
-            hipEventCreateWithFlags(&c->ev_fast, hipEventDisableTiming);
-            hipEventCreateWithFlags(&c->ev_oct, hipEventDisableTiming);
-        } else {
+        if (!c->oct_mode ||
+            hipStreamCreateWithPriority(&c->ostream, hipStreamNonBlocking, oprio) != hipSuccess) {
             c->ostream = nullptr;
             c->oct_mode = 0;
         }
     }
-    {
-        const char *e = getenv("ORBG_SIDE");
-        c->side_mode = e ? atoi(e) : 1;  // normal priority: 1.596 vs 1.605 ms (high) after k_blur2
-        if (c->side_mode && hipStreamCreateWithPriority(&c->fstream, hipStreamNonBlocking,
-                                                        c->side_mode >= 2 ? prio_hi : 0) != hipSuccess) {
-            c->fstream = nullptr;
-            c->side_mode = 0;
-        }
-        for (int i = 0; i < 2; i++) {
-            hipEventCreateWithFlags(&c->ev_f0[i], hipEventDisableTiming);
-            hipEventCreateWithFlags(&c->ev_b0[i], hipEventDisableTiming);
-            hipEventCreateWithFlags(&c->ev_pfork[i], hipEventDisableTiming);
-            hipEventCreateWithFlags(&c->ev_pyr[i], hipEventDisableTiming);
-        }
-        const char *bs = getenv("ORBG_BLUR_SIDE");
-        c->blur_side = bs ? atoi(bs) != 0 : false;
-        const char *og = getenv("ORBG_OCT_GATE");
-        c->oct_gate = !og || atoi(og) != 0;
-        const char *fb = getenv("ORBG_FAST_BLUR");
-        c->fast_blur_env = fb && atoi(fb) != 0;
-        const char *bt = getenv("ORBG_BLUR_TILED");
-        c->blur_tiled_env = !bt || atoi(bt) != 0;
-        const char *sb = getenv("ORBG_SBLUR");
-        c->sblur = !sb || atoi(sb) != 0;
-        const char *bq = getenv("ORBG_BLUR_Q3");
-        // off: 0.240 against 0.229 ms p50 single frame (r06av: a fourth busy stream past the
-        // four hardware queues shares one with another stream)
-        c->blur_q3 = c->fstream && (bq ? atoi(bq) != 0 : false) &&
-                     hipEventCreateWithFlags(&c->ev_sblur, hipEventDisableTiming) == hipSuccess;
-        const char *bg = getenv("ORBG_BIG_SIDE");
-        c->big_side = c->fstream && (bg ? atoi(bg) != 0 : false);
-        if (c->big_side)
-            for (hipEvent_t *e : {&c->ev_big_a, &c->ev_big_b, &c->ev_big})
-                if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) c->big_side = false;
+    c->side_mode = env_int("ORBG_SIDE", 1);  // normal priority: 1.596 vs 1.605 ms (high) after k_blur2
+    if (c->side_mode && hipStreamCreateWithPriority(&c->fstream, hipStreamNonBlocking,
+                                                    c->side_mode >= 2 ? prio_hi : 0) != hipSuccess) {
+        c->fstream = nullptr;
+        c->side_mode = 0;
     }
-    if (hipStreamCreateWithPriority(&c->mstream, hipStreamNonBlocking, mprio) != hipSuccess) {
-        hipStreamDestroy(c->aux_stream);
-        hipStreamDestroy(c->own_stream);
-        delete c;
-        return set_err(ORBG_EIO, "hipStreamCreate failed");
-    }
-    for (int i = 0; i < 2; i++) {
-        hipEventCreateWithFlags(&c->ev_fork[i], hipEventDisableTiming);
-        hipEventCreateWithFlags(&c->ev_join[i], hipEventDisableTiming);
-        hipEventCreateWithFlags(&c->ev_ext[i], hipEventDisableTiming);
-        hipEventCreateWithFlags(&c->ev_mat[i], hipEventDisableTiming);
-        hipEventCreateWithFlags(&c->ev_cells[i], hipEventDisableTiming);
-        hipEventCreateWithFlags(&c->ev_front[i], hipEventDisableTiming);
-        hipEventCreateWithFlags(&c->ev_back[i], hipEventDisableTiming);
-    }
-    hipEventCreateWithFlags(&c->ev_sback, hipEventDisableTiming);
-    hipEventCreateWithFlags(&c->ev_ssum, hipEventDisableTiming);
-    hipEventCreateWithFlags(&c->ev_rel[0], hipEventDisableTiming);
-    hipEventCreateWithFlags(&c->ev_rel[1], hipEventDisableTiming);
-    hipEventCreateWithFlags(&c->ev_srel, hipEventDisableTiming);
-    hipEventCreateWithFlags(&c->ev_caller, hipEventDisableTiming);
-    if (const char *e = getenv("ORBG_PIPELINE")) c->pipelined = atoi(e) && c->ostream;
-    if (const char *e = getenv("ORBG_FAST_ROWS")) c->fr_mode = atoi(e);
+    c->blur_side = env_int("ORBG_BLUR_SIDE", 0) != 0;
+    c->oct_gate = env_int("ORBG_OCT_GATE", 1) != 0;
+    c->fast_blur_env = env_int("ORBG_FAST_BLUR", 0) != 0;
+    c->blur_tiled_env = env_int("ORBG_BLUR_TILED", 1) != 0;
+    c->sblur = env_int("ORBG_SBLUR", 1) != 0;
+    // off: 0.240 against 0.229 ms p50 single frame (r06av: a fourth busy stream past the
+    // four hardware queues shares one with another stream)
+    c->blur_q3 = c->fstream && env_int("ORBG_BLUR_Q3", 0) != 0;
+    c->big_side = c->fstream && env_int("ORBG_BIG_SIDE", 0) != 0;
+    if (hipStreamCreateWithPriority(&c->mstream, hipStreamNonBlocking, mprio) != hipSuccess)
+        return fail(ORBG_EIO, "hipStreamCreate failed");
+    for (auto m : ctx_events)
+        if (hipEventCreateWithFlags(&(c->*m), hipEventDisableTiming) != hipSuccess)
+            return fail(ORBG_EIO, "hipEventCreate failed");
+    for (auto m : ctx_event_pairs)
+        for (int i = 0; i < 2; i++)
+            if (hipEventCreateWithFlags(&(c->*m)[i], hipEventDisableTiming) != hipSuccess)
+                return fail(ORBG_EIO, "hipEventCreate failed");
+    c->pipelined = env_int("ORBG_PIPELINE", 0) && c->ostream;
+    c->fr_mode = env_int("ORBG_FAST_ROWS", 0);
 #ifdef ORBG_DEV_KNOBS
     if (getenv("ORBG_SKIP") || getenv("ORBG_DBG"))
         fprintf(stderr, "liborbg (developer build): ORBG_SKIP / ORBG_DBG set -- launches are "
@@ -1232,57 +1176,32 @@ extern "C" int orbg_create(int device, const orbg_params *p, orbg_ctx **out)
     return ORBG_OK;
 }
 
+// a context that orbg_create left partly built as well: every member starts null
 extern "C" void orbg_destroy(orbg_ctx *c)
 {
-    if (c && c->h_stage) hipHostFree(c->h_stage);
     if (!c) return;
+    hipSetDevice(c->device);
+    if (c->h_stage) hipHostFree(c->h_stage);
     for (int i = 0; i < 2; i++)
         if (c->gexec[i]) hipGraphExecDestroy(c->gexec[i]);
     if (c->h_gin) hipHostFree(c->h_gin);
     if (c->h_gout) hipHostFree(c->h_gout);
-    hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
     c->prof.collect();
     for (hipEvent_t e : c->prof.pool) hipEventDestroy(e);
-    free_plan(c);
-    if (c->d_img) hipFree(c->d_img);
-    if (c->d_pack) hipFree(c->d_pack);
+    free_plan(c);  // drains the context's own streams
+    for (void *q : {(void *)c->d_img, (void *)c->d_pack, c->d_scr, c->d_trk, c->d_sim3,
+                    (void *)c->d_err, c->d_mpose, (void *)c->d_kps_un})
+        if (q) hipFree(q);
     if (c->h_imz) hipHostFree(c->h_imz);
     if (c->h_zc) hipHostFree(c->h_zc);
-    if (c->d_scr) hipFree(c->d_scr);
-    if (c->d_trk) hipFree(c->d_trk);
-    if (c->d_sim3) hipFree(c->d_sim3);
-    if (c->d_err) hipFree(c->d_err);
-    if (c->d_mpose) hipFree(c->d_mpose);
-    if (c->d_kps_un) hipFree(c->d_kps_un);
-    if (c->aux_stream) hipStreamSynchronize(c->aux_stream);
-    if (c->ostream) hipStreamSynchronize(c->ostream);
-    if (c->mstream) hipStreamSynchronize(c->mstream);
-    for (int i = 0; i < 2; i++) {
-        if (c->ev_fork[i]) hipEventDestroy(c->ev_fork[i]);
-        if (c->ev_join[i]) hipEventDestroy(c->ev_join[i]);
-        if (c->ev_ext[i]) hipEventDestroy(c->ev_ext[i]);
-        if (c->ev_mat[i]) hipEventDestroy(c->ev_mat[i]);
-        if (c->ev_cells[i]) hipEventDestroy(c->ev_cells[i]);
-        if (c->ev_front[i]) hipEventDestroy(c->ev_front[i]);
-        if (c->ev_back[i]) hipEventDestroy(c->ev_back[i]);
-    }
-    if (c->aux_stream) hipStreamDestroy(c->aux_stream);
-    if (c->ostream) hipStreamDestroy(c->ostream);
-    for (int i = 0; i < 2; i++)
-        for (hipEvent_t e : {c->ev_f0[i], c->ev_b0[i], c->ev_pfork[i], c->ev_pyr[i]})
+    for (auto m : ctx_events)
+        if (c->*m) hipEventDestroy(c->*m);
+    for (auto m : ctx_event_pairs)
+        for (hipEvent_t e : c->*m)
             if (e) hipEventDestroy(e);
-    if (c->fstream) hipStreamDestroy(c->fstream);
-    if (c->ev_sblur) hipEventDestroy(c->ev_sblur);
-    for (hipEvent_t e : {c->ev_big_a, c->ev_big_b, c->ev_big})
-        if (e) hipEventDestroy(e);
-    if (c->ev_fast) hipEventDestroy(c->ev_fast);
-    if (c->ev_oct) hipEventDestroy(c->ev_oct);
-    for (hipEvent_t e : {c->ev_sback, c->ev_ssum, c->ev_rel[0], c->ev_rel[1], c->ev_srel,
-                         c->ev_caller})
-        if (e) hipEventDestroy(e);
-    if (c->mstream) hipStreamDestroy(c->mstream);
-    if (c->own_stream) hipStreamDestroy(c->own_stream);
+    for (hipStream_t q : {c->aux_stream, c->ostream, c->fstream, c->mstream, c->own_stream})
+        if (q) hipStreamDestroy(q);
     delete c;
 }
 
@@ -1351,8 +1270,6 @@ static hipError_t launch_pyramid(orbg_ctx *c, hipStream_t st, const uint8_t *d_i
     return hipGetLastError();
 }
 
-// GaussianBlur of levels [l0, l1) of every frame on `st`: k_blur2 (one wave per 244 x SEG
-// output tile, blur_kernels.hip)
 // level 0 of k_octree_lds: a batch's split pair (dims[2] then the frames past its cap at
 // dims[0]), else one launch.  keep_cnt: k_octree runs concurrently (big_side) and owns the
 // lvl_cnt entries of the levels left to it
@@ -1391,6 +1308,20 @@ static hipError_t launch_octree_upper(orbg_ctx *c, int B, hipStream_t st, bool k
                              c->d_lvl_cnt, c->d_err, d);
 }
 
+// k_octree, the fallback quadtree for the levels past k_octree_lds' capacity, on `st`.  gate 1:
+// its workgroups exit at once unless an earlier launch of the batch left a level to them
+// (d_err[2])
+static void launch_octree_big(orbg_ctx *c, int B, hipStream_t st, int gate)
+{
+    PROF_LAUNCH(c, "octree_big",
+                hipLaunchKernelGGL(k_octree, dim3(c->geom.L, B), dim3(ORBG_OCT_THREADS), 0, st,
+                                   c->d_geom, c->d_cell_cnt, c->d_cell_kp, c->d_keys, c->d_knode,
+                                   c->d_act, c->d_qk, c->d_nodes, c->d_lvl_kp, c->d_lvl_idx,
+                                   c->d_lvl_cnt, c->d_err, gate));
+}
+
+// GaussianBlur of levels [l0, l1) of every frame on `st`: k_blur2 (one wave per 244 x SEG
+// output tile, blur_kernels.hip)
 static hipError_t launch_blur_levels(orbg_ctx *c, hipStream_t st, const uint8_t *d_imgs, int B,
                                      int pitch, int64_t fs, int l0, int l1)
 {
@@ -1441,6 +1372,49 @@ static hipError_t launch_fast_cells(orbg_ctx *c, hipStream_t st, const uint8_t *
 static size_t pack_ods(int frame_cap)
 {
     return ORBG_PACK_OKP + (((size_t)frame_cap * sizeof(orbg_keypoint) + 255) & ~(size_t)255);
+}
+
+// The end of a batch on `st`, the stream of its quadtree: the per-frame outputs go to slot s
+// once the slot's last readers are done (the matching of the batch before last, ev_mat; the
+// caller's reads, orbg_batch_release's ev_rel), then k_orient_desc and the batch's events.  A
+// pipelined batch (`piped`) has no zero-copy block and no fallback tag: it passes
+// k_orient_desc's defaults for them, and records ev_back for the next front into its slot.
+static int finish_extract(orbg_ctx *c, hipStream_t st, const uint8_t *d_imgs, int B, int pitch,
+                          int64_t fs, int s, bool piped)
+{
+    const OrbgGeom &G = c->geom;
+    if (c->mat_pending[s]) {
+        HIPCHK(hipStreamWaitEvent(st, c->ev_mat[s], 0));
+        c->mat_pending[s] = false;
+    }
+    if (c->rel_pending[s]) {
+        HIPCHK(hipStreamWaitEvent(st, c->ev_rel[s], 0));
+        c->rel_pending[s] = false;
+    }
+    c->slot = s;
+    c->d_kps = c->kps_slot[s];
+    c->d_desc = c->desc_slot[s];
+    c->d_counts = c->counts_slot[s];
+    uint8_t *hc = piped ? nullptr : c->hc_dst;
+    PROF_LAUNCH(c, "orient_desc",
+                launch_orient_desc(G.brief_fma != 0, G.blur_tiled != 0,
+                                   dim3((G.out_frame + 4 * ORBG_OD_KPW - 1) / (4 * ORBG_OD_KPW) * B),
+                                   st, c->d_geom, d_imgs, fs, pitch, c->d_pyr, c->d_blur,
+                                   c->d_odtab, c->d_lvl_kp, c->d_lvl_idx, c->d_lvl_cnt,
+                                   (OrbgKeypointDev *)c->d_kps, c->d_desc, c->d_counts, hc,
+                                   piped ? nullptr : c->d_err, hc ? ORBG_PACK_OKP : 0,
+                                   hc ? pack_ods(G.frame_cap) : 0, piped ? 0 : c->oct_tag));
+    HIPCHK(hipEventRecord(c->ev_ext[s], st));
+    if (piped) {
+        HIPCHK(hipEventRecord(c->ev_back[s], st));
+        c->back_pending[s] = true;
+    }
+    HIPCHK(hipGetLastError());
+    c->last_img = d_imgs;
+    c->last_fs = fs;
+    c->last_pitch = pitch;
+    c->last_n = B;
+    return ORBG_OK;
 }
 
 // Pipelined batch into slot s (orbg_set_pipeline).  Front on `stream`: resize chain, FAST
@@ -1504,39 +1478,9 @@ static int launch_extract_pipe(orbg_ctx *c, const uint8_t *d_imgs, int B, int pi
     HIPCHK(hipMemsetAsync(c->d_err + 2, 0, sizeof(int32_t), st));
     PROF_LAUNCH(c, "octree", launch_octree_l0(c, B, st));
     if (G.L > 1) PROF_LAUNCH(c, "octree", launch_octree_upper(c, B, st));
-    PROF_LAUNCH(c, "octree_big",
-                hipLaunchKernelGGL(k_octree, dim3(G.L, B), dim3(ORBG_OCT_THREADS), 0, st,
-                                   c->d_geom, c->d_cell_cnt, c->d_cell_kp, c->d_keys, c->d_knode,
-                                   c->d_act, c->d_qk, c->d_nodes, c->d_lvl_kp, c->d_lvl_idx, c->d_lvl_cnt,
-                                   c->d_err, c->oct_gate ? 1 : 0));
+    launch_octree_big(c, B, st, c->oct_gate ? 1 : 0);
     HIPCHK(hipStreamWaitEvent(st, c->ev_front[s], 0));
-    if (c->mat_pending[s]) {  // the matching of the batch before last reads output slot s
-        HIPCHK(hipStreamWaitEvent(st, c->ev_mat[s], 0));
-        c->mat_pending[s] = false;
-    }
-    if (c->rel_pending[s]) {  // ... and so may the caller (orbg_batch_release)
-        HIPCHK(hipStreamWaitEvent(st, c->ev_rel[s], 0));
-        c->rel_pending[s] = false;
-    }
-    c->slot = s;
-    c->d_kps = c->kps_slot[s];
-    c->d_desc = c->desc_slot[s];
-    c->d_counts = c->counts_slot[s];
-    PROF_LAUNCH(c, "orient_desc",
-                launch_orient_desc(G.brief_fma != 0, G.blur_tiled != 0,
-                                   dim3((G.out_frame + 4 * ORBG_OD_KPW - 1) / (4 * ORBG_OD_KPW) * B),
-                                   st, c->d_geom, d_imgs, fs, pitch, c->d_pyr,
-                                   c->d_blur, c->d_odtab, c->d_lvl_kp, c->d_lvl_idx, c->d_lvl_cnt,
-                                   (OrbgKeypointDev *)c->d_kps, c->d_desc, c->d_counts));
-    HIPCHK(hipEventRecord(c->ev_ext[s], st));
-    HIPCHK(hipEventRecord(c->ev_back[s], st));
-    c->back_pending[s] = true;
-    HIPCHK(hipGetLastError());
-    c->last_img = d_imgs;
-    c->last_fs = fs;
-    c->last_pitch = pitch;
-    c->last_n = B;
-    return ORBG_OK;
+    return finish_extract(c, st, d_imgs, B, pitch, fs, s, true);
 }
 
 static int launch_extract(orbg_ctx *c, const uint8_t *d_imgs, int B, int pitch, int64_t fs)
@@ -1607,13 +1551,8 @@ static int launch_extract(orbg_ctx *c, const uint8_t *d_imgs, int B, int pitch, 
             HIPCHK(hipEventRecord(c->ev_big_b, st));
             HIPCHK(hipStreamWaitEvent(c->fstream, c->ev_big_a, 0));
             HIPCHK(hipStreamWaitEvent(c->fstream, c->ev_big_b, 0));
-            hipStream_t st = c->fstream;  // PROF_LAUNCH records on `st`
-            PROF_LAUNCH(c, "octree_big",
-                        hipLaunchKernelGGL(k_octree, dim3(G.L, B), dim3(ORBG_OCT_THREADS), 0, st,
-                                           c->d_geom, c->d_cell_cnt, c->d_cell_kp, c->d_keys,
-                                           c->d_knode, c->d_act, c->d_qk, c->d_nodes, c->d_lvl_kp,
-                                           c->d_lvl_idx, c->d_lvl_cnt, c->d_err, 0));
-            HIPCHK(hipEventRecord(c->ev_big, st));
+            launch_octree_big(c, B, c->fstream, 0);
+            HIPCHK(hipEventRecord(c->ev_big, c->fstream));
         }
     } else {
         HIPCHK(launch_fast(st, 0, G.ncells));
@@ -1657,40 +1596,8 @@ static int launch_extract(orbg_ctx *c, const uint8_t *d_imgs, int B, int pitch, 
     if (big_side)
         HIPCHK(hipStreamWaitEvent(st, c->ev_big, 0));
     else if (!c->skip_big)
-        PROF_LAUNCH(c, "octree_big",
-                    hipLaunchKernelGGL(k_octree, dim3(G.L, B), dim3(ORBG_OCT_THREADS), 0, st,
-                                       c->d_geom, c->d_cell_cnt, c->d_cell_kp, c->d_keys, c->d_knode,
-                                       c->d_act, c->d_qk, c->d_nodes, c->d_lvl_kp, c->d_lvl_idx,
-                                       c->d_lvl_cnt, c->d_err, 0));
-    // per-frame outputs go to the other slot; wait until its last reader (matching of the
-    // batch before last) is done
-    if (c->mat_pending[s]) {
-        HIPCHK(hipStreamWaitEvent(st, c->ev_mat[s], 0));
-        c->mat_pending[s] = false;
-    }
-    if (c->rel_pending[s]) {
-        HIPCHK(hipStreamWaitEvent(st, c->ev_rel[s], 0));
-        c->rel_pending[s] = false;
-    }
-    c->slot = s;
-    c->d_kps = c->kps_slot[s];
-    c->d_desc = c->desc_slot[s];
-    c->d_counts = c->counts_slot[s];
-    PROF_LAUNCH(c, "orient_desc",
-                launch_orient_desc(G.brief_fma != 0, G.blur_tiled != 0,
-                                   dim3((G.out_frame + 4 * ORBG_OD_KPW - 1) / (4 * ORBG_OD_KPW) * B),
-                                   st, c->d_geom, d_imgs, fs, pitch, c->d_pyr,
-                                   c->d_blur, c->d_odtab, c->d_lvl_kp, c->d_lvl_idx, c->d_lvl_cnt, (OrbgKeypointDev *)c->d_kps,
-                                   c->d_desc, c->d_counts,
-                                   c->hc_dst, c->d_err, c->hc_dst ? ORBG_PACK_OKP : 0,
-                                   c->hc_dst ? pack_ods(G.frame_cap) : 0, c->oct_tag));
-    HIPCHK(hipEventRecord(c->ev_ext[s], st));
-    HIPCHK(hipGetLastError());
-    c->last_img = d_imgs;
-    c->last_fs = fs;
-    c->last_pitch = pitch;
-    c->last_n = B;
-    return ORBG_OK;
+        launch_octree_big(c, B, st, 0);
+    return finish_extract(c, st, d_imgs, B, pitch, fs, s, false);
 }
 
 // the single-frame path's latency-critical waits (the frame's extraction, its
@@ -1699,10 +1606,7 @@ static int launch_extract(orbg_ctx *c, const uint8_t *d_imgs, int B, int pitch, 
 // against 0.2296 ms p50, r06aw: the traced gap to the next launch grew), so off by default
 static int spin_sync(hipStream_t st)
 {
-    static const int on = [] {
-        const char *e = getenv("ORBG_SPIN");
-        return e ? atoi(e) : 0;
-    }();
+    static const int on = env_int("ORBG_SPIN", 0);
     if (on) {
         for (;;) {
             const hipError_t e = hipStreamQuery(st);
@@ -2274,7 +2178,7 @@ extern "C" int orbg_batch_stats(orbg_ctx *c, int64_t *ncand, int64_t *nkp)
 }
 
 // `mstream` after everything queued on the context stream so far (ev_caller)
-static hipError_t order_after_caller(orbg_ctx *c)
+hipError_t orbg::order_after_caller(orbg_ctx *c)
 {
     hipError_t e = hipEventRecord(c->ev_caller, c->stream);
     if (e != hipSuccess) return e;
@@ -3685,264 +3589,6 @@ extern "C" int orbg_local_ba_optimize(orbg_ctx *c, orbg_pose *poses, int npose, 
 }
 
 // ---------------------------------------------------------------------------
-// tracking matchers (ORBmatcher::SearchByProjection x 2)
-// ---------------------------------------------------------------------------
-static int track_run(orbg_ctx *c, int mode, const orbg_track_batch *tb, int nframes)
-{
-    if (tb->frame_cap <= 0 || tb->query_cap <= 0 || tb->frame_cap > (1 << 20))
-        return set_err(ORBG_EINVAL, "frame_cap / query_cap out of range");
-    if (!tb->kps || !tb->desc || !tb->counts || !tb->bounds || !tb->queries || !tb->qdesc ||
-        !tb->qcounts || !tb->match || !tb->nmatches)
-        return set_err(ORBG_EINVAL, "NULL device array");
-    if (mode == ORBG_TRACK_LASTFRAME && !tb->cams) return set_err(ORBG_EINVAL, "cams is NULL");
-    if ((mode == ORBG_TRACK_RELOC || mode == ORBG_TRACK_LOOP) && !tb->fcams)
-        return set_err(ORBG_EINVAL, "fcams is NULL");
-    const size_t tk = al256((size_t)nframes * tb->query_cap * ORBG_MATCH_TOPK * 8);
-    const size_t need = tk + al256((size_t)nframes * tb->query_cap * 4);
-    if (c->trk_bytes < need) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->d_trk) hipFree(c->d_trk);
-        c->d_trk = nullptr;
-        c->trk_bytes = 0;
-        if (hipMalloc(&c->d_trk, need) != hipSuccess)
-            return set_err(ORBG_ENOMEM, "track scratch %zu bytes", need);
-        c->trk_bytes = need;
-    }
-    TrackArgs A{};
-    A.kps = tb->kps;
-    A.desc = tb->desc;
-    A.uright = tb->uright;
-    A.taken0 = tb->taken0;
-    A.counts = tb->counts;
-    A.bounds = tb->bounds;
-    A.fc = tb->frame_cap;
-    A.q = tb->queries;
-    A.qdesc = tb->qdesc;
-    A.qcounts = tb->qcounts;
-    A.qc = tb->query_cap;
-    A.cams = tb->cams;
-    for (int l = 0; l < ORBG_MAX_LEVELS; l++)
-        A.scale[l] = l < c->p.nlevels ? c->scale[l] : 1.f;
-    A.th = tb->th;
-    A.nnratio = tb->nnratio;
-    A.check_ori = tb->check_ori;
-    A.topk = (unsigned long long *)c->d_trk;
-    A.topn = (int32_t *)((uint8_t *)c->d_trk + tk);
-    A.match = tb->match;
-    A.nmatches = tb->nmatches;
-    // fcams / orb_dist were appended to orbg_track_batch in round 4: a caller built against
-    // the older header passes the shorter struct, so they are read only in the modes that
-    // define them (ABI notes)
-    if (mode == ORBG_TRACK_RELOC || mode == ORBG_TRACK_LOOP) {
-        A.fcams = tb->fcams;
-        A.orb_dist = tb->orb_dist;
-    }
-    if (mode == ORBG_TRACK_LOOP) A.check_ori = 0;
-    const int rc = launch_track(c->stream, mode, A, nframes, &c->prof);
-    if (rc == ORBG_ENOTSUP)
-        return set_err(rc, "frame_cap %d / query_cap %d exceed the LDS budget", tb->frame_cap,
-                       tb->query_cap);
-    if (rc) return set_err(rc, "track launch failed");
-    return ORBG_OK;
-}
-
-extern "C" int orbg_search_by_projection_batch_device(orbg_ctx *c, int mode,
-                                                      const orbg_track_batch *tb, int nframes)
-{
-    if (!c || !tb) return set_err(ORBG_EINVAL, "NULL argument");
-    if (mode < ORBG_TRACK_LASTFRAME || mode > ORBG_TRACK_LOOP)
-        return set_err(ORBG_EINVAL, "mode %d", mode);
-    if (nframes <= 0) return ORBG_OK;
-    HIPCHK(hipSetDevice(c->device));
-    return track_run(c, mode, tb, nframes);
-}
-
-// one frame from host arrays: upload, run, download
-static int track_host(orbg_ctx *c, int mode, const orbg_keypoint *kps, const uint8_t *desc,
-                      const float *uright, int n, const uint8_t *taken0, const orbg_bounds *bounds,
-                      const void *q, size_t qrec, const uint8_t *qdesc, int nq,
-                      const orbg_track_camera *cam, float th, float nnratio, int check_ori,
-                      int32_t *match, int *nmatches, const orbg_frustum_camera *fcam = nullptr,
-                      int orb_dist = 0)
-{
-    if (!c || !bounds || !match || (n > 0 && (!kps || !desc)) || (nq > 0 && (!q || !qdesc)))
-        return set_err(ORBG_EINVAL, "NULL argument");
-    if (n < 0 || nq < 0) return set_err(ORBG_EINVAL, "negative size");
-    if (mode == ORBG_TRACK_LASTFRAME && !cam) return set_err(ORBG_EINVAL, "cam is NULL");
-    if ((mode == ORBG_TRACK_RELOC || mode == ORBG_TRACK_LOOP) && !fcam)
-        return set_err(ORBG_EINVAL, "cam is NULL");
-    for (int i = 0; i < n; i++) match[i] = -1;
-    if (nmatches) *nmatches = 0;
-    if (n == 0 || nq == 0) return ORBG_OK;
-    HIPCHK(hipSetDevice(c->device));
-    const size_t fc = (size_t)n, qc = (size_t)nq;
-    Layout L;
-    const size_t o_kps = L.take(fc * sizeof(orbg_keypoint)), o_desc = L.take(fc * 32);
-    const size_t o_ur = uright ? L.take(fc * 4) : 0, o_tk = taken0 ? L.take(fc) : 0;
-    const size_t o_cnt = L.take(8), o_b = L.take(sizeof(orbg_bounds)), o_q = L.take(qc * qrec);
-    const size_t o_qd = L.take(qc * 32), o_cam = L.take(sizeof(orbg_track_camera));
-    const size_t o_fcam = L.take(sizeof(orbg_frustum_camera));
-    const size_t o_match = L.take(fc * 4), o_nm = L.take(4);
-    uint8_t *b;
-    int rc = L.device(c, &b);
-    if (rc) return rc;
-    const int32_t cnts[2] = {n, nq};
-    HIPCHK(hipMemcpyAsync(b + o_kps, kps, fc * sizeof(orbg_keypoint), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(b + o_desc, desc, fc * 32, hipMemcpyHostToDevice, c->stream));
-    if (uright) HIPCHK(hipMemcpyAsync(b + o_ur, uright, fc * 4, hipMemcpyHostToDevice, c->stream));
-    if (taken0) HIPCHK(hipMemcpyAsync(b + o_tk, taken0, fc, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(b + o_cnt, cnts, 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(b + o_b, bounds, sizeof(orbg_bounds), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(b + o_q, q, qc * qrec, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(b + o_qd, qdesc, qc * 32, hipMemcpyHostToDevice, c->stream));
-    if (cam)
-        HIPCHK(hipMemcpyAsync(b + o_cam, cam, sizeof(*cam), hipMemcpyHostToDevice, c->stream));
-    if (fcam)
-        HIPCHK(hipMemcpyAsync(b + o_fcam, fcam, sizeof(*fcam), hipMemcpyHostToDevice, c->stream));
-    orbg_track_batch tb{};
-    tb.kps = L.at<orbg_keypoint>(b, o_kps);
-    tb.desc = b + o_desc;
-    tb.uright = uright ? L.at<float>(b, o_ur) : nullptr;
-    tb.taken0 = taken0 ? b + o_tk : nullptr;
-    tb.counts = L.at<int32_t>(b, o_cnt);
-    tb.bounds = L.at<orbg_bounds>(b, o_b);
-    tb.frame_cap = n;
-    tb.queries = b + o_q;
-    tb.qdesc = b + o_qd;
-    tb.qcounts = L.at<int32_t>(b, o_cnt) + 1;
-    tb.query_cap = nq;
-    tb.cams = cam ? L.at<orbg_track_camera>(b, o_cam) : nullptr;
-    tb.th = th;
-    tb.nnratio = nnratio;
-    tb.check_ori = check_ori;
-    tb.match = L.at<int32_t>(b, o_match);
-    tb.nmatches = L.at<int32_t>(b, o_nm);
-    tb.fcams = fcam ? L.at<orbg_frustum_camera>(b, o_fcam) : nullptr;
-    tb.orb_dist = orb_dist;
-    if ((rc = track_run(c, mode, &tb, 1))) return rc;
-    int32_t nm = 0;
-    HIPCHK(hipMemcpyAsync(match, b + o_match, fc * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(&nm, b + o_nm, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    c->prof.collect();
-    if (nmatches) *nmatches = nm;
-    return ORBG_OK;
-}
-
-extern "C" int orbg_search_by_projection_lastframe(orbg_ctx *c, const orbg_keypoint *kps,
-                                                   const uint8_t *desc, const float *uright,
-                                                   int n, const uint8_t *taken0,
-                                                   const orbg_bounds *bounds,
-                                                   const orbg_lastframe_point *pts,
-                                                   const uint8_t *pdesc, int np,
-                                                   const orbg_track_camera *cam, float th,
-                                                   int check_ori, int32_t *match, int *nmatches)
-{
-    return track_host(c, ORBG_TRACK_LASTFRAME, kps, desc, uright, n, taken0, bounds, pts,
-                      sizeof(orbg_lastframe_point), pdesc, np, cam, th, 0.f, check_ori, match,
-                      nmatches);
-}
-
-extern "C" int orbg_search_by_projection_local(orbg_ctx *c, const orbg_keypoint *kps,
-                                               const uint8_t *desc, const float *uright, int n,
-                                               const uint8_t *taken0, const orbg_bounds *bounds,
-                                               const orbg_map_projection *mps,
-                                               const uint8_t *mdesc, int nm, float th,
-                                               float nnratio, int32_t *match, int *nmatches)
-{
-    return track_host(c, ORBG_TRACK_LOCAL, kps, desc, uright, n, taken0, bounds, mps,
-                      sizeof(orbg_map_projection), mdesc, nm, nullptr, th, nnratio, 0, match,
-                      nmatches);
-}
-
-extern "C" int orbg_search_by_projection_reloc(orbg_ctx *c, const orbg_keypoint *kps,
-                                               const uint8_t *desc, int n, const uint8_t *taken0,
-                                               const orbg_frustum_camera *cam,
-                                               const orbg_reloc_point *pts, const uint8_t *pdesc,
-                                               int np, float th, int orb_dist, int check_ori,
-                                               int32_t *match, int *nmatches)
-{
-    if (!cam) return set_err(ORBG_EINVAL, "NULL argument");
-    return track_host(c, ORBG_TRACK_RELOC, kps, desc, nullptr, n, taken0, &cam->bounds, pts,
-                      sizeof(orbg_reloc_point), pdesc, np, nullptr, th, 0.f, check_ori, match,
-                      nmatches, cam, orb_dist);
-}
-
-extern "C" int orbg_search_by_projection_sim3(orbg_ctx *c, const orbg_keypoint *kps,
-                                              const uint8_t *desc, int n, const uint8_t *taken0,
-                                              const orbg_frustum_camera *cam,
-                                              const orbg_map_point *mps, const uint8_t *mdesc,
-                                              int nm, int th, int32_t *match, int *nmatches)
-{
-    if (!cam) return set_err(ORBG_EINVAL, "NULL argument");
-    return track_host(c, ORBG_TRACK_LOOP, kps, desc, nullptr, n, taken0, &cam->bounds, mps,
-                      sizeof(orbg_map_point), mdesc, nm, nullptr, (float)th, 0.f, 0, match,
-                      nmatches, cam, 0);
-}
-
-// ---------------------------------------------------------------------------
-// Optimizer::PoseOptimization
-// ---------------------------------------------------------------------------
-extern "C" int orbg_pose_optimization_batch_device(orbg_ctx *c, const orbg_pose_edge *edges,
-                                                   const int32_t *counts, int edge_cap,
-                                                   const orbg_pose_camera *cams,
-                                                   const float *tcw_in, double *q_out,
-                                                   double *t_out, float *tcw_out,
-                                                   uint8_t *outlier, int32_t *ninliers,
-                                                   int nframes)
-{
-    if (!c) return set_err(ORBG_EINVAL, "ctx is NULL");
-    if (nframes <= 0) return ORBG_OK;
-    if (edge_cap < 0 || !edges || !counts || !cams || !tcw_in || !q_out || !t_out || !tcw_out ||
-        !outlier || !ninliers)
-        return set_err(ORBG_EINVAL, "NULL device array");
-    HIPCHK(hipSetDevice(c->device));
-    const int rc = launch_pose_opt(c->stream, edges, counts, edge_cap, cams, tcw_in, q_out,
-                                   t_out, tcw_out, outlier, ninliers, nframes, &c->prof);
-    return rc ? set_err(rc, "pose optimisation launch failed") : ORBG_OK;
-}
-
-extern "C" int orbg_pose_optimization(orbg_ctx *c, const orbg_pose_edge *edges, int n,
-                                      const orbg_pose_camera *cam, const float tcw_in[12],
-                                      double q_out[4], double t_out[3], float tcw_out[12],
-                                      uint8_t *outlier, int *ninliers)
-{
-    if (!c || !cam || !tcw_in || !q_out || !t_out || !tcw_out || (n > 0 && (!edges || !outlier)))
-        return set_err(ORBG_EINVAL, "NULL argument");
-    if (n < 0) return set_err(ORBG_EINVAL, "negative size");
-    HIPCHK(hipSetDevice(c->device));
-    Layout L;
-    const size_t o_e = L.take((size_t)std::max(n, 1) * sizeof(orbg_pose_edge)), o_n = L.take(4);
-    const size_t o_cam = L.take(sizeof(orbg_pose_camera)), o_tin = L.take(48), o_q = L.take(32);
-    const size_t o_t = L.take(24), o_tout = L.take(48), o_out = L.take((size_t)std::max(n, 1));
-    const size_t o_ni = L.take(4);
-    uint8_t *b;
-    int rc = L.device(c, &b);
-    if (rc) return rc;
-    const int32_t cnt = n;
-    if (n) HIPCHK(hipMemcpyAsync(b + o_e, edges, (size_t)n * sizeof(orbg_pose_edge), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(b + o_n, &cnt, 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(b + o_cam, cam, sizeof(*cam), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(b + o_tin, tcw_in, 48, hipMemcpyHostToDevice, c->stream));
-    if ((rc = launch_pose_opt(c->stream, L.at<orbg_pose_edge>(b, o_e), L.at<int32_t>(b, o_n),
-                              std::max(n, 1), L.at<orbg_pose_camera>(b, o_cam),
-                              L.at<float>(b, o_tin), L.at<double>(b, o_q), L.at<double>(b, o_t),
-                              L.at<float>(b, o_tout), b + o_out, L.at<int32_t>(b, o_ni), 1,
-                              &c->prof)))
-        return set_err(rc, "pose optimisation launch failed");
-    int32_t ni = 0;
-    HIPCHK(hipMemcpyAsync(q_out, b + o_q, 32, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(t_out, b + o_t, 24, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(tcw_out, b + o_tout, 48, hipMemcpyDeviceToHost, c->stream));
-    if (n) HIPCHK(hipMemcpyAsync(outlier, b + o_out, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(&ni, b + o_ni, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    c->prof.collect();
-    if (ninliers) *ninliers = ni;
-    return ORBG_OK;
-}
-
-// ---------------------------------------------------------------------------
 // LocalBundleAdjustment: BlockSolver<6,3>::solve (Schur complement)
 // ---------------------------------------------------------------------------
 extern "C" int orbg_ba_schur_solve(orbg_ctx *c, const orbg_pose *poses, int npose, int npoint,
@@ -4012,713 +3658,6 @@ extern "C" int orbg_ba_schur_solve(orbg_ctx *c, const orbg_pose *poses, int npos
     HIPCHK(hipStreamSynchronize(c->stream));
     c->prof.collect();
     *ok = okv;
-    return ORBG_OK;
-}
-
-// ---------------------------------------------------------------------------
-// DBoW2 vocabulary (TemplatedVocabulary::loadFromTextFile) + transform (Frame::ComputeBoW)
-// ---------------------------------------------------------------------------
-extern "C" int orbg_vocab_create(orbg_ctx *c, int k, int L, int scoring, int weighting,
-                                 int nnodes, const int32_t *parent, const uint8_t *is_leaf,
-                                 const uint8_t *desc, const double *weight, orbg_vocab **out)
-{
-    if (!c || !out) return set_err(ORBG_EINVAL, "NULL argument");
-    *out = nullptr;
-    // header checks of loadFromTextFile (TemplatedVocabulary.h:1359-1363)
-    if (k < 0 || k > 20 || L < 1 || L > 10 || scoring < 0 || scoring > 5 || weighting < 0 ||
-        weighting > 3)
-        return set_err(ORBG_EINVAL, "k %d L %d scoring %d weighting %d outside the text format",
-                       k, L, scoring, weighting);
-    if (nnodes < 1) return set_err(ORBG_EINVAL, "a vocabulary has at least the root node");
-    if (nnodes > 1 && (!parent || !is_leaf || !desc || !weight))
-        return set_err(ORBG_EINVAL, "NULL node array");
-    std::vector<int32_t> off(nnodes + 1, 0), word(nnodes, 0);
-    int nwords = 0;
-    for (int i = 1; i < nnodes; i++) {
-        if (parent[i] < 0 || parent[i] >= i)
-            return set_err(ORBG_EINVAL, "node %d: parent %d is not an earlier node", i, parent[i]);
-        off[parent[i] + 1]++;
-        if (is_leaf[i]) word[i] = nwords++;
-    }
-    int maxc = 0;
-    for (int i = 0; i < nnodes; i++) {
-        maxc = std::max(maxc, off[i + 1]);
-        off[i + 1] += off[i];
-    }
-    if (maxc > 64) return set_err(ORBG_ENOTSUP, "a node with %d children (> 64)", maxc);
-    std::vector<BowSlot> slots(std::max(nnodes - 1, 1));
-    std::vector<int32_t> fill(off.begin(), off.end() - 1);
-    for (int i = 1; i < nnodes; i++) {  // children in node (file) order
-        BowSlot &s = slots[fill[parent[i]]++];
-        memset(&s, 0, sizeof(s));
-        memcpy(s.d, desc + (size_t)i * 32, 32);
-        s.c0 = off[i];
-        s.c1 = off[i + 1];
-        s.node = i;
-        s.word = word[i];
-        s.weight = weight[i];
-    }
-    auto *v = new orbg_vocab();
-    v->device = c->device;
-    v->k = k;
-    v->L = L;
-    v->scoring = scoring;
-    v->weighting = weighting;
-    v->nnodes = nnodes;
-    v->nwords = nwords;
-    v->group = maxc <= 16 ? 16 : maxc <= 32 ? 32 : 64;
-    v->root_c0 = off[0];
-    v->root_c1 = off[1];
-    hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = hipMalloc(&v->d_slots, slots.size() * sizeof(BowSlot));
-    if (e == hipSuccess)
-        e = hipMemcpy(v->d_slots, slots.data(), slots.size() * sizeof(BowSlot), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (v->d_slots) hipFree(v->d_slots);
-        delete v;
-        return set_err(ORBG_ENOMEM, "vocabulary upload: %s", hipGetErrorString(e));
-    }
-    *out = v;
-    return ORBG_OK;
-}
-
-extern "C" int orbg_vocab_load_text(orbg_ctx *c, const char *path, orbg_vocab **out)
-{
-    if (!c || !path || !out) return set_err(ORBG_EINVAL, "NULL argument");
-    FILE *fp = fopen(path, "r");
-    if (!fp) return set_err(ORBG_EINVAL, "cannot open %s", path);
-    char *line = nullptr;
-    size_t cap = 0;
-    int k = 0, L = 0, n1 = 0, n2 = 0, rc = ORBG_OK;
-    std::vector<int32_t> parent(1, 0);
-    std::vector<uint8_t> leaf(1, 0), desc(32, 0);
-    std::vector<double> weight(1, 0.0);
-    if (getline(&line, &cap, fp) < 0 || sscanf(line, "%d %d %d %d", &k, &L, &n1, &n2) != 4) {
-        rc = set_err(ORBG_EINVAL, "%s: missing header line", path);
-    } else {
-        long lineno = 1;
-        while (getline(&line, &cap, fp) >= 0) {
-            lineno++;
-            char *p = line, *e;
-            while (*p == ' ' || *p == '\t' || *p == '\r' || *p == '\n') p++;
-            if (!*p) continue;  // blank line
-            long vals[34];
-            int nv = 0;
-            for (; nv < 34; nv++) {
-                vals[nv] = strtol(p, &e, 10);
-                if (e == p) break;
-                p = e;
-            }
-            const double w = strtod(p, &e);
-            if (nv < 34 || e == p) {
-                rc = set_err(ORBG_EINVAL, "%s:%ld: expected parent isLeaf 32 bytes weight", path,
-                             lineno);
-                break;
-            }
-            parent.push_back((int32_t)vals[0]);
-            leaf.push_back(vals[1] > 0);
-            for (int j = 0; j < 32; j++) desc.push_back((uint8_t)vals[2 + j]);
-            weight.push_back(w);
-        }
-    }
-    free(line);
-    fclose(fp);
-    if (rc) return rc;
-    return orbg_vocab_create(c, k, L, n1, n2, (int)parent.size(), parent.data(), leaf.data(),
-                             desc.data(), weight.data(), out);
-}
-
-extern "C" void orbg_vocab_destroy(orbg_vocab *v)
-{
-    if (!v) return;
-    if (v->d_slots) {
-        hipSetDevice(v->device);
-        hipFree(v->d_slots);
-    }
-    delete v;
-}
-
-extern "C" int orbg_vocab_info(const orbg_vocab *v, int32_t *k, int32_t *L, int32_t *scoring,
-                               int32_t *weighting, int32_t *nnodes, int32_t *nwords)
-{
-    if (!v) return set_err(ORBG_EINVAL, "vocabulary is NULL");
-    if (k) *k = v->k;
-    if (L) *L = v->L;
-    if (scoring) *scoring = v->scoring;
-    if (weighting) *weighting = v->weighting;
-    if (nnodes) *nnodes = v->nnodes;
-    if (nwords) *nwords = v->nwords;
-    return ORBG_OK;
-}
-
-#define ORBG_BOW_MAX_CAP 8192   // k_bow_vectors sorts a frame's keys in LDS
-
-static BowArgs bow_args(const orbg_vocab *v, int levelsup)
-{
-    BowArgs A{};
-    A.slots = v->d_slots;
-    A.root_c0 = v->root_c0;
-    A.root_c1 = v->root_c1;
-    A.group = v->group;
-    A.nid_level = v->L - levelsup;
-    A.scoring = v->scoring;
-    A.weighting = v->weighting;
-    A.empty = v->nwords == 0;
-    return A;
-}
-
-extern "C" int orbg_bow_transform_batch_device(orbg_ctx *c, const orbg_vocab *v,
-                                               const uint8_t *desc, const int32_t *counts,
-                                               int cap, int nframes, int levelsup,
-                                               int32_t *bow_words, double *bow_weights,
-                                               int32_t *nbow, int32_t *fv_nodes,
-                                               int32_t *fv_off, int32_t *fv_feats, int32_t *nfv,
-                                               int32_t *word_of, int32_t *node_of)
-{
-    if (!c || !v) return set_err(ORBG_EINVAL, "NULL context or vocabulary");
-    if (v->device != c->device) return set_err(ORBG_EINVAL, "vocabulary lives on another device");
-    if (nframes <= 0) return ORBG_OK;
-    if (cap < 1 || cap > ORBG_BOW_MAX_CAP)
-        return set_err(ORBG_ENOTSUP, "cap %d outside 1..%d", cap, ORBG_BOW_MAX_CAP);
-    if (!desc || !counts || !bow_words || !bow_weights || !nbow || !fv_nodes || !fv_off ||
-        !fv_feats || !nfv)
-        return set_err(ORBG_EINVAL, "NULL device array");
-    HIPCHK(hipSetDevice(c->device));
-    const size_t per = (size_t)nframes * cap;
-    const size_t o_w = 0, o_n = al256(per * 4), o_x = o_n + al256(per * 4);
-    void *s;
-    int rc = scratch(c, o_x + al256(per * 8), &s);
-    if (rc) return rc;
-    BowArgs A = bow_args(v, levelsup);
-    A.desc = desc;
-    A.counts = counts;
-    A.cap = cap;
-    A.nframes = nframes;
-    A.fword = word_of ? word_of : (int32_t *)((uint8_t *)s + o_w);
-    A.fnode = node_of ? node_of : (int32_t *)((uint8_t *)s + o_n);
-    A.fweight = (double *)((uint8_t *)s + o_x);
-    A.bow_words = bow_words;
-    A.bow_weights = bow_weights;
-    A.nbow = nbow;
-    A.fv_nodes = fv_nodes;
-    A.fv_off = fv_off;
-    A.fv_feats = fv_feats;
-    A.nfv = nfv;
-    if ((rc = launch_bow(c->stream, A, &c->prof))) return set_err(rc, "bow launch failed");
-    return ORBG_OK;
-}
-
-extern "C" int orbg_bow_transform(orbg_ctx *c, const orbg_vocab *v, const uint8_t *desc, int n,
-                                  int levelsup, int32_t *bow_words, double *bow_weights,
-                                  int *nbow, int32_t *fv_nodes, int32_t *fv_off,
-                                  int32_t *fv_feats, int *nfv)
-{
-    if (!c || !v || !nbow || !nfv || !fv_off) return set_err(ORBG_EINVAL, "NULL argument");
-    if (n < 0) return set_err(ORBG_EINVAL, "negative size");
-    if (n > ORBG_BOW_MAX_CAP) return set_err(ORBG_ENOTSUP, "%d descriptors (> %d)", n, ORBG_BOW_MAX_CAP);
-    if (n > 0 && (!desc || !bow_words || !bow_weights || !fv_nodes || !fv_feats))
-        return set_err(ORBG_EINVAL, "NULL array");
-    *nbow = *nfv = 0;
-    fv_off[0] = 0;
-    if (n == 0) return ORBG_OK;
-    HIPCHK(hipSetDevice(c->device));
-    Layout L;
-    const size_t o_d = L.take((size_t)n * 32), o_c = L.take(4), o_fw = L.take((size_t)n * 4);
-    const size_t o_fn = L.take((size_t)n * 4), o_fx = L.take((size_t)n * 8);
-    const size_t o_bw = L.take((size_t)n * 4), o_bx = L.take((size_t)n * 8), o_nb = L.take(4);
-    const size_t o_vn = L.take((size_t)n * 4), o_vo = L.take((size_t)(n + 1) * 4);
-    const size_t o_vf = L.take((size_t)n * 4), o_nf = L.take(4);
-    uint8_t *b;
-    int rc = L.device(c, &b);
-    if (rc) return rc;
-    const int32_t cnt = n;
-    HIPCHK(hipMemcpyAsync(b + o_d, desc, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(b + o_c, &cnt, 4, hipMemcpyHostToDevice, c->stream));
-    BowArgs A = bow_args(v, levelsup);
-    A.desc = b + o_d;
-    A.counts = L.at<int32_t>(b, o_c);
-    A.cap = n;
-    A.nframes = 1;
-    A.fword = L.at<int32_t>(b, o_fw);
-    A.fnode = L.at<int32_t>(b, o_fn);
-    A.fweight = L.at<double>(b, o_fx);
-    A.bow_words = L.at<int32_t>(b, o_bw);
-    A.bow_weights = L.at<double>(b, o_bx);
-    A.nbow = L.at<int32_t>(b, o_nb);
-    A.fv_nodes = L.at<int32_t>(b, o_vn);
-    A.fv_off = L.at<int32_t>(b, o_vo);
-    A.fv_feats = L.at<int32_t>(b, o_vf);
-    A.nfv = L.at<int32_t>(b, o_nf);
-    if ((rc = launch_bow(c->stream, A, &c->prof))) return set_err(rc, "bow launch failed");
-    int32_t nb = 0, nf = 0;
-    HIPCHK(hipMemcpyAsync(&nb, b + o_nb, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(&nf, b + o_nf, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    // outputs are at most n long; copy what was produced
-    HIPCHK(hipMemcpyAsync(bow_words, b + o_bw, (size_t)nb * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(bow_weights, b + o_bx, (size_t)nb * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(fv_nodes, b + o_vn, (size_t)nf * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(fv_off, b + o_vo, (size_t)(nf + 1) * 4, hipMemcpyDeviceToHost, c->stream));
-    int32_t m = 0;
-    HIPCHK(hipMemcpyAsync(&m, b + o_vo + (size_t)nf * 4, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (m) HIPCHK(hipMemcpy(fv_feats, b + o_vf, (size_t)m * 4, hipMemcpyDeviceToHost));
-    c->prof.collect();
-    *nbow = nb;
-    *nfv = nf;
-    return ORBG_OK;
-}
-
-// ---------------------------------------------------------------------------
-// ORBmatcher::SearchByBoW(KeyFrame*, Frame&) (bow_match_kernels.hip)
-// ---------------------------------------------------------------------------
-extern "C" int orbg_search_by_bow_kf_batch_device(orbg_ctx *c, const orbg_bow_frames *kf1,
-                                                  const orbg_bow_frames *kf2, int cap,
-                                                  const int32_t *d_kf1_index,
-                                                  const int32_t *d_kf2_index, int npairs,
-                                                  float nnratio, int check_ori,
-                                                  int32_t *d_match12, int32_t *d_nmatch)
-{
-    if (!c || !kf1 || !kf2) return set_err(ORBG_EINVAL, "NULL argument");
-    if (npairs < 0 || cap <= 0 || cap > 8192) return set_err(ORBG_EINVAL, "bad npairs / cap");
-    if (npairs == 0) return ORBG_OK;
-    if (!d_kf1_index || !d_kf2_index || !d_match12 || !d_nmatch || !kf1->desc || !kf1->kps ||
-        !kf1->counts || !kf1->fv_nodes || !kf1->fv_off || !kf1->fv_feats || !kf1->nfv ||
-        !kf2->desc || !kf2->kps || !kf2->fv_nodes || !kf2->fv_off || !kf2->fv_feats || !kf2->nfv)
-        return set_err(ORBG_EINVAL, "NULL device array");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(order_after_caller(c));
-    hipStream_t st = c->mstream;  // PROF_LAUNCH records on `st`
-    int rc = 0;
-    PROF_LAUNCH(c, "bow_match_kf",
-                rc = launch_bow_match(st, *kf1, *kf2, cap, d_kf1_index, d_kf2_index, npairs,
-                                      nnratio, check_ori, d_match12, d_nmatch, true));
-    if (rc == ORBG_ENOTSUP) return set_err(ORBG_ENOTSUP, "SearchByBoW: more than 4096 features per frame");
-    if (rc) return set_err(ORBG_EIO, "k_bow_match launch failed");
-    return ORBG_OK;
-}
-
-extern "C" int orbg_search_by_bow_batch_device(orbg_ctx *c, const orbg_bow_frames *kf,
-                                               const orbg_bow_frames *f, int cap,
-                                               const int32_t *d_kf_index, const int32_t *d_f_index,
-                                               int npairs, float nnratio, int check_ori,
-                                               int32_t *d_match, int32_t *d_nmatch)
-{
-    if (!c || !kf || !f) return set_err(ORBG_EINVAL, "NULL argument");
-    if (npairs < 0 || cap <= 0 || cap > 8192) return set_err(ORBG_EINVAL, "bad npairs / cap");
-    if (npairs == 0) return ORBG_OK;
-    if (!d_kf_index || !d_f_index || !d_match || !d_nmatch || !kf->desc || !kf->kps ||
-        !kf->fv_nodes || !kf->fv_off || !kf->fv_feats || !kf->nfv || !f->desc || !f->kps ||
-        !f->counts || !f->fv_nodes || !f->fv_off || !f->fv_feats || !f->nfv)
-        return set_err(ORBG_EINVAL, "NULL device array");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(order_after_caller(c));
-    hipStream_t st = c->mstream;  // PROF_LAUNCH records on `st`
-    int rc = 0;
-    PROF_LAUNCH(c, "bow_match",
-                rc = launch_bow_match(st, *kf, *f, cap, d_kf_index, d_f_index, npairs, nnratio,
-                                      check_ori, d_match, d_nmatch));
-    if (rc == ORBG_ENOTSUP) return set_err(ORBG_ENOTSUP, "SearchByBoW: more than 4096 features per frame");
-    if (rc) return set_err(ORBG_EIO, "k_bow_match launch failed");
-    return ORBG_OK;
-}
-
-static int search_by_bow_host(orbg_ctx *c, const uint8_t *kf_desc, const float *kf_angle,
-                                  const uint8_t *kf_valid, int n_kf, const int32_t *kf_fv_nodes,
-                                  const int32_t *kf_fv_off, const int32_t *kf_fv_feats, int kf_nfv,
-                                  const uint8_t *f_desc, const float *f_angle,
-                                  const uint8_t *f_valid, int n_f,
-                                  const int32_t *f_fv_nodes, const int32_t *f_fv_off,
-                                  const int32_t *f_fv_feats, int f_nfv, float nnratio,
-                                  int check_ori, int32_t *match, int *nmatches, bool kfkf)
-{
-    const int n_out = kfkf ? n_kf : n_f;  // KeyFrame-KeyFrame: vpMatches12 over pKF1
-    if (!c || !match || !nmatches) return set_err(ORBG_EINVAL, "NULL argument");
-    if (n_kf < 0 || n_f < 0 || kf_nfv < 0 || f_nfv < 0 || kf_nfv > std::max(n_kf, 0) ||
-        f_nfv > std::max(n_f, 0))
-        return set_err(ORBG_EINVAL, "bad sizes");
-    if ((n_kf && (!kf_desc || !kf_angle)) || (n_f && (!f_desc || !f_angle)) ||
-        (kf_nfv && (!kf_fv_nodes || !kf_fv_off || !kf_fv_feats)) ||
-        (f_nfv && (!f_fv_nodes || !f_fv_off || !f_fv_feats)))
-        return set_err(ORBG_EINVAL, "NULL input array");
-    *nmatches = 0;
-    for (int i = 0; i < n_out; i++) match[i] = -1;
-    if (!n_f || !n_kf || !kf_nfv || !f_nfv) return ORBG_OK;
-    for (int j = 0; j < kf_nfv; j++)
-        for (int k = kf_fv_off[j]; k < kf_fv_off[j + 1]; k++)
-            if (kf_fv_feats[k] < 0 || kf_fv_feats[k] >= n_kf)
-                return set_err(ORBG_EINVAL, "KF feature index out of range");
-    for (int j = 0; j < f_nfv; j++)
-        for (int k = f_fv_off[j]; k < f_fv_off[j + 1]; k++)
-            if (f_fv_feats[k] < 0 || f_fv_feats[k] >= n_f)
-                return set_err(ORBG_EINVAL, "F feature index out of range");
-    HIPCHK(hipSetDevice(c->device));
-    // one buffer: two frames (KF = 0, F = 1) at cap = max(n_kf, n_f)
-    const int cap = std::max(n_kf, n_f);
-    if (cap > 8192) return set_err(ORBG_ENOTSUP, "more than 8192 features");
-    const size_t cp = (size_t)cap;
-    Layout L;
-    const size_t o_desc = L.take(2 * cp * 32), o_kps = L.take(2 * cp * sizeof(orbg_keypoint)),
-                 o_cnt = L.take(2 * 4), o_nodes = L.take(2 * cp * 4), o_off = L.take(2 * (cp + 1) * 4),
-                 o_feats = L.take(2 * cp * 4), o_nfv = L.take(2 * 4), o_val = L.take(2 * cp),
-                 o_idx = L.take(2 * 4), o_match = L.take(cp * 4), o_nm = L.take(4);
-    uint8_t *hs, *db;
-    int rc = L.host(c, &hs);
-    if (rc) return rc;
-    memset(hs, 0, L.total());
-    memcpy(hs + o_desc, kf_desc, (size_t)n_kf * 32);
-    memcpy(hs + o_desc + cp * 32, f_desc, (size_t)n_f * 32);
-    orbg_keypoint *hk = L.at<orbg_keypoint>(hs, o_kps);
-    for (int i = 0; i < n_kf; i++) hk[i].angle = kf_angle[i];
-    for (int i = 0; i < n_f; i++) hk[cp + i].angle = f_angle[i];
-    int32_t *hc = L.at<int32_t>(hs, o_cnt);
-    hc[0] = n_kf;
-    hc[1] = n_f;
-    memcpy(hs + o_nodes, kf_fv_nodes, (size_t)kf_nfv * 4);
-    memcpy(hs + o_nodes + cp * 4, f_fv_nodes, (size_t)f_nfv * 4);
-    memcpy(hs + o_off, kf_fv_off, (size_t)(kf_nfv + 1) * 4);
-    memcpy(hs + o_off + (cp + 1) * 4, f_fv_off, (size_t)(f_nfv + 1) * 4);
-    memcpy(hs + o_feats, kf_fv_feats, (size_t)kf_fv_off[kf_nfv] * 4);
-    memcpy(hs + o_feats + cp * 4, f_fv_feats, (size_t)f_fv_off[f_nfv] * 4);
-    int32_t *hn = L.at<int32_t>(hs, o_nfv);
-    hn[0] = kf_nfv;
-    hn[1] = f_nfv;
-    if (kf_valid)
-        memcpy(hs + o_val, kf_valid, (size_t)n_kf);
-    else
-        memset(hs + o_val, 1, (size_t)n_kf);
-    if (f_valid)
-        memcpy(hs + o_val + cp, f_valid, (size_t)n_f);
-    else
-        memset(hs + o_val + cp, 1, (size_t)n_f);
-    int32_t *hi = L.at<int32_t>(hs, o_idx);
-    hi[0] = 0;
-    hi[1] = 1;
-    if ((rc = L.device(c, &db))) return rc;
-    HIPCHK(hipMemcpyAsync(db, hs, L.total(), hipMemcpyHostToDevice, c->stream));
-    orbg_bow_frames K{}, F{};
-    K.desc = F.desc = db + o_desc;
-    K.kps = F.kps = L.at<orbg_keypoint>(db, o_kps);
-    K.counts = F.counts = L.at<int32_t>(db, o_cnt);
-    K.fv_nodes = F.fv_nodes = L.at<int32_t>(db, o_nodes);
-    K.fv_off = F.fv_off = L.at<int32_t>(db, o_off);
-    K.fv_feats = F.fv_feats = L.at<int32_t>(db, o_feats);
-    K.nfv = F.nfv = L.at<int32_t>(db, o_nfv);
-    K.valid = F.valid = db + o_val;  // frame 0 (KF / pKF1) and frame 1 (F / pKF2) at + cap
-    const int32_t *di = L.at<int32_t>(db, o_idx);
-    rc = launch_bow_match(c->stream, K, F, cap, di, di + 1, 1, nnratio, check_ori,
-                          L.at<int32_t>(db, o_match), L.at<int32_t>(db, o_nm), kfkf);
-    if (rc == ORBG_ENOTSUP) return set_err(ORBG_ENOTSUP, "SearchByBoW: more than 4096 features per frame");
-    if (rc) return set_err(ORBG_EIO, "k_bow_match launch failed");
-    HIPCHK(hipMemcpyAsync(hs + o_match, db + o_match, cp * 4 + 256, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    memcpy(match, hs + o_match, (size_t)n_out * 4);
-    memcpy(nmatches, hs + o_nm, 4);
-    return ORBG_OK;
-}
-
-extern "C" int orbg_search_by_bow(orbg_ctx *c, const uint8_t *kf_desc, const float *kf_angle,
-                                  const uint8_t *kf_valid, int n_kf, const int32_t *kf_fv_nodes,
-                                  const int32_t *kf_fv_off, const int32_t *kf_fv_feats, int kf_nfv,
-                                  const uint8_t *f_desc, const float *f_angle, int n_f,
-                                  const int32_t *f_fv_nodes, const int32_t *f_fv_off,
-                                  const int32_t *f_fv_feats, int f_nfv, float nnratio,
-                                  int check_ori, int32_t *match, int *nmatches)
-{
-    return search_by_bow_host(c, kf_desc, kf_angle, kf_valid, n_kf, kf_fv_nodes, kf_fv_off,
-                              kf_fv_feats, kf_nfv, f_desc, f_angle, nullptr, n_f, f_fv_nodes,
-                              f_fv_off, f_fv_feats, f_nfv, nnratio, check_ori, match, nmatches,
-                              false);
-}
-
-extern "C" int orbg_search_by_bow_kf(orbg_ctx *c, const uint8_t *desc1, const float *angle1,
-                                     const uint8_t *valid1, int n1, const int32_t *fv_nodes1,
-                                     const int32_t *fv_off1, const int32_t *fv_feats1, int nfv1,
-                                     const uint8_t *desc2, const float *angle2,
-                                     const uint8_t *valid2, int n2, const int32_t *fv_nodes2,
-                                     const int32_t *fv_off2, const int32_t *fv_feats2, int nfv2,
-                                     float nnratio, int check_ori, int32_t *match12,
-                                     int *nmatches)
-{
-    return search_by_bow_host(c, desc1, angle1, valid1, n1, fv_nodes1, fv_off1, fv_feats1, nfv1,
-                              desc2, angle2, valid2, n2, fv_nodes2, fv_off2, fv_feats2, nfv2,
-                              nnratio, check_ori, match12, nmatches, true);
-}
-
-// ---------------------------------------------------------------------------
-// Frame / MapPoint geometry (frame_kernels.hip)
-// ---------------------------------------------------------------------------
-static bool cam_ok(const orbg_camera *cam)
-{
-    return cam && std::isfinite(cam->fx) && std::isfinite(cam->fy) && cam->fx != 0.f &&
-           cam->fy != 0.f;
-}
-
-extern "C" int orbg_compute_image_bounds(const orbg_camera *cam, int w, int h, orbg_bounds *out)
-{
-    if (!cam || !out) return set_err(ORBG_EINVAL, "NULL argument");
-    if (w < 0 || h < 0) return set_err(ORBG_EINVAL, "negative image size");
-    if (cam->k1 != 0.0f) {
-        if (!cam_ok(cam)) return set_err(ORBG_EINVAL, "fx / fy must be finite and nonzero");
-        // the corners (0,0), (cols,0), (0,rows), (cols,rows), Frame.cc:579-600
-        float o[8];
-        const float in[8] = {0.f, 0.f, (float)w, 0.f, 0.f, (float)h, (float)w, (float)h};
-        for (int i = 0; i < 4; i++) orbg::undistort_point(*cam, in[2 * i], in[2 * i + 1], &o[2 * i], &o[2 * i + 1]);
-        out->min_x = std::min(o[0], o[4]);
-        out->max_x = std::max(o[2], o[6]);
-        out->min_y = std::min(o[1], o[3]);
-        out->max_y = std::max(o[5], o[7]);
-    } else {
-        out->min_x = 0.0f;
-        out->max_x = (float)w;
-        out->min_y = 0.0f;
-        out->max_y = (float)h;
-    }
-    return ORBG_OK;
-}
-
-extern "C" int orbg_set_camera(orbg_ctx *c, const orbg_camera *cam)
-{
-    if (!c) return set_err(ORBG_EINVAL, "NULL context");
-    if (cam && cam->k1 != 0.0f && !cam_ok(cam))
-        return set_err(ORBG_EINVAL, "fx / fy must be finite and nonzero");
-    c->has_cam = cam && cam->k1 != 0.0f;
-    if (cam) c->cam = *cam;
-    return ORBG_OK;
-}
-
-extern "C" int orbg_batch_keys_un(orbg_ctx *c, orbg_keypoint **d_kps_un, int32_t *frame_cap)
-{
-    if (!c || !d_kps_un) return set_err(ORBG_EINVAL, "NULL argument");
-    if (!c->gw || c->last_n <= 0) return set_err(ORBG_EINVAL, "no batch extracted");
-    *d_kps_un = c->kps_un_valid ? c->d_kps_un : c->d_kps;
-    if (frame_cap) *frame_cap = c->geom.frame_cap;
-    return ORBG_OK;
-}
-
-extern "C" int orbg_undistort_batch_device(orbg_ctx *c, const orbg_camera *cam,
-                                           const orbg_keypoint *d_kps, const int32_t *d_counts,
-                                           int frame_cap, int nframes, orbg_keypoint *d_kps_un)
-{
-    if (!c || !cam) return set_err(ORBG_EINVAL, "NULL argument");
-    if (nframes < 0 || frame_cap < 0) return set_err(ORBG_EINVAL, "negative size");
-    if (nframes == 0 || frame_cap == 0) return ORBG_OK;
-    if (!d_kps || !d_counts || !d_kps_un) return set_err(ORBG_EINVAL, "NULL device array");
-    if (cam->k1 != 0.0f && !cam_ok(cam)) return set_err(ORBG_EINVAL, "fx / fy must be finite and nonzero");
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    int rc = 0;
-    PROF_LAUNCH(c, "undistort",
-                rc = launch_undistort(st, *cam, d_kps, d_counts, frame_cap, nframes, d_kps_un));
-    if (rc) return set_err(ORBG_EIO, "k_undistort launch failed");
-    return ORBG_OK;
-}
-
-extern "C" int orbg_rgbd_stereo_batch_device(orbg_ctx *c, const void *d_depth, int depth_type,
-                                             float factor, int w, int h, size_t pitch,
-                                             size_t image_stride, const orbg_keypoint *d_kps,
-                                             const orbg_keypoint *d_kps_un,
-                                             const int32_t *d_counts, int frame_cap, int nframes,
-                                             float mbf, float *d_uright, float *d_depth_out)
-{
-    if (!c) return set_err(ORBG_EINVAL, "NULL argument");
-    if (depth_type != ORBG_DEPTH_F32 && depth_type != ORBG_DEPTH_U16)
-        return set_err(ORBG_EINVAL, "depth_type %d", depth_type);
-    if (nframes < 0 || frame_cap < 0 || w < 0 || h < 0) return set_err(ORBG_EINVAL, "negative size");
-    if (nframes == 0 || frame_cap == 0) return ORBG_OK;
-    const size_t px = depth_type == ORBG_DEPTH_U16 ? 2 : 4;
-    if (pitch < (size_t)w * px) return set_err(ORBG_EINVAL, "pitch below the row width");
-    if (nframes > 1 && image_stride < pitch * (size_t)h)
-        return set_err(ORBG_EINVAL, "image_stride below one image");
-    if (!d_depth || !d_kps || !d_kps_un || !d_counts || !d_uright || !d_depth_out)
-        return set_err(ORBG_EINVAL, "NULL device array");
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    int rc = 0;
-    PROF_LAUNCH(c, "rgbd",
-                rc = launch_rgbd(st, d_depth, depth_type == ORBG_DEPTH_U16, factor, w, h, pitch,
-                                 image_stride, d_kps, d_kps_un, d_counts, frame_cap, nframes, mbf,
-                                 d_uright, d_depth_out));
-    if (rc) return set_err(ORBG_EIO, "k_rgbd launch failed");
-    return ORBG_OK;
-}
-
-extern "C" int orbg_rgbd_stereo(orbg_ctx *c, const void *depth, int depth_type, float factor,
-                                int w, int h, size_t pitch, const orbg_keypoint *kps,
-                                const orbg_keypoint *kps_un, int n, float mbf, float *uright,
-                                float *depth_out)
-{
-    if (!c) return set_err(ORBG_EINVAL, "NULL argument");
-    if (depth_type != ORBG_DEPTH_F32 && depth_type != ORBG_DEPTH_U16)
-        return set_err(ORBG_EINVAL, "depth_type %d", depth_type);
-    if (n < 0 || w < 0 || h < 0) return set_err(ORBG_EINVAL, "negative size");
-    if (n == 0) return ORBG_OK;
-    if (!depth || !kps || !kps_un || !uright || !depth_out) return set_err(ORBG_EINVAL, "NULL array");
-    const size_t px = depth_type == ORBG_DEPTH_U16 ? 2 : 4;
-    if (pitch < (size_t)w * px) return set_err(ORBG_EINVAL, "pitch below the row width");
-    HIPCHK(hipSetDevice(c->device));
-    // only the keypoints' pixels are read: upload the image rows once (w x h), packed
-    Layout L;
-    const size_t o_img = L.take((size_t)w * px * h), o_k = L.take((size_t)n * sizeof(orbg_keypoint)),
-                 o_ku = L.take((size_t)n * sizeof(orbg_keypoint)), o_cnt = L.take(4),
-                 o_ur = L.take((size_t)n * 4), o_d = L.take((size_t)n * 4);
-    uint8_t *hs, *db;
-    int rc = L.host(c, &hs);
-    if (rc) return rc;
-    if ((rc = L.device(c, &db))) return rc;
-    for (int y = 0; y < h; y++)
-        memcpy(hs + o_img + (size_t)y * w * px, (const uint8_t *)depth + (size_t)y * pitch, (size_t)w * px);
-    memcpy(hs + o_k, kps, (size_t)n * sizeof(orbg_keypoint));
-    memcpy(hs + o_ku, kps_un, (size_t)n * sizeof(orbg_keypoint));
-    const int32_t cnt = n;
-    memcpy(hs + o_cnt, &cnt, 4);
-    HIPCHK(hipMemcpyAsync(db, hs, o_ur, hipMemcpyHostToDevice, c->stream));
-    rc = launch_rgbd(c->stream, db + o_img, depth_type == ORBG_DEPTH_U16, factor, w, h,
-                     (size_t)w * px, 0, L.at<orbg_keypoint>(db, o_k),
-                     L.at<orbg_keypoint>(db, o_ku), L.at<int32_t>(db, o_cnt), n, 1, mbf,
-                     L.at<float>(db, o_ur), L.at<float>(db, o_d));
-    if (rc) return set_err(ORBG_EIO, "k_rgbd launch failed");
-    HIPCHK(hipMemcpyAsync(hs + o_ur, db + o_ur, L.total() - o_ur, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    memcpy(uright, hs + o_ur, (size_t)n * 4);
-    memcpy(depth_out, hs + o_d, (size_t)n * 4);
-    return ORBG_OK;
-}
-
-extern "C" int orbg_undistort_keypoints(orbg_ctx *c, const orbg_camera *cam,
-                                        const orbg_keypoint *kps, int n, orbg_keypoint *kps_un)
-{
-    if (!c || !cam) return set_err(ORBG_EINVAL, "NULL argument");
-    if (n < 0) return set_err(ORBG_EINVAL, "negative size");
-    if (n == 0) return ORBG_OK;
-    if (!kps || !kps_un) return set_err(ORBG_EINVAL, "NULL array");
-    if (cam->k1 != 0.0f && !cam_ok(cam)) return set_err(ORBG_EINVAL, "fx / fy must be finite and nonzero");
-    HIPCHK(hipSetDevice(c->device));
-    Layout L;
-    const size_t o_k = L.take((size_t)n * sizeof(orbg_keypoint)), o_cnt = L.take(4),
-                 o_un = L.take((size_t)n * sizeof(orbg_keypoint));
-    uint8_t *hs, *db;
-    int rc = L.host(c, &hs);
-    if (rc) return rc;
-    if ((rc = L.device(c, &db))) return rc;
-    memcpy(hs + o_k, kps, (size_t)n * sizeof(orbg_keypoint));
-    const int32_t cnt = n;
-    memcpy(hs + o_cnt, &cnt, 4);
-    HIPCHK(hipMemcpyAsync(db, hs, o_cnt + 4, hipMemcpyHostToDevice, c->stream));
-    rc = launch_undistort(c->stream, *cam, L.at<orbg_keypoint>(db, o_k), L.at<int32_t>(db, o_cnt),
-                          n, 1, L.at<orbg_keypoint>(db, o_un));
-    if (rc) return set_err(ORBG_EIO, "k_undistort launch failed");
-    HIPCHK(hipMemcpyAsync(hs + o_un, db + o_un, (size_t)n * sizeof(orbg_keypoint),
-                          hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    memcpy(kps_un, hs + o_un, (size_t)n * sizeof(orbg_keypoint));
-    return ORBG_OK;
-}
-
-extern "C" int orbg_is_in_frustum_batch_device(orbg_ctx *c, const orbg_frustum_camera *d_cams,
-                                               const orbg_map_point *d_mps,
-                                               const int32_t *d_counts, int cap, int nframes,
-                                               float viewing_cos_limit,
-                                               orbg_map_projection *d_proj, int32_t *d_nvisible)
-{
-    if (!c) return set_err(ORBG_EINVAL, "NULL context");
-    if (nframes < 0 || cap < 0) return set_err(ORBG_EINVAL, "negative size");
-    if (nframes == 0 || cap == 0) return ORBG_OK;
-    if (!d_cams || !d_mps || !d_counts || !d_proj || !d_nvisible)
-        return set_err(ORBG_EINVAL, "NULL device array");
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    int rc = 0;
-    PROF_LAUNCH(c, "frustum",
-                rc = launch_frustum(st, d_cams, d_mps, d_counts, cap, nframes, viewing_cos_limit,
-                                    d_proj, d_nvisible));
-    if (rc) return set_err(ORBG_EIO, "k_frustum launch failed");
-    return ORBG_OK;
-}
-
-extern "C" int orbg_is_in_frustum(orbg_ctx *c, const orbg_frustum_camera *cam,
-                                  const orbg_map_point *mps, int n, float viewing_cos_limit,
-                                  orbg_map_projection *proj, int *nvisible)
-{
-    if (!c || !cam || !nvisible) return set_err(ORBG_EINVAL, "NULL argument");
-    if (n < 0) return set_err(ORBG_EINVAL, "negative size");
-    *nvisible = 0;
-    if (n == 0) return ORBG_OK;
-    if (!mps || !proj) return set_err(ORBG_EINVAL, "NULL array");
-    HIPCHK(hipSetDevice(c->device));
-    Layout L;
-    const size_t o_cam = L.take(sizeof(orbg_frustum_camera)), o_cnt = L.take(4),
-                 o_mp = L.take((size_t)n * sizeof(orbg_map_point)),
-                 o_pr = L.take((size_t)n * sizeof(orbg_map_projection)), o_nv = L.take(4);
-    uint8_t *hs, *db;
-    int rc = L.host(c, &hs);
-    if (rc) return rc;
-    if ((rc = L.device(c, &db))) return rc;
-    memcpy(hs + o_cam, cam, sizeof(orbg_frustum_camera));
-    const int32_t cnt = n;
-    memcpy(hs + o_cnt, &cnt, 4);
-    memcpy(hs + o_mp, mps, (size_t)n * sizeof(orbg_map_point));
-    // the projections a point not in view keeps (only its flags are written)
-    memcpy(hs + o_pr, proj, (size_t)n * sizeof(orbg_map_projection));
-    HIPCHK(hipMemcpyAsync(db, hs, o_nv, hipMemcpyHostToDevice, c->stream));
-    rc = launch_frustum(c->stream, L.at<orbg_frustum_camera>(db, o_cam),
-                        L.at<orbg_map_point>(db, o_mp), L.at<int32_t>(db, o_cnt), n, 1,
-                        viewing_cos_limit, L.at<orbg_map_projection>(db, o_pr),
-                        L.at<int32_t>(db, o_nv));
-    if (rc) return set_err(ORBG_EIO, "k_frustum launch failed");
-    HIPCHK(hipMemcpyAsync(hs + o_pr, db + o_pr, L.total() - o_pr, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    memcpy(proj, hs + o_pr, (size_t)n * sizeof(orbg_map_projection));
-    memcpy(nvisible, hs + o_nv, 4);
-    return ORBG_OK;
-}
-
-extern "C" int orbg_distinctive_descriptors_batch_device(orbg_ctx *c, const uint8_t *d_pool,
-                                                         const int32_t *d_rows,
-                                                         const int32_t *d_off, int npoints,
-                                                         int32_t *d_best, uint8_t *d_desc)
-{
-    if (!c) return set_err(ORBG_EINVAL, "NULL context");
-    if (npoints < 0) return set_err(ORBG_EINVAL, "negative size");
-    if (npoints == 0) return ORBG_OK;
-    if (!d_pool || !d_rows || !d_off || !d_best) return set_err(ORBG_EINVAL, "NULL device array");
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    int rc = 0;
-    PROF_LAUNCH(c, "distinctive",
-                rc = launch_distinctive(st, d_pool, d_rows, d_off, npoints, d_best, d_desc));
-    if (rc) return set_err(ORBG_EIO, "k_distinctive launch failed");
-    return ORBG_OK;
-}
-
-extern "C" int orbg_distinctive_descriptor(orbg_ctx *c, const uint8_t *desc, int n, int32_t *best)
-{
-    if (!c || !best) return set_err(ORBG_EINVAL, "NULL argument");
-    if (n < 0) return set_err(ORBG_EINVAL, "negative size");
-    *best = -1;
-    if (n == 0) return ORBG_OK;  // observations empty: the reference returns (MapPoint.cc:356)
-    if (!desc) return set_err(ORBG_EINVAL, "NULL array");
-    HIPCHK(hipSetDevice(c->device));
-    Layout L;
-    const size_t o_d = L.take((size_t)n * 32), o_r = L.take((size_t)n * 4), o_off = L.take(8),
-                 o_b = L.take(4);
-    uint8_t *hs, *db;
-    int rc = L.host(c, &hs);
-    if (rc) return rc;
-    if ((rc = L.device(c, &db))) return rc;
-    memcpy(hs + o_d, desc, (size_t)n * 32);
-    int32_t *hr = L.at<int32_t>(hs, o_r);
-    for (int i = 0; i < n; i++) hr[i] = i;
-    int32_t *ho = L.at<int32_t>(hs, o_off);
-    ho[0] = 0;
-    ho[1] = n;
-    HIPCHK(hipMemcpyAsync(db, hs, o_b, hipMemcpyHostToDevice, c->stream));
-    rc = launch_distinctive(c->stream, db + o_d, L.at<int32_t>(db, o_r),
-                            L.at<int32_t>(db, o_off), 1, L.at<int32_t>(db, o_b), nullptr);
-    if (rc) return set_err(ORBG_EIO, "k_distinctive launch failed");
-    HIPCHK(hipMemcpyAsync(hs + o_b, db + o_b, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    memcpy(best, hs + o_b, 4);
     return ORBG_OK;
 }
 
@@ -5202,431 +4141,3 @@ extern "C" int orbg_fuse_sim3(orbg_ctx *c, const orbg_keyframe *kf, const orbg_f
 {
     return fuse_host(c, kf, cam, mps, mdesc, nmp, th, 1, best_idx, best_dist, nfused);
 }
-
-// ---------------------------------------------------------------------------
-// place recognition: TemplatedVocabulary::score + KeyFrameDatabase (place_kernels.hip)
-// ---------------------------------------------------------------------------
-struct orbg_kfdb {
-    int device = 0;
-    PlaceDb D{};
-    void *d_mem = nullptr;       // one allocation behind every PlaceDb array
-    bool dirty = true;           // the inverted file is stale (add / erase / clear since)
-    bool touched = false;        // any device work issued yet
-    hipStream_t stream = nullptr;  // the context stream of the last call
-};
-
-static int place_l1_only(const orbg_vocab *v)
-{
-    if (v->scoring != ORBG_L1_NORM)
-        return set_err(ORBG_ENOTSUP, "scoring type %d: only L1_NORM (0) is supported", v->scoring);
-    return ORBG_OK;
-}
-
-extern "C" int orbg_bow_score_batch_device(orbg_ctx *c, const orbg_vocab *v,
-                                           const orbg_bow_vectors *a, const orbg_bow_vectors *b,
-                                           int cap, const int32_t *d_a_index,
-                                           const int32_t *d_b_index, int npairs, double *d_score)
-{
-    if (!c || !v || !a || !b) return set_err(ORBG_EINVAL, "NULL argument");
-    if (v->device != c->device) return set_err(ORBG_EINVAL, "vocabulary lives on another device");
-    int rc = place_l1_only(v);
-    if (rc) return rc;
-    if (npairs < 0 || cap < 1 || cap > ORBG_KFDB_MAX_CAP) return set_err(ORBG_EINVAL, "bad npairs / cap");
-    if (npairs == 0) return ORBG_OK;
-    if (!a->words || !a->weights || !a->nbow || !b->words || !b->weights || !b->nbow || !d_score)
-        return set_err(ORBG_EINVAL, "NULL device array");
-    HIPCHK(hipSetDevice(c->device));
-    if ((rc = launch_place_score(c->stream, *a, *b, cap, d_a_index, d_b_index, npairs, d_score,
-                                 &c->prof)))
-        return set_err(rc, "k_place_score launch failed");
-    return ORBG_OK;
-}
-
-extern "C" int orbg_bow_score(orbg_ctx *c, const orbg_vocab *v, const int32_t *words1,
-                              const double *weights1, int n1, const int32_t *words2,
-                              const double *weights2, int n2, double *score)
-{
-    if (!c || !v || !score) return set_err(ORBG_EINVAL, "NULL argument");
-    int rc = place_l1_only(v);
-    if (rc) return rc;
-    if (n1 < 0 || n2 < 0) return set_err(ORBG_EINVAL, "negative size");
-    if (n1 > ORBG_KFDB_MAX_CAP || n2 > ORBG_KFDB_MAX_CAP)
-        return set_err(ORBG_ENOTSUP, "a BowVector with more than %d entries", ORBG_KFDB_MAX_CAP);
-    if ((n1 && (!words1 || !weights1)) || (n2 && (!words2 || !weights2)))
-        return set_err(ORBG_EINVAL, "NULL array");
-    HIPCHK(hipSetDevice(c->device));
-    const int cap = std::max(std::max(n1, n2), 1);
-    Layout L;
-    const size_t o_w = L.take((size_t)2 * cap * 4), o_x = L.take((size_t)2 * cap * 8);
-    const size_t o_n = L.take(8), o_i = L.take(8), o_s = L.take(8);
-    uint8_t *b;
-    if ((rc = L.device(c, &b))) return rc;
-    const int32_t nb[2] = {n1, n2}, idx[2] = {0, 1};
-    if (n1) HIPCHK(hipMemcpyAsync(b + o_w, words1, (size_t)n1 * 4, hipMemcpyHostToDevice, c->stream));
-    if (n1) HIPCHK(hipMemcpyAsync(b + o_x, weights1, (size_t)n1 * 8, hipMemcpyHostToDevice, c->stream));
-    if (n2) HIPCHK(hipMemcpyAsync(b + o_w + (size_t)cap * 4, words2, (size_t)n2 * 4, hipMemcpyHostToDevice, c->stream));
-    if (n2) HIPCHK(hipMemcpyAsync(b + o_x + (size_t)cap * 8, weights2, (size_t)n2 * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(b + o_n, nb, 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(b + o_i, idx, 8, hipMemcpyHostToDevice, c->stream));
-    orbg_bow_vectors V{L.at<int32_t>(b, o_w), L.at<double>(b, o_x),
-                       L.at<int32_t>(b, o_n)};
-    if ((rc = launch_place_score(c->stream, V, V, cap, L.at<int32_t>(b, o_i),
-                                 L.at<int32_t>(b, o_i) + 1, 1, L.at<double>(b, o_s), &c->prof)))
-        return set_err(rc, "k_place_score launch failed");
-    HIPCHK(hipMemcpyAsync(score, b + o_s, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    c->prof.collect();
-    return ORBG_OK;
-}
-
-extern "C" int orbg_kfdb_create(orbg_ctx *c, const orbg_vocab *v, int max_keyframes, int cap,
-                                orbg_kfdb **out)
-{
-    if (!c || !v || !out) return set_err(ORBG_EINVAL, "NULL argument");
-    *out = nullptr;
-    if (v->device != c->device) return set_err(ORBG_EINVAL, "vocabulary lives on another device");
-    int rc = place_l1_only(v);
-    if (rc) return rc;
-    if (max_keyframes < 1 || cap < 1) return set_err(ORBG_EINVAL, "max_keyframes / cap < 1");
-    if (max_keyframes > ORBG_KFDB_MAX_KEYFRAMES)
-        return set_err(ORBG_ENOTSUP, "max_keyframes %d (> %d: a query's per-slot state lives in LDS)",
-                       max_keyframes, ORBG_KFDB_MAX_KEYFRAMES);
-    if (cap > ORBG_KFDB_MAX_CAP) return set_err(ORBG_ENOTSUP, "cap %d (> %d)", cap, ORBG_KFDB_MAX_CAP);
-    HIPCHK(hipSetDevice(c->device));
-    const size_t K = (size_t)max_keyframes, kc = K * (size_t)cap, nw = (size_t)v->nwords;
-    Layout L;
-    const size_t o_wt = L.take(kc * 8), o_wd = L.take(kc * 4), o_nb = L.take(K * 4);
-    const size_t o_lv = L.take(K * 4), o_sq = L.take(K * 8), o_rl = L.take(K * 4);
-    const size_t o_ct = L.take(8), o_nl = L.take(4), o_rk = L.take(K * 4);
-    const size_t o_io = L.take((nw + 1) * 4), o_ic = L.take(nw * 4), o_po = L.take(kc * 2);
-    const size_t o_pe = L.take(K * 8), o_pt = L.take((nw / 4096 + 1) * 4);
-    auto *db = new orbg_kfdb();
-    db->device = c->device;
-    if (hipMalloc(&db->d_mem, L.total()) != hipSuccess) {
-        delete db;
-        return set_err(ORBG_ENOMEM, "KeyFrameDatabase: hipMalloc(%zu bytes)", L.total());
-    }
-    uint8_t *b = (uint8_t *)db->d_mem;
-    PlaceDb &D = db->D;
-    D.K = max_keyframes;
-    D.cap = cap;
-    D.nwords = v->nwords;
-    D.weights = L.at<double>(b, o_wt);
-    D.words = L.at<int32_t>(b, o_wd);
-    D.nbow = L.at<int32_t>(b, o_nb);
-    D.live = L.at<int32_t>(b, o_lv);
-    D.seq = L.at<int64_t>(b, o_sq);
-    D.reloc = L.at<float>(b, o_rl);
-    D.counter = L.at<int64_t>(b, o_ct);
-    D.nlive = L.at<int32_t>(b, o_nl);
-    D.rank = L.at<int32_t>(b, o_rk);
-    D.inv_off = L.at<int32_t>(b, o_io);
-    D.inv_cur = L.at<int32_t>(b, o_ic);
-    D.post = L.at<uint16_t>(b, o_po);
-    D.pending = L.at<unsigned long long>(b, o_pe);
-    D.part = L.at<int32_t>(b, o_pt);
-    // everything from nbow on starts at zero (no live slot, counter 0, no pending score)
-    hipError_t e = hipMemsetAsync(b + o_nb, 0, L.total() - o_nb, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        hipFree(db->d_mem);
-        delete db;
-        return set_err(ORBG_EIO, "KeyFrameDatabase: %s", hipGetErrorString(e));
-    }
-    db->stream = c->stream;
-    *out = db;
-    return ORBG_OK;
-}
-
-extern "C" void orbg_kfdb_destroy(orbg_kfdb *db)
-{
-    if (!db) return;
-    hipSetDevice(db->device);
-    if (db->d_mem) hipFree(db->d_mem);
-    delete db;
-}
-
-extern "C" int orbg_kfdb_info(orbg_kfdb *db, int32_t *nlive, int32_t *max_keyframes, int32_t *cap,
-                              int32_t *limit)
-{
-    if (!db) return set_err(ORBG_EINVAL, "database is NULL");
-    if (max_keyframes) *max_keyframes = db->D.K;
-    if (cap) *cap = db->D.cap;
-    if (limit) *limit = ORBG_KFDB_MAX_KEYFRAMES;
-    if (nlive) {
-        *nlive = 0;
-        if (db->touched) {
-            HIPCHK(hipSetDevice(db->device));
-            if (launch_place_count(db->stream, db->D)) return set_err(ORBG_EIO, "k_place_count launch failed");
-            HIPCHK(hipMemcpyAsync(nlive, db->D.nlive, 4, hipMemcpyDeviceToHost, db->stream));
-            HIPCHK(hipStreamSynchronize(db->stream));
-        }
-    }
-    return ORBG_OK;
-}
-
-static int kfdb_enter(orbg_ctx *c, orbg_kfdb *db)
-{
-    if (!c || !db) return set_err(ORBG_EINVAL, "NULL context or database");
-    if (db->device != c->device) return set_err(ORBG_EINVAL, "database lives on another device");
-    HIPCHK(hipSetDevice(c->device));
-    if (db->stream != c->stream) {  // the context's stream changed: finish what the old one holds
-        if (db->touched) HIPCHK(hipStreamSynchronize(db->stream));
-        db->stream = c->stream;
-    }
-    return ORBG_OK;
-}
-
-extern "C" int orbg_kfdb_add_batch_device(orbg_ctx *c, orbg_kfdb *db, const int32_t *d_slots,
-                                          const orbg_bow_vectors *v, int vcap,
-                                          const int32_t *d_index, int n)
-{
-    int rc = kfdb_enter(c, db);
-    if (rc) return rc;
-    if (n < 0) return set_err(ORBG_EINVAL, "negative size");
-    if (n == 0) return ORBG_OK;
-    if (!d_slots || !v || !v->words || !v->weights || !v->nbow)
-        return set_err(ORBG_EINVAL, "NULL device array");
-    if (vcap < 1 || vcap > db->D.cap)
-        return set_err(ORBG_EINVAL, "vcap %d outside 1..%d (the database's cap)", vcap, db->D.cap);
-    if ((rc = launch_place_add(c->stream, db->D, d_slots, *v, vcap, d_index, n, &c->prof)))
-        return set_err(rc, "k_place_add launch failed");
-    db->dirty = db->touched = true;
-    return ORBG_OK;
-}
-
-extern "C" int orbg_kfdb_add(orbg_ctx *c, orbg_kfdb *db, int slot, const int32_t *words,
-                             const double *weights, int n)
-{
-    int rc = kfdb_enter(c, db);
-    if (rc) return rc;
-    const PlaceDb &D = db->D;
-    if (slot < 0 || slot >= D.K) return set_err(ORBG_EINVAL, "slot %d outside [0, %d)", slot, D.K);
-    if (n < 0 || n > D.cap) return set_err(ORBG_EINVAL, "%d entries (cap %d)", n, D.cap);
-    if (n && (!words || !weights)) return set_err(ORBG_EINVAL, "NULL array");
-    for (int i = 0; i < n; i++) {
-        if (words[i] < 0 || words[i] >= D.nwords)
-            return set_err(ORBG_EINVAL, "word id %d outside [0, %d)", words[i], D.nwords);
-        if (i && words[i] <= words[i - 1])
-            return set_err(ORBG_EINVAL, "word ids not strictly ascending at entry %d", i);
-    }
-    int32_t live = 0;
-    if (db->touched) {
-        HIPCHK(hipMemcpyAsync(&live, D.live + slot, 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-    }
-    if (live) return set_err(ORBG_EINVAL, "slot %d is already live", slot);
-    const int cap = std::max(n, 1);
-    Layout L;
-    const size_t o_w = L.take((size_t)cap * 4), o_x = L.take((size_t)cap * 8), o_n = L.take(4);
-    const size_t o_s = L.take(4);
-    uint8_t *b;
-    if ((rc = L.device(c, &b))) return rc;
-    const int32_t nb = n, sl = slot;
-    if (n) HIPCHK(hipMemcpyAsync(b + o_w, words, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    if (n) HIPCHK(hipMemcpyAsync(b + o_x, weights, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(b + o_n, &nb, 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(b + o_s, &sl, 4, hipMemcpyHostToDevice, c->stream));
-    orbg_bow_vectors V{L.at<int32_t>(b, o_w), L.at<double>(b, o_x),
-                       L.at<int32_t>(b, o_n)};
-    if ((rc = launch_place_add(c->stream, D, L.at<int32_t>(b, o_s), V, cap, nullptr, 1, &c->prof)))
-        return set_err(rc, "k_place_add launch failed");
-    db->dirty = db->touched = true;
-    HIPCHK(hipStreamSynchronize(c->stream));  // the scratch is the next host call's too
-    c->prof.collect();
-    return ORBG_OK;
-}
-
-extern "C" int orbg_kfdb_erase(orbg_ctx *c, orbg_kfdb *db, int slot)
-{
-    int rc = kfdb_enter(c, db);
-    if (rc) return rc;
-    if (slot < 0 || slot >= db->D.K)
-        return set_err(ORBG_EINVAL, "slot %d outside [0, %d)", slot, db->D.K);
-    if (launch_place_erase(c->stream, db->D, slot)) return set_err(ORBG_EIO, "k_place_erase launch failed");
-    db->dirty = db->touched = true;
-    return ORBG_OK;
-}
-
-extern "C" int orbg_kfdb_clear(orbg_ctx *c, orbg_kfdb *db)
-{
-    int rc = kfdb_enter(c, db);
-    if (rc) return rc;
-    HIPCHK(hipMemsetAsync(db->D.live, 0, (size_t)db->D.K * 4, c->stream));
-    db->dirty = db->touched = true;
-    return ORBG_OK;
-}
-
-extern "C" int orbg_kfdb_rebuild(orbg_ctx *c, orbg_kfdb *db)
-{
-    int rc = kfdb_enter(c, db);
-    if (rc) return rc;
-    if (!db->dirty) return ORBG_OK;
-    if ((rc = launch_place_rebuild(c->stream, db->D, &c->prof)))
-        return set_err(rc, "inverted file rebuild launch failed");
-    db->dirty = false;
-    db->touched = true;
-    return ORBG_OK;
-}
-
-extern "C" int orbg_kfdb_reloc_scores(orbg_ctx *c, orbg_kfdb *db, float *reloc_score)
-{
-    int rc = kfdb_enter(c, db);
-    if (rc) return rc;
-    if (!reloc_score) return set_err(ORBG_EINVAL, "NULL array");
-    HIPCHK(hipMemcpyAsync(reloc_score, db->D.reloc, (size_t)db->D.K * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return ORBG_OK;
-}
-
-static int kfdb_detect(orbg_ctx *c, orbg_kfdb *db, PlaceQuery &Q)
-{
-    int rc = kfdb_enter(c, db);
-    if (rc) return rc;
-    if (Q.nq < 0 || Q.cand_cap < 0) return set_err(ORBG_EINVAL, "negative size");
-    if (Q.nq == 0) return ORBG_OK;
-    if (Q.qcap < 1 || Q.qcap > ORBG_KFDB_MAX_CAP)
-        return set_err(ORBG_ENOTSUP, "qcap %d outside 1..%d", Q.qcap, ORBG_KFDB_MAX_CAP);
-    if (!Q.q.words || !Q.q.weights || !Q.q.nbow || !Q.neigh || !Q.ncand || (Q.cand_cap && !Q.cand))
-        return set_err(ORBG_EINVAL, "NULL device array");
-    if (Q.loop) {
-        if (Q.conn_cap < 0) return set_err(ORBG_EINVAL, "negative size");
-        if (!Q.nconn || !Q.min_score || (Q.conn_cap && !Q.conn))
-            return set_err(ORBG_EINVAL, "NULL device array");
-    }
-    if ((rc = orbg_kfdb_rebuild(c, db))) return rc;
-    if ((rc = launch_place_query(c->stream, db->D, Q, &c->prof)))
-        return set_err(rc, "k_place_query launch failed");
-    db->touched = true;
-    return ORBG_OK;
-}
-
-extern "C" int orbg_kfdb_detect_reloc_batch_device(orbg_ctx *c, orbg_kfdb *db,
-                                                   const orbg_bow_vectors *q, int qcap,
-                                                   const int32_t *d_qindex, int nq,
-                                                   const int32_t *d_neigh, int32_t *d_cand,
-                                                   int cand_cap, int32_t *d_ncand,
-                                                   int32_t *d_max_common, int32_t *d_nscored)
-{
-    if (!c || !db || !q) return set_err(ORBG_EINVAL, "NULL argument");
-    PlaceQuery Q{};
-    Q.q = *q;
-    Q.qcap = qcap;
-    Q.nq = nq;
-    Q.qindex = d_qindex;
-    Q.neigh = d_neigh;
-    Q.cand = d_cand;
-    Q.cand_cap = cand_cap;
-    Q.ncand = d_ncand;
-    Q.max_common = d_max_common;
-    Q.nscored = d_nscored;
-    return kfdb_detect(c, db, Q);
-}
-
-extern "C" int orbg_kfdb_detect_loop_batch_device(orbg_ctx *c, orbg_kfdb *db,
-                                                  const orbg_bow_vectors *q, int qcap,
-                                                  const int32_t *d_qindex, int nq,
-                                                  const int32_t *d_conn, int conn_cap,
-                                                  const int32_t *d_nconn, const float *d_min_score,
-                                                  const int32_t *d_neigh, int32_t *d_cand,
-                                                  int cand_cap, int32_t *d_ncand,
-                                                  int32_t *d_max_common, int32_t *d_nscored)
-{
-    if (!c || !db || !q) return set_err(ORBG_EINVAL, "NULL argument");
-    PlaceQuery Q{};
-    Q.q = *q;
-    Q.qcap = qcap;
-    Q.nq = nq;
-    Q.qindex = d_qindex;
-    Q.neigh = d_neigh;
-    Q.conn = d_conn;
-    Q.conn_cap = conn_cap;
-    Q.nconn = d_nconn;
-    Q.min_score = d_min_score;
-    Q.loop = 1;
-    Q.cand = d_cand;
-    Q.cand_cap = cand_cap;
-    Q.ncand = d_ncand;
-    Q.max_common = d_max_common;
-    Q.nscored = d_nscored;
-    return kfdb_detect(c, db, Q);
-}
-
-// one query from host arrays: uploads, runs the batched form with nq = 1, downloads
-static int kfdb_detect_host(orbg_ctx *c, orbg_kfdb *db, const int32_t *words,
-                            const double *weights, int n, bool loop, const int32_t *conn,
-                            int nconn, float min_score, const int32_t *neigh, int32_t *cand,
-                            int cand_cap, int32_t *ncand, int32_t *max_common, int32_t *nscored)
-{
-    int rc = kfdb_enter(c, db);
-    if (rc) return rc;
-    if (!ncand || !neigh) return set_err(ORBG_EINVAL, "NULL argument");
-    if (n < 0 || cand_cap < 0 || nconn < 0) return set_err(ORBG_EINVAL, "negative size");
-    if (n > ORBG_KFDB_MAX_CAP)
-        return set_err(ORBG_ENOTSUP, "a BowVector with more than %d entries", ORBG_KFDB_MAX_CAP);
-    if ((n && (!words || !weights)) || (nconn && !conn) || (cand_cap && !cand))
-        return set_err(ORBG_EINVAL, "NULL array");
-    const int cap = std::max(n, 1), K = db->D.K;
-    Layout L;
-    const size_t o_w = L.take((size_t)cap * 4), o_x = L.take((size_t)cap * 8), o_n = L.take(4);
-    const size_t o_ng = L.take((size_t)K * ORBG_KFDB_NEIGH * 4), o_cn = L.take((size_t)nconn * 4);
-    const size_t o_nc = L.take(4), o_ms = L.take(4), o_cd = L.take((size_t)cand_cap * 4);
-    const size_t o_out = L.take(12);
-    uint8_t *b;
-    if ((rc = L.device(c, &b))) return rc;
-    const int32_t nb = n, ncn = nconn;
-    if (n) HIPCHK(hipMemcpyAsync(b + o_w, words, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    if (n) HIPCHK(hipMemcpyAsync(b + o_x, weights, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(b + o_n, &nb, 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(b + o_ng, neigh, (size_t)K * ORBG_KFDB_NEIGH * 4, hipMemcpyHostToDevice, c->stream));
-    if (nconn) HIPCHK(hipMemcpyAsync(b + o_cn, conn, (size_t)nconn * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(b + o_nc, &ncn, 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(b + o_ms, &min_score, 4, hipMemcpyHostToDevice, c->stream));
-    PlaceQuery Q{};
-    Q.q = orbg_bow_vectors{L.at<int32_t>(b, o_w), L.at<double>(b, o_x),
-                           L.at<int32_t>(b, o_n)};
-    Q.qcap = cap;
-    Q.nq = 1;
-    Q.neigh = L.at<int32_t>(b, o_ng);
-    Q.conn = L.at<int32_t>(b, o_cn);
-    Q.conn_cap = nconn;
-    Q.nconn = L.at<int32_t>(b, o_nc);
-    Q.min_score = L.at<float>(b, o_ms);
-    Q.loop = loop ? 1 : 0;
-    Q.cand = L.at<int32_t>(b, o_cd);
-    Q.cand_cap = cand_cap;
-    Q.ncand = L.at<int32_t>(b, o_out);
-    Q.max_common = Q.ncand + 1;
-    Q.nscored = Q.ncand + 2;
-    if ((rc = kfdb_detect(c, db, Q))) return rc;
-    int32_t out[3] = {0, 0, 0};
-    HIPCHK(hipMemcpyAsync(out, b + o_out, 12, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    const int nw = std::min(out[0], cand_cap);
-    if (nw > 0) HIPCHK(hipMemcpy(cand, b + o_cd, (size_t)nw * 4, hipMemcpyDeviceToHost));
-    c->prof.collect();
-    *ncand = out[0];
-    if (max_common) *max_common = out[1];
-    if (nscored) *nscored = out[2];
-    return ORBG_OK;
-}
-
-extern "C" int orbg_kfdb_detect_reloc(orbg_ctx *c, orbg_kfdb *db, const int32_t *words,
-                                      const double *weights, int n, const int32_t *neigh,
-                                      int32_t *cand, int cand_cap, int32_t *ncand,
-                                      int32_t *max_common, int32_t *nscored)
-{
-    return kfdb_detect_host(c, db, words, weights, n, false, nullptr, 0, 0.0f, neigh, cand,
-                            cand_cap, ncand, max_common, nscored);
-}
-
-extern "C" int orbg_kfdb_detect_loop(orbg_ctx *c, orbg_kfdb *db, const int32_t *words,
-                                     const double *weights, int n, const int32_t *conn, int nconn,
-                                     float min_score, const int32_t *neigh, int32_t *cand,
-                                     int cand_cap, int32_t *ncand, int32_t *max_common,
-                                     int32_t *nscored)
-{
-    return kfdb_detect_host(c, db, words, weights, n, true, conn, nconn, min_score, neigh, cand,
-                            cand_cap, ncand, max_common, nscored);
-}
-

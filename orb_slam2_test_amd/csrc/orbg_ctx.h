@@ -1,6 +1,6 @@
 // orbg_ctx.h -- host-only internals shared by the host files (orbg_api.hip, api_*.hip): the
-// context, errors, profiling and the buffer helpers.  Not for kernel files (they see
-// orbg_launch.h only).
+// context, errors, profiling, the environment-knob reader and the buffer helpers.  Not for
+// kernel files (they see orbg_launch.h only).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -344,7 +344,8 @@ struct orbg_ctx {
     orbg::Prof prof;
 };
 
-// DBoW2 vocabulary handle (orbg_api.hip: the vocabulary entries fill it, the place recognition reads its scoring type)
+// DBoW2 vocabulary handle (api_bow.hip: the vocabulary entries fill it; api_place.hip reads its
+// scoring type)
 struct orbg_vocab {
     int device = 0;
     int k = 0, L = 0, scoring = 0, weighting = 0, nnodes = 0, nwords = 0;
@@ -372,9 +373,20 @@ inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 // pipelined context runs everything on the context stream)
 inline hipStream_t back_stream(orbg_ctx *c) { return c->last_piped ? c->ostream : c->stream; }
 
+// an integer environment knob: atoi of the variable, `dflt` when it is unset.  Whether a knob
+// is read per process, per context or per plan is its reader's business.
+inline int env_int(const char *name, int dflt)
+{
+    const char *e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+
 // orbg_api.hip: the context's pinned stage and device scratch, grown on demand
 int stage(orbg_ctx *c, size_t bytes, uint8_t **out);
 int scratch(orbg_ctx *c, size_t bytes, void **p);
+// orbg_api.hip: `mstream` ordered after everything queued on the context stream so far
+// (ev_caller), ahead of a write to a caller's buffer on `mstream`
+hipError_t order_after_caller(orbg_ctx *c);
 
 // Byte layout of the buffers of an entry point on host arrays: take() hands out the offsets
 // of 256-byte-aligned sub-buffers (an empty array still gets 256 bytes of its own, so it

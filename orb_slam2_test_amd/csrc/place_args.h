@@ -1,5 +1,5 @@
 // place_args.h -- device layout and launch arguments of place recognition (place_kernels.hip:
-// DBoW2 L1 score, KeyFrameDatabase), shared with the host entry points (orbg_api.hip).
+// DBoW2 L1 score, KeyFrameDatabase), shared with the host entry points (api_place.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>

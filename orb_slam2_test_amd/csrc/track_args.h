@@ -1,5 +1,5 @@
 // track_args.h -- launch arguments of the tracking matchers (track_kernels.hip), shared
-// with the host entry points (orbg_api.hip).
+// with the host entry points (api_track.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
