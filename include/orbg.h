@@ -72,6 +72,10 @@
  *   orbg_pnp_solve .................. PnPsolver(F, vpMapPointMatches) + SetRansacParameters +
  *                                     iterate / find  src/PnPsolver.cc:67-900
  *                                     (Tracking::Relocalization, Tracking.cc:2017-2060)
+ *   orbg_optimize_essential_graph ... Optimizer::OptimizeEssentialGraph(pMap, pLoopKF, pCurKF,
+ *                                     NonCorrectedSim3, CorrectedSim3, LoopConnections,
+ *                                     bFixScale)'s optimisation and write-back arithmetic
+ *                                     src/Optimizer.cc:1021-1324 (LoopClosing.cc:914)
  *
  * Batched, device-resident entry points (orbg_*_device) run the same kernels over many
  * frames at once; they exist for the batched-sequence mode and the bench.
@@ -1548,6 +1552,68 @@ int orbg_pnp_solve_batch_device(orbg_ctx *ctx, const orbg_pnp_problem *d_problem
                                 orbg_pnp_hyp *d_hyps, uint64_t *d_masks,
                                 orbg_pnp_refine *d_refines, uint64_t *d_refined_masks,
                                 orbg_pnp_result *d_results, uint8_t *d_inliers, int n1cap);
+
+/* ---------------- Optimizer::OptimizeEssentialGraph (LoopClosing::CorrectLoop) ----------------
+ * The Sim3 pose graph of src/Optimizer.cc:1021-1324 (LoopClosing.cc:914): one
+ * VertexSim3Expmap per keyframe, EdgeSim3 edges with identity information and no robust
+ * kernel, g2o's numeric Jacobian (central differences, delta 1e-9), BlockSolver_7_3 with
+ * OptimizationAlgorithmLevenberg under setUserLambdaInit(1e-16), optimize(20).  The map
+ * bookkeeping (which keyframes, which edges; :1040-1258) is the caller's: vertices are
+ * numbered 0 .. nvert - 1, Scw[v] is vScw (the corrected Sim3 where CorrectedSim3 has one,
+ * else the keyframe's pose with scale 1), Snc[v] the NonCorrectedSim3 where one exists, else
+ * Scw[v].  Edge (i, j, kind): vertex 0 of the EdgeSim3 is i, vertex 1 is j, its measurement
+ * Sjw * Swi taken from Scw (kind 0: a LoopConnections edge, :1104-1134) or from Snc (kind 1:
+ * spanning tree, loop and covisibility edges, :1140-1258).  Two vertices may share several
+ * edges.  Precondition, as in the reference: every free vertex is connected to the fixed one.
+ *
+ * orbg_eg_graph_create plans a graph once, on the host: a deterministic minimum-degree
+ * elimination order, the 7x7 block pattern of the factor L including fill, and the lists the
+ * kernels sum in a fixed order.  orbg_eg_graph_info reports the free vertices and the blocks
+ * of H and of L (lower triangles, diagonals included).  ORBG_ENOTSUP for more than 262144
+ * blocks of H or of L, more than 2^24 block updates in the factorisation, or more than 2^26
+ * edges.  ORBG_EINVAL for a NULL pointer, nvert < 1, an edge index outside [0, nvert),
+ * i == j, a kind other than 0 or 1, a fixed_vertex outside [0, nvert).
+ *
+ * orbg_eg_graph_optimize: d_Scw / d_Snc [nvert] in device memory; the LM loop runs on the
+ * host over state in HBM and reads three scalars per trial (chi2 = sum e^T e, computeScale,
+ * the solver's ok; fixed-order device reductions).  The solve is an LDL^T without pivoting in
+ * one workgroup; a pivot that is not positive and finite makes the trial fail as g2o's failed
+ * Cholesky does.  Outputs: d_Siw_out [nvert], the optimised estimates (the fixed vertex, and
+ * under fix_scale every s, bit-identical to d_Scw), and d_Tiw_out [nvert][12] (may be NULL),
+ * the 3x4 [R(q) | t * (1 / s)] of :1266-1286 rounded once to float.  nvert = 1, nedge = 0 or
+ * iterations = 0 run no iteration: the input comes back (report->iterations = 0).
+ * Synchronises.  Two runs give identical bytes. */
+typedef struct {
+    double q[4], t[3], s; /* q = x, y, z, w; never re-normalised, as g2o::Sim3 */
+} orbg_sim3d;
+typedef struct {
+    int32_t i, j, kind; /* kind 0: measurement from Scw, 1: from Snc */
+} orbg_eg_edge;
+typedef struct orbg_eg_graph orbg_eg_graph;
+int orbg_eg_graph_create(orbg_ctx *ctx, const orbg_eg_edge *edges, int nedge, int nvert,
+                         int fixed_vertex, orbg_eg_graph **out);
+int orbg_eg_graph_info(const orbg_eg_graph *graph, int32_t *nfree, int32_t *h_blocks,
+                       int32_t *l_blocks);
+int orbg_eg_graph_destroy(orbg_eg_graph *graph);
+int orbg_eg_graph_optimize(orbg_ctx *ctx, orbg_eg_graph *graph, const orbg_sim3d *d_Scw,
+                           const orbg_sim3d *d_Snc, int fix_scale, int iterations,
+                           orbg_sim3d *d_Siw_out, float *d_Tiw_out, orbg_lm_report *report);
+/* The map points' correction (:1288-1323), device memory: d_out[p] = correctedSwr.map(
+ * Srw.map(d_points[p])) with Srw = d_Scw[d_ref[p]] and correctedSwr = d_Siw[d_ref[p]]^-1,
+ * computed in double from the float position and rounded once.  d_ref[p] is the caller's
+ * (mnCorrectedReference or the reference keyframe); one outside [0, nvert) leaves its point
+ * as it is.  d_points / d_out: float [n][3], may be the same array.  Context stream, no host
+ * synchronisation. */
+int orbg_eg_correct_points_device(orbg_ctx *ctx, const orbg_sim3d *d_Scw, const orbg_sim3d *d_Siw,
+                                  int nvert, const int32_t *d_ref, const float *d_points, int n,
+                                  float *d_out);
+/* One call from host arrays: plans, uploads, optimises, downloads (Siw_out [nvert], Tiw_out
+ * [nvert][12] or NULL).  Bit-identical to the graph entry points.  An error return leaves the
+ * outputs untouched. */
+int orbg_optimize_essential_graph(orbg_ctx *ctx, const orbg_sim3d *Scw, const orbg_sim3d *Snc,
+                                  int nvert, const orbg_eg_edge *edges, int nedge,
+                                  int fixed_vertex, int fix_scale, int iterations,
+                                  orbg_sim3d *Siw_out, float *Tiw_out, orbg_lm_report *report);
 
 #ifdef __cplusplus
 }

@@ -91,6 +91,10 @@ SIM3OPT_RESULT_DTYPE = np.dtype([("q", "<f8", 4), ("t", "<f8", 3), ("s", "<f8"),
                                  ("R", "<f4", 9), ("tf", "<f4", 3), ("sf", "<f4"),
                                  ("ninliers", "<i4"), ("nbad", "<i4"), ("ncorr", "<i4"),
                                  ("iterations", "<i4", 2)])
+# OptimizeEssentialGraph records (orbg_sim3d, orbg_eg_edge)
+SIM3D_DTYPE = np.dtype([("q", "<f8", 4), ("t", "<f8", 3), ("s", "<f8")])
+EG_EDGE_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("kind", "<i4")])
+EG_MAX_BLOCKS = 262144   # blocks of H or of L per graph (ORBG_ENOTSUP past it)
 RELOC_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("min_dist", "<f4"),
                         ("max_dist", "<f4"), ("angle", "<f4"), ("flags", "<i4")])
 MAPPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"),
@@ -407,6 +411,13 @@ def lib():
                                               vp, vp, i32]),
         "orbg_optimize_sim3": (i32, [vp, vp, vp, vp, i32, vp, vp]),
         "orbg_optimize_sim3_batch_device": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, i32]),
+        "orbg_eg_graph_create": (i32, [vp, vp, i32, i32, i32, P(vp)]),
+        "orbg_eg_graph_info": (i32, [vp, P(C.c_int32), P(C.c_int32), P(C.c_int32)]),
+        "orbg_eg_graph_destroy": (i32, [vp]),
+        "orbg_eg_graph_optimize": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, P(LmReport)]),
+        "orbg_eg_correct_points_device": (i32, [vp, vp, vp, i32, vp, vp, i32, vp]),
+        "orbg_optimize_essential_graph": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp,
+                                                P(LmReport)]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("ORBG_LIB_VARIANT") and not hasattr(L, name):

@@ -3,7 +3,8 @@
 // pivoted LDLT, the unpacking of reduced sums into H and b, the pinned workgroup sum and the
 // step control of OptimizationAlgorithmLevenberg::solve.  Used by PoseOptimization
 // (pose_kernels.hip), LocalBundleAdjustment (ba_kernels.hip, lm_kernels.hip and the host loop
-// of orbg_api.hip) and OptimizeSim3 (sim3opt_args.h, sim3opt_kernels.hip, sim3opt_host.hip).
+// of orbg_api.hip), OptimizeSim3 (sim3opt_args.h, sim3opt_kernels.hip, sim3opt_host.hip) and
+// OptimizeEssentialGraph (essential_args.h, essential_kernels.hip, api_essential.hip).
 //
 // Everything but wg_reduce is __host__ __device__ with a fixed operation order (no FMA
 // contraction), so a host program runs the very same statements as a kernel.  The oracles
@@ -301,6 +302,14 @@ __host__ __device__ inline void lm_begin(LmState *L, int it, double maxdiag)
         L->nBad = 0;
     }
     L->qmax = 0;
+}
+
+// ... under setUserLambdaInit(user_lambda): computeLambdaInit returns a positive user value
+// as it is and never looks at the diagonal
+__host__ __device__ inline void lm_begin(LmState *L, int it, double maxdiag, double user_lambda)
+{
+    lm_begin(L, it, maxdiag);
+    if (it == 0 && user_lambda > 0) L->lambda = user_lambda;
 }
 
 template <int N>

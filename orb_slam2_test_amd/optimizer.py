@@ -11,7 +11,8 @@ Arrays use the dtypes of ``_lib`` (POSE_DTYPE, EDGE_DTYPE, EDGE_OUT_DTYPE).
 
 PoseOptimization (Optimizer.cc:356-631) and OptimizeSim3 (:1366-1578, the Sim3 refinement of
 LoopClosing::ComputeSim3) run whole on the device, LM driver included: one workgroup per frame
-or per loop candidate.
+or per loop candidate.  OptimizeEssentialGraph (:1021-1324, the pose graph of
+LoopClosing::CorrectLoop) keeps its state on the device and its LM loop on the host.
 """
 import ctypes
 import math
@@ -233,6 +234,143 @@ def optimize_sim3_batch(problems, corr_list, init, n1cap, cap=None, ctx=None, de
         d_r.data_ptr(), d_k.data_ptr(), int(n1cap)), "orbg_optimize_sim3_batch_device")
     c_.sync()
     return d_r.cpu().numpy().view(L.SIM3OPT_RESULT_DTYPE), d_k.cpu().numpy()
+
+
+def sim3d_records(S):
+    """orbg_sim3d [n] from SIM3D_DTYPE records, or from a sequence of (q, t, s) with q =
+    (x, y, z, w)."""
+    if isinstance(S, np.ndarray) and S.dtype == L.SIM3D_DTYPE:
+        return np.ascontiguousarray(S).reshape(-1)
+    out = np.zeros(len(S), L.SIM3D_DTYPE)
+    for k, (q, t, s) in enumerate(S):
+        out["q"][k], out["t"][k], out["s"][k] = q, t, s
+    return out
+
+
+def eg_edge_records(edges):
+    """orbg_eg_edge [n] from EG_EDGE_DTYPE records or an (n, 3) array of (i, j, kind)."""
+    if isinstance(edges, np.ndarray) and edges.dtype == L.EG_EDGE_DTYPE:
+        return np.ascontiguousarray(edges).reshape(-1)
+    e = np.asarray(edges, np.int64).reshape(-1, 3)
+    out = np.zeros(len(e), L.EG_EDGE_DTYPE)
+    out["i"], out["j"], out["kind"] = e[:, 0], e[:, 1], e[:, 2]
+    return out
+
+
+def _lm_report(rep):
+    return dict(iterations=rep.iterations, trials=rep.trials, terminated=rep.terminated,
+                initial_chi2=rep.initial_chi2, final_chi2=rep.final_chi2, lam=rep.lam)
+
+
+def OptimizeEssentialGraph(Scw, Snc, edges, fixed, bFixScale, iterations=20, device=0):
+    """The optimisation of Optimizer::OptimizeEssentialGraph (Optimizer.cc:1021-1286) on the
+    device (orbg_optimize_essential_graph).
+
+    Vertices are the keyframes, numbered 0 .. n - 1 by the caller.  Scw[v]: vScw, the corrected
+    Sim3 where CorrectedSim3 has one, else the pose with scale 1; Snc[v]: the NonCorrectedSim3
+    where one exists, else Scw[v] (both SIM3D_DTYPE, or sequences of (q, t, s)).  edges:
+    (i, j, kind) per EdgeSim3, vertex 0 = i, vertex 1 = j, kind 0 a LoopConnections edge
+    (measurement from Scw), 1 any other (from Snc).  fixed: pLoopKF's index.  Every free vertex
+    must be connected to the fixed one.
+
+    Returns (Siw SIM3D_DTYPE [n], Tiw float32 [n, 3, 4] = SetPose's matrices, report dict)."""
+    Scw, Snc, e = sim3d_records(Scw), sim3d_records(Snc), eg_edge_records(edges)
+    if len(Snc) != len(Scw):
+        raise ValueError("Scw and Snc differ in length")
+    n = len(Scw)
+    Siw = np.zeros(n, L.SIM3D_DTYPE)
+    Tiw = np.zeros((n, 3, 4), np.float32)
+    rep = L.LmReport()
+    L.check(L.lib().orbg_optimize_essential_graph(
+        _ctx(device).handle, L.ptr(Scw), L.ptr(Snc), n, L.ptr(e), len(e), int(fixed),
+        1 if bFixScale else 0, int(iterations), L.ptr(Siw), L.ptr(Tiw), ctypes.byref(rep)),
+        "orbg_optimize_essential_graph")
+    return Siw, Tiw, _lm_report(rep)
+
+
+class EssentialGraph:
+    """A planned essential graph (orbg_eg_graph): the elimination order and block pattern are
+    made once, optimize() may run many times."""
+
+    def __init__(self, edges, nvert, fixed, device=0):
+        self._ctx = _ctx(device)
+        self.nvert = int(nvert)
+        e = eg_edge_records(edges)
+        h = ctypes.c_void_p()
+        L.check(L.lib().orbg_eg_graph_create(self._ctx.handle, L.ptr(e), len(e), self.nvert,
+                                             int(fixed), ctypes.byref(h)), "orbg_eg_graph_create")
+        self.handle = h
+
+    def info(self):
+        """(free vertices, blocks of H, blocks of L)."""
+        a, b, c = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        L.check(L.lib().orbg_eg_graph_info(self.handle, ctypes.byref(a), ctypes.byref(b),
+                                           ctypes.byref(c)), "orbg_eg_graph_info")
+        return a.value, b.value, c.value
+
+    def optimize(self, Scw, Snc, bFixScale, iterations=20):
+        """orbg_eg_graph_optimize from host records (uploaded and downloaded here).  Returns
+        (Siw, Tiw, report dict) as OptimizeEssentialGraph."""
+        import torch
+        Scw, Snc = sim3d_records(Scw), sim3d_records(Snc)
+        if len(Scw) != self.nvert or len(Snc) != self.nvert:
+            raise ValueError("the graph has %d vertices" % self.nvert)
+
+        def up(a):
+            return torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).cuda()
+        d_c, d_n = up(Scw), up(Snc)
+        d_o = torch.zeros(self.nvert * 64, dtype=torch.uint8, device="cuda")
+        d_t = torch.zeros(self.nvert * 12, dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        rep = L.LmReport()
+        L.check(L.lib().orbg_eg_graph_optimize(
+            self._ctx.handle, self.handle, d_c.data_ptr(), d_n.data_ptr(), 1 if bFixScale else 0,
+            int(iterations), d_o.data_ptr(), d_t.data_ptr(), ctypes.byref(rep)),
+            "orbg_eg_graph_optimize")
+        return (d_o.cpu().numpy().view(L.SIM3D_DTYPE).copy(),
+                d_t.cpu().numpy().reshape(self.nvert, 3, 4), _lm_report(rep))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            L.lib().orbg_eg_graph_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def CorrectMapPoints(Scw, Siw, ref, points, device=0):
+    """The map points' correction of OptimizeEssentialGraph (Optimizer.cc:1288-1323,
+    orbg_eg_correct_points_device): correctedSwr.map(Srw.map(P)) per point with r = ref[p]
+    (mnCorrectedReference where the point was corrected by the current keyframe, else its
+    reference keyframe), Srw = Scw[r], correctedSwr = Siw[r]^-1; double arithmetic on the float
+    position, rounded once.  Returns float32 [n, 3]."""
+    import torch
+    Scw, Siw = sim3d_records(Scw), sim3d_records(Siw)
+    if len(Scw) != len(Siw):
+        raise ValueError("Scw and Siw differ in length")
+    ref = np.ascontiguousarray(ref, np.int32).reshape(-1)
+    pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    if len(ref) != len(pts):
+        raise ValueError("one reference index per point")
+    n = len(pts)
+    if n == 0:
+        return np.zeros((0, 3), np.float32)
+
+    def up(a):
+        return torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).cuda()
+    c_ = _ctx(device)
+    d_c, d_s, d_r, d_p = up(Scw), up(Siw), up(ref), up(pts)
+    d_o = torch.zeros(n * 3, dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    L.check(L.lib().orbg_eg_correct_points_device(c_.handle, d_c.data_ptr(), d_s.data_ptr(), len(Scw),
+                                                  d_r.data_ptr(), d_p.data_ptr(), n, d_o.data_ptr()),
+            "orbg_eg_correct_points_device")
+    c_.sync()
+    return d_o.cpu().numpy().reshape(n, 3)
 
 
 def vertex_csr(edges, field, nvert):
