@@ -1615,6 +1615,79 @@ int orbg_optimize_essential_graph(orbg_ctx *ctx, const orbg_sim3d *Scw, const or
                                   int fixed_vertex, int fix_scale, int iterations,
                                   orbg_sim3d *Siw_out, float *Tiw_out, orbg_lm_report *report);
 
+/* ---------------- GlobalBundleAdjustment (Optimizer::BundleAdjustment) ----------------
+ * src/Optimizer.cc:105-320: every keyframe a VertexSE3Expmap (fixed iff mnId == 0), every map
+ * point a marginalised VertexSBAPointXYZ, one EdgeSE3ProjectXYZ / EdgeStereoSE3ProjectXYZ per
+ * observation (Huber deltas sqrt(5.99) / sqrt(7.815) when bRobust), BlockSolver_6_3 under
+ * OptimizationAlgorithmLevenberg, optimize(nIterations) with the force-stop flag.  Called by
+ * Tracking::CreateInitialMapMonocular (20 iterations, robust) and LoopClosing::
+ * RunGlobalBundleAdjustment (10 iterations, &mbStopGBA, not robust).  The edge types, the
+ * build, the error pass and the LM are LocalBundleAdjustment's (orbg_ba_graph above); what
+ * differs is the reduced camera system: every pose but one is free, so it is kept and
+ * factorised as a block-sparse matrix instead of orbg_ba_graph_schur_plan's dense one.
+ *
+ * orbg_ba_graph_schur_plan_sparse: the graph's second plan kind.  On the host it takes the
+ * 6x6 block pattern of S (a block per pair of free poses sharing an active landmark), orders
+ * the free poses by minimum degree (the smallest index on ties), finds the pattern of the
+ * factor L by symbolic elimination, the list of updates of every block, and a level for every
+ * column (greater than the level of every column in its row of L): columns of one level are
+ * independent.  orbg_ba_graph_schur_solve / _optimize / _optimize_ctl then use it (they use
+ * whichever plan the graph holds; orbg_ba_graph_set_active rebuilds the plan of the same
+ * kind): S is written straight into L's pattern and factorised L D L^T without pivoting, one
+ * launch per level with a workgroup per column, one workgroup for the single-column levels at
+ * the top of the elimination tree; a pivot that is not positive and finite gives *d_ok = 0
+ * and zero increments.  Every sum has a fixed order: two solves give identical bytes (they
+ * are not the dense plan's bytes: another elimination order).  info (may be NULL) receives
+ * the plan's figures.  ORBG_ENOTSUP past ORBG_GBA_MAX_L_BLOCKS blocks of L (288 bytes each:
+ * 576 MiB) or ORBG_GBA_MAX_UPDATES block updates (16 bytes each: 1 GiB).  The caps are set
+ * by memory alone: how many blocks the global BA of a real map has, has not been measured. */
+#define ORBG_GBA_MAX_L_BLOCKS (1 << 21)
+#define ORBG_GBA_MAX_UPDATES (1 << 26)
+typedef struct orbg_ba_sparse_info {
+    int32_t nfree;        /* free poses = block columns */
+    int32_t s_blocks;     /* blocks of S, lower triangle with the diagonals */
+    int32_t l_blocks;     /* blocks of L: s_blocks + fill */
+    int32_t levels;       /* levels of the schedule */
+    int32_t tail_columns; /* columns of the single-column levels at the top (one workgroup) */
+    int32_t pad;
+    int64_t updates;      /* block updates L(r,k) D(k) L(j,k)^T of one factorisation */
+} orbg_ba_sparse_info;
+int orbg_ba_graph_schur_plan_sparse(orbg_ctx *ctx, orbg_ba_graph *graph, const uint8_t *fixed,
+                                    orbg_ba_sparse_info *info);
+/* The symbolic work alone, on the host (no context, no device): edges as parallel arrays
+ * (pose, point, active), fixed [npose].  order_out [nfree]: the free poses (pose indices) in
+ * elimination order; colptr_out [nfree + 1] / rowidx_out [cap]: L by columns in elimination
+ * positions, rows ascending, the diagonal first; level_out [nfree]: the level of each column.
+ * Any output array may be NULL; rowidx_out with cap < info->l_blocks: ORBG_EINVAL (info is
+ * filled).  Errors as above. */
+int orbg_ba_sparse_symbolic(const int32_t *epose, const int32_t *epoint, const uint8_t *eactive,
+                            int nedge, int npose, int npoint, const uint8_t *fixed,
+                            int32_t *order_out, int32_t *colptr_out, int32_t *rowidx_out, int cap,
+                            int32_t *level_out, orbg_ba_sparse_info *info);
+/* Optimizer::BundleAdjustment's optimisation (Optimizer.cc:113-247) from host arrays: creates
+ * the graph (edges as orbg_ba_graph_create; active / robust as given), makes the sparse plan
+ * with poses[i].fixed, runs optimize(iterations) under control->force_stop (control may be
+ * NULL; d_last_chi2 is honoured), and overwrites poses / points with the estimates.  A fixed
+ * pose, and a point without an active edge, come back byte for byte.  nedge = 0: nothing runs
+ * (report zero).  Equal to the graph entry points on the same arrays, byte for byte. */
+typedef struct {
+    orbg_lm_report lm;
+    orbg_ba_sparse_info plan;
+} orbg_gba_report;
+int orbg_global_ba_optimize(orbg_ctx *ctx, orbg_pose *poses, int npose, double *points, int npoint,
+                            const orbg_edge *edges, int nedge, int iterations,
+                            const orbg_lm_control *control, orbg_gba_report *report);
+/* The map points global BA did not optimise (LoopClosing.cc:1101-1113): Xc = Rcw X + tcw with
+ * the reference keyframe's mTcwBefGBA, then Rwc Xc + twc with its GetPoseInverse(), both in
+ * float by the cv::Mat rule (R * X + t is one cv::gemm: each entry's three products and t
+ * accumulated in double, rounded once).  d_Tcw_before / d_Twc_after: float [nkf][12] (3x4, row-major); d_ref[p]
+ * the reference keyframe's index, one outside [0, nkf) (a keyframe global BA did not reach)
+ * leaves the point as it is.  d_points / d_out: float [n][3], may be the same array.  Context
+ * stream, no host synchronisation. */
+int orbg_gba_correct_points_device(orbg_ctx *ctx, const float *d_Tcw_before,
+                                   const float *d_Twc_after, int nkf, const int32_t *d_ref,
+                                   const float *d_points, int n, float *d_out);
+
 #ifdef __cplusplus
 }
 #endif

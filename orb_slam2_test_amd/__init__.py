@@ -6,7 +6,8 @@ Frame::ComputeStereoMatches, the tracking matchers (SearchByProjection), PoseOpt
 DBoW2's vocabulary transform (Frame::ComputeBoW) and score, KeyFrameDatabase's place
 recognition (DetectRelocalizationCandidates, DetectLoopCandidates), Sim3Solver's RANSAC and
 Optimizer::OptimizeSim3 (LoopClosing::ComputeSim3), Optimizer::OptimizeEssentialGraph
-(LoopClosing::CorrectLoop), the LBA Schur solve and
+(LoopClosing::CorrectLoop), Optimizer::GlobalBundleAdjustemnt (a block-sparse Schur solve),
+the LBA Schur solve and
 the per-edge arithmetic of Optimizer::LocalBundleAdjustment, as hand-written HIP
 kernels behind the C ABI in include/orbg.h (lib/liborbg.so).  The Python classes mirror
 the reference's C++ interfaces; see DESIGN.md.
@@ -17,6 +18,7 @@ from .orbmatcher import Frame, MapPointProjections, ORBmatcher  # noqa: F401
 from .frame import StereoFrame  # noqa: F401
 from .optimizer import PoseOptimization, linearize_local_ba, OptimizeSim3, OptimizeSim3Batch  # noqa: F401
 from .optimizer import OptimizeEssentialGraph, CorrectMapPoints, EssentialGraph  # noqa: F401
+from .optimizer import GlobalBundleAdjustment, CorrectPointsGBA, sparse_symbolic  # noqa: F401
 from .vocabulary import ORBVocabulary, BowVector, FeatureVector  # noqa: F401
 from .keyframedatabase import KeyFrameDatabase  # noqa: F401
 from .sim3solver import Sim3Solver  # noqa: F401
@@ -24,6 +26,7 @@ from .pnpsolver import PnPsolver  # noqa: F401
 
 __all__ = ["ORBextractor", "ORBmatcher", "Frame", "MapPointProjections", "StereoFrame", "PoseOptimization", "linearize_local_ba", "OptimizeSim3", "OptimizeSim3Batch",
            "OptimizeEssentialGraph", "CorrectMapPoints", "EssentialGraph",
+           "GlobalBundleAdjustment", "CorrectPointsGBA", "sparse_symbolic",
            "ORBVocabulary", "BowVector", "FeatureVector", "KeyFrameDatabase", "Sim3Solver", "PnPsolver",
            "KP_DTYPE",
            "EDGE_DTYPE", "EDGE_OUT_DTYPE", "POSE_DTYPE"]

@@ -131,6 +131,21 @@ class LmReport(C.Structure):
                 ("lam", C.c_double)]
 
 
+class BaSparseInfo(C.Structure):
+    """orbg_ba_sparse_info (include/orbg.h): the figures of a sparse Schur plan."""
+    _fields_ = [("nfree", C.c_int32), ("s_blocks", C.c_int32), ("l_blocks", C.c_int32),
+                ("levels", C.c_int32), ("tail_columns", C.c_int32), ("pad", C.c_int32),
+                ("updates", C.c_int64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "pad"}
+
+
+class GbaReport(C.Structure):
+    """orbg_gba_report (include/orbg.h)."""
+    _fields_ = [("lm", LmReport), ("plan", BaSparseInfo)]
+
+
 LM_POST_ITERATION = C.CFUNCTYPE(None, C.c_void_p, C.c_int)
 LM_POST_TRIAL = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int)
 
@@ -334,6 +349,12 @@ def lib():
         "orbg_ba_graph_build_system": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "orbg_ba_graph_errors": (i32, [vp, vp, vp, vp, vp, vp, vp, vp]),
         "orbg_ba_graph_schur_plan": (i32, [vp, vp, vp]),
+        "orbg_ba_graph_schur_plan_sparse": (i32, [vp, vp, vp, P(BaSparseInfo)]),
+        "orbg_ba_sparse_symbolic": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp,
+                                          P(BaSparseInfo)]),
+        "orbg_global_ba_optimize": (i32, [vp, vp, i32, vp, i32, vp, i32, i32, P(LmControl),
+                                          P(GbaReport)]),
+        "orbg_gba_correct_points_device": (i32, [vp, vp, vp, i32, vp, vp, i32, vp]),
         "orbg_ba_graph_schur_solve": (i32, [vp, vp, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp]),
         "orbg_ba_graph_set_robust": (i32, [vp, vp, vp]),
         "orbg_ba_update_device": (i32, [vp, vp, i32, vp, i32, vp, vp, vp, vp]),

@@ -861,6 +861,136 @@ void LocalBundleAdjustment(orbg_ctx *ctx, KeyFrameT *pKF, bool *pbStopFlag, MapT
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// Global bundle adjustment
+// ---------------------------------------------------------------------------------------
+
+// Optimizer::BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, nLoopKF, bRobust)
+// (Optimizer.cc:113-320) with the optimisation on the device (orbg_global_ba_optimize: the
+// block-sparse Schur solve), in the reference's order:
+//   vertices: the key frames that are not bad (fixed iff mnId == 0, :140-152), the map points
+//   that are not bad (:160-170);
+//   edges: one per observation in GetObservations() order, skipped when its key frame is bad
+//   or mnId > maxKFid (:178-184); mono iff mvuRight < 0; information mvInvLevelSigma2[octave];
+//   a Huber kernel iff bRobust, deltas (float)sqrt(5.99) / (float)sqrt(7.815) (:157-158: 5.99,
+//   not LocalBundleAdjustment's 5.991); a point left without an edge is taken out and never
+//   written (vbNotIncludedMP, :236-244);
+//   optimize(nIterations) under pbStopFlag (:248-249);
+//   write-back (:253-318): nLoopKF == 0: SetPose, and SetWorldPos + UpdateNormalAndDepth;
+//   otherwise mTcwGBA / mPosGBA and mnBAGlobalForKF = nLoopKF.
+// report (may be NULL).
+template <class KeyFrameT, class MapPointT>
+void BundleAdjustment(orbg_ctx *ctx, const std::vector<KeyFrameT *> &vpKFs,
+                      const std::vector<MapPointT *> &vpMP, int nIterations = 5,
+                      bool *pbStopFlag = nullptr, const unsigned long nLoopKF = 0,
+                      const bool bRobust = true, orbg_gba_report *report = nullptr)
+{
+    typedef typename std::decay<decltype(vpKFs[0]->GetPose())>::type MatT;
+    std::vector<orbg_pose> poses;
+    std::vector<double> points;
+    std::vector<orbg_edge> edges;
+    std::vector<KeyFrameT *> kfs;
+    std::vector<int> point_of(vpMP.size(), -1);  // -1: bad, or no edge (vbNotIncludedMP)
+    std::map<const KeyFrameT *, int> pose_of;
+    unsigned long maxKFid = 0;
+    for (KeyFrameT *pKF : vpKFs) {
+        if (pKF->isBad()) continue;
+        float T[12];
+        pose12(pKF->GetPose(), T);
+        pose_of[pKF] = (int)poses.size();
+        poses.push_back(se3quat_of(T, pKF->mnId == 0 ? 1 : 0));
+        kfs.push_back(pKF);
+        if (pKF->mnId > maxKFid) maxKFid = pKF->mnId;
+    }
+    const float thHuber2D = std::sqrt(5.99), thHuber3D = std::sqrt(7.815);
+    for (size_t i = 0; i < vpMP.size(); i++) {
+        MapPointT *pMP = vpMP[i];
+        if (pMP->isBad()) continue;
+        const int pt = (int)(points.size() / 3);
+        const size_t first = edges.size();
+        const auto observations = pMP->GetObservations();
+        for (const auto &obs : observations) {
+            KeyFrameT *pKF = obs.first;
+            if (pKF->isBad() || pKF->mnId > maxKFid) continue;
+            auto it = pose_of.find(pKF);
+            if (it == pose_of.end()) continue;  // (g2o has no such vertex: the reference would fault)
+            const size_t k = obs.second;
+            const auto &kpUn = pKF->mvKeysUn[k];
+            orbg_edge e;
+            std::memset(&e, 0, sizeof(e));
+            e.point = pt;
+            e.pose = it->second;
+            e.stereo = pKF->mvuRight[k] < 0 ? 0 : 1;
+            e.robust = bRobust ? 1 : 0;
+            e.active = 1;
+            e.obs[0] = kpUn.pt.x;
+            e.obs[1] = kpUn.pt.y;
+            e.obs[2] = e.stereo ? pKF->mvuRight[k] : 0.0;
+            e.inv_sigma2 = pKF->mvInvLevelSigma2[kpUn.octave];
+            e.fx = pKF->fx;
+            e.fy = pKF->fy;
+            e.cx = pKF->cx;
+            e.cy = pKF->cy;
+            e.bf = pKF->mbf;
+            e.huber_delta = e.stereo ? thHuber3D : thHuber2D;
+            edges.push_back(e);
+        }
+        if (edges.size() == first) continue;  // nEdges == 0: removeVertex
+        point_of[i] = pt;
+        const auto X = pMP->GetWorldPos();
+        for (int c = 0; c < 3; c++) points.push_back(X.template at<float>(c));
+    }
+    orbg_lm_control K;
+    std::memset(&K, 0, sizeof(K));
+    K.force_stop = reinterpret_cast<const volatile uint8_t *>(pbStopFlag);
+    orbg_gba_report rep;
+    std::memset(&rep, 0, sizeof(rep));
+    check(orbg_global_ba_optimize(ctx, poses.data(), (int)poses.size(), points.data(),
+                                  (int)(points.size() / 3), edges.data(), (int)edges.size(),
+                                  nIterations, &K, &rep),
+          "orbg_global_ba_optimize");
+    if (report) *report = rep;
+    for (size_t i = 0; i < kfs.size(); i++) {
+        float T[12];
+        tcw_of(poses[i], T);
+        MatT pose = MatT::eye(4, 4, 5 /* CV_32F */);
+        for (int r = 0; r < 3; r++)
+            for (int c = 0; c < 4; c++) pose.template at<float>(r, c) = T[4 * r + c];
+        if (nLoopKF == 0) {
+            kfs[i]->SetPose(pose);
+        } else {
+            kfs[i]->mTcwGBA = pose;
+            kfs[i]->mnBAGlobalForKF = nLoopKF;
+        }
+    }
+    for (size_t i = 0; i < vpMP.size(); i++) {
+        if (point_of[i] < 0) continue;
+        MapPointT *pMP = vpMP[i];
+        if (pMP->isBad()) continue;
+        MatT X(3, 1, 5 /* CV_32F */);
+        for (int c = 0; c < 3; c++) X.template at<float>(c) = (float)points[3 * (size_t)point_of[i] + c];
+        if (nLoopKF == 0) {
+            pMP->SetWorldPos(X);
+            pMP->UpdateNormalAndDepth();
+        } else {
+            pMP->mPosGBA = X;
+            pMP->mnBAGlobalForKF = nLoopKF;
+        }
+    }
+}
+
+// Optimizer::GlobalBundleAdjustemnt(pMap, nIterations, pbStopFlag, nLoopKF, bRobust)
+// (Optimizer.cc:105-111; the reference's spelling)
+template <class MapT>
+void GlobalBundleAdjustemnt(orbg_ctx *ctx, MapT *pMap, int nIterations = 5,
+                            bool *pbStopFlag = nullptr, const unsigned long nLoopKF = 0,
+                            const bool bRobust = true, orbg_gba_report *report = nullptr)
+{
+    const auto vpKFs = pMap->GetAllKeyFrames();
+    const auto vpMP = pMap->GetAllMapPoints();
+    BundleAdjustment(ctx, vpKFs, vpMP, nIterations, pbStopFlag, nLoopKF, bRobust, report);
+}
+
 // ---------------------------------------------------------------------------
 // Frame geometry
 // ---------------------------------------------------------------------------

@@ -7,6 +7,7 @@
 // (api_place.hip) and the solvers (api_solvers.hip).
 #include "orbg_ctx.h"
 #include "schur_args.h"
+#include "bsolve_args.h"
 #include "bow_args.h"
 #include "g2o_math.h"
 
@@ -2948,6 +2949,11 @@ struct orbg_ba_graph {
     uint8_t *d_schur = nullptr;  // structure + scratch (schur_layout)
     size_t schur_bytes = 0;
     SchurArgs sa{};
+    // the sparse plan kind (orbg_ba_graph_schur_plan_sparse): the symbolic factorisation's
+    // device arrays follow the Schur structure in d_schur
+    bool sparse = false;
+    BsLaunch bs;
+    orbg_ba_sparse_info sinfo{};
     // orbg_ba_graph_optimize's workspace (allocated on first use): the system, the errors,
     // the increments, the pushed estimates and the reductions' scalars
     uint8_t *d_lm = nullptr;
@@ -2978,6 +2984,7 @@ static size_t schur_layout(const SchurPlanHost &P, int nedge, uint8_t *base, Sch
     A.blk_i2 = (const int32_t *)take(P.blk_i2.size() * 4);
     A.blk_seg = (const int32_t *)take(P.blk_seg.size() * 4);
     A.blk_order = (const int32_t *)take(P.blk_order.size() * 4);
+    A.blk_dst = (const int32_t *)take(P.blk_order.size() * 4);  // the sparse plan's (bsolve_args.h)
     A.pose_off = (const int32_t *)take(P.pose_off.size() * 4);
     A.pose_slots = (const int32_t *)take(P.pose_slots.size() * 4);
     A.seg_lo = (const int32_t *)take(P.seg_lo.size() * 4);
@@ -3027,6 +3034,33 @@ static int schur_upload(const SchurPlanHost &P, const SchurArgs &A, hipStream_t 
     return ORBG_OK;
 }
 
+// Device layout of a BsPlanHost and the factorisation's arrays from `base` (nullptr: sizes
+// only); returns the bytes
+static size_t bsolve_layout(const BsPlanHost &B, uint8_t *base, BsArgs &A)
+{
+    size_t off = 0;
+    auto take = [&](size_t bytes) -> uint8_t * {
+        uint8_t *q = base ? base + off : nullptr;
+        off += al256(std::max(bytes, (size_t)1));
+        return q;
+    };
+    const size_t n = (size_t)std::max(B.n, 1), nl = B.rowidx.size();
+    A.n = B.n;
+    A.perm = (const int32_t *)take(B.perm.size() * 4);
+    A.colptr = (const int32_t *)take(B.colptr.size() * 4);
+    A.rowidx = (const int32_t *)take(B.rowidx.size() * 4);
+    A.upoff = (const int32_t *)take(B.upoff.size() * 4);
+    A.up = (const int4 *)take(B.up.size() * 16);
+    A.rowoff = (const int32_t *)take(B.rowoff.size() * 4);
+    A.row = (const int2 *)take(B.row.size() * 8);
+    A.lvl_cols = (const int32_t *)take(B.lvl_cols.size() * 4);
+    A.L = (double *)take(nl * 36 * 8);
+    A.D = (double *)take(n * 6 * 8);
+    A.y = (double *)take(n * 6 * 8);
+    A.xs = (double *)take(n * 6 * 8);
+    return off;
+}
+
 // (re)build an orbg_ba_graph's Schur structure from its host edges and the stored fixed
 // flags, and upload it in stream order (no host synchronisation unless the buffer grows)
 static int ba_graph_schur_replan(orbg_ctx *c, orbg_ba_graph *g)
@@ -3041,8 +3075,21 @@ static int ba_graph_schur_replan(orbg_ctx *c, orbg_ba_graph *g)
     }
     SchurPlanHost P;
     build_schur_plan(g->npose, g->npoint, ne, ep.data(), eq.data(), ea.data(), g->fixed.data(), P);
+    BsPlanHost B;
+    BsArgs BA{};
+    if (g->sparse) {
+        if (int rc = build_bsolve_plan(P, B)) {
+            g->schur_planned = false;  // (set_active past a cap: the old plan is another active set's)
+            return rc;
+        }
+        // no dense system: the blocks of S go to L's pattern (SchurArgs.S = BsArgs.L below)
+        P.nseg = P.max_seg = 0;
+        P.seg_lo.assign(1, 0);
+        P.seg_soff.assign(1, 0);
+    }
     SchurArgs A{};
-    const size_t bytes = schur_layout(P, ne, nullptr, A, nullptr);
+    const size_t sbytes = schur_layout(P, ne, nullptr, A, nullptr);
+    const size_t bytes = sbytes + (g->sparse ? bsolve_layout(B, nullptr, BA) : 0);
     if (bytes > g->schur_bytes) {
         if (g->d_schur) {
             HIPCHK(hipStreamSynchronize(c->stream));  // a queued solve may still read it
@@ -3050,13 +3097,43 @@ static int ba_graph_schur_replan(orbg_ctx *c, orbg_ba_graph *g)
         }
         g->d_schur = nullptr;
         g->schur_bytes = 0;
-        if (hipMalloc((void **)&g->d_schur, bytes) != hipSuccess)
+        if (hipMalloc((void **)&g->d_schur, bytes) != hipSuccess) {
+            g->schur_planned = false;  // the old plan's arrays are gone
             return set_err(ORBG_ENOMEM, "Schur structure %zu bytes", bytes);
+        }
         g->schur_bytes = bytes;
     }
     schur_layout(P, ne, g->d_schur, A, nullptr);
     int rc = schur_upload(P, A, c->stream);
     if (rc) return rc;
+    if (g->sparse) {
+        bsolve_layout(B, g->d_schur + sbytes, BA);
+        auto up = [&](const void *dst, const void *src, size_t n) -> int {
+            if (n) HIPCHK(hipMemcpyAsync((void *)dst, src, n, hipMemcpyHostToDevice, c->stream));
+            return ORBG_OK;
+        };
+        // (pageable sources: each copy has left the host buffer when the call returns)
+        if ((rc = up(BA.perm, B.perm.data(), B.perm.size() * 4)) ||
+            (rc = up(BA.colptr, B.colptr.data(), B.colptr.size() * 4)) ||
+            (rc = up(BA.rowidx, B.rowidx.data(), B.rowidx.size() * 4)) ||
+            (rc = up(BA.upoff, B.upoff.data(), B.upoff.size() * 4)) ||
+            (rc = up(BA.up, B.up.data(), B.up.size() * 16)) ||
+            (rc = up(BA.rowoff, B.rowoff.data(), B.rowoff.size() * 4)) ||
+            (rc = up(BA.row, B.row.data(), B.row.size() * 8)) ||
+            (rc = up(BA.lvl_cols, B.lvl_cols.data(), B.lvl_cols.size() * 4)) ||
+            (rc = up(A.blk_dst, B.blk_dst.data(), B.blk_dst.size() * 4)))
+            return rc;
+        const int64_t nl = B.n ? B.colptr[B.n] : 0;
+        A.S = BA.L;  // k_schur_points zeroes it (the fill blocks), k_schur_blocks* writes S's
+        A.s_total = 36 * nl;
+        g->bs.a = BA;
+        g->bs.lvl_off = B.lvl_off;
+        g->bs.npar = B.npar;
+        g->bs.ntail = B.ntail;
+        g->bs.nl = nl;
+        g->sinfo = orbg_ba_sparse_info{B.n, (int32_t)B.sblocks, (int32_t)nl, B.nlevel, B.ntail, 0,
+                                       B.n ? (int64_t)B.upoff[nl] : 0};
+    }
     g->sa = A;
     g->schur_planned = true;
     return ORBG_OK;
@@ -3261,7 +3338,25 @@ extern "C" int orbg_ba_graph_schur_plan(orbg_ctx *c, orbg_ba_graph *g, const uin
     HIPCHK(hipSetDevice(c->device));
     g->fixed.assign(std::max(g->npose, 1), 0);
     for (int i = 0; i < g->npose; i++) g->fixed[i] = fixed[i] ? 1 : 0;
+    g->sparse = false;
     return ba_graph_schur_replan(c, g);
+}
+
+extern "C" int orbg_ba_graph_schur_plan_sparse(orbg_ctx *c, orbg_ba_graph *g, const uint8_t *fixed,
+                                               orbg_ba_sparse_info *info)
+{
+    if (!c || !g) return set_err(ORBG_EINVAL, "ctx / graph is NULL");
+    if (g->npose && !fixed) return set_err(ORBG_EINVAL, "fixed is NULL");
+    if (g->device != c->device) return set_err(ORBG_EINVAL, "graph of another device");
+    HIPCHK(hipSetDevice(c->device));
+    g->fixed.assign(std::max(g->npose, 1), 0);
+    for (int i = 0; i < g->npose; i++) g->fixed[i] = fixed[i] ? 1 : 0;
+    g->sparse = true;
+    g->schur_planned = false;  // a failed plan leaves none
+    const int rc = ba_graph_schur_replan(c, g);
+    if (rc) return rc;
+    if (info) *info = g->sinfo;
+    return ORBG_OK;
 }
 
 extern "C" int orbg_ba_graph_schur_solve(orbg_ctx *c, orbg_ba_graph *g, double lambda,
@@ -3288,7 +3383,12 @@ extern "C" int orbg_ba_graph_schur_solve(orbg_ctx *c, orbg_ba_graph *g, double l
     A.ok = d_ok;
     A.dx_pose = d_dx_pose;
     A.dx_point = d_dx_point;
-    const int rc = launch_schur(c->stream, A, &c->prof);
+    BsLaunch *bs = g->sparse ? &g->bs : nullptr;
+    if (bs) {
+        bs->a.x = A.x;
+        bs->a.ok = d_ok;
+    }
+    const int rc = launch_schur(c->stream, A, &c->prof, bs);
     if (rc) return set_err(rc, "schur launch failed");
     return ORBG_OK;
 }
@@ -3585,6 +3685,77 @@ extern "C" int orbg_local_ba_optimize(orbg_ctx *c, orbg_pose *poses, int npose, 
         HIPCHK(hipMemcpyAsync(points, d_points, (size_t)npoint * 24, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (rep) *rep = R;
+    return ORBG_OK;
+}
+
+// Optimizer::BundleAdjustment's optimisation (Optimizer.cc:113-247) from host arrays: see
+// include/orbg.h
+extern "C" int orbg_global_ba_optimize(orbg_ctx *c, orbg_pose *poses, int npose, double *points,
+                                       int npoint, const orbg_edge *edges, int nedge,
+                                       int iterations, const orbg_lm_control *control,
+                                       orbg_gba_report *rep)
+{
+    if (!c) return set_err(ORBG_EINVAL, "ctx is NULL");
+    if (npose < 0 || npoint < 0 || nedge < 0 || iterations < 0)
+        return set_err(ORBG_EINVAL, "negative size");
+    if ((npose && !poses) || (npoint && !points) || (nedge && !edges))
+        return set_err(ORBG_EINVAL, "NULL array");
+    orbg_gba_report R{};
+    if (nedge == 0) {  // initializeOptimization of an empty graph fails: nothing optimised
+        if (rep) *rep = R;
+        return ORBG_OK;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    orbg_ba_graph *g = nullptr;
+    int rc = orbg_ba_graph_create(c, edges, nedge, npose, npoint, &g);
+    if (rc) return rc;
+    uint8_t *dmem = nullptr;
+    struct Guard {
+        orbg_ba_graph *g;
+        uint8_t **m;
+        ~Guard()
+        {
+            if (*m) hipFree(*m);
+            if (g) orbg_ba_graph_destroy(g);
+        }
+    } guard{g, &dmem};
+    const size_t np = (size_t)std::max(npose, 1), nq = (size_t)std::max(npoint, 1);
+    const size_t o_q = al256(np * sizeof(orbg_pose));
+    HIPCHK(hipMalloc((void **)&dmem, o_q + al256(nq * 24)));
+    orbg_pose *d_poses = (orbg_pose *)dmem;
+    double *d_points = (double *)(dmem + o_q);
+    hipStream_t st = c->stream;
+    if (npose)
+        HIPCHK(hipMemcpyAsync(d_poses, poses, (size_t)npose * sizeof(orbg_pose), hipMemcpyHostToDevice, st));
+    if (npoint)
+        HIPCHK(hipMemcpyAsync(d_points, points, (size_t)npoint * 24, hipMemcpyHostToDevice, st));
+    std::vector<uint8_t> fixed(np, 0);
+    for (int i = 0; i < npose; i++) fixed[i] = poses[i].fixed ? 1 : 0;
+    if ((rc = orbg_ba_graph_schur_plan_sparse(c, g, fixed.data(), &R.plan))) return rc;
+    if ((rc = orbg_ba_graph_optimize_ctl(c, g, d_poses, d_points, iterations, control, &R.lm)))
+        return rc;
+    if (npose)
+        HIPCHK(hipMemcpyAsync(poses, d_poses, (size_t)npose * sizeof(orbg_pose), hipMemcpyDeviceToHost, st));
+    if (npoint)
+        HIPCHK(hipMemcpyAsync(points, d_points, (size_t)npoint * 24, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (rep) *rep = R;
+    return ORBG_OK;
+}
+
+extern "C" int orbg_gba_correct_points_device(orbg_ctx *c, const float *d_Tcw_before,
+                                              const float *d_Twc_after, int nkf,
+                                              const int32_t *d_ref, const float *d_points, int n,
+                                              float *d_out)
+{
+    if (!c) return set_err(ORBG_EINVAL, "ctx is NULL");
+    if (nkf < 0 || n < 0) return set_err(ORBG_EINVAL, "negative size");
+    if (n == 0) return ORBG_OK;
+    if (!d_ref || !d_points || !d_out || (nkf && (!d_Tcw_before || !d_Twc_after)))
+        return set_err(ORBG_EINVAL, "NULL device array");
+    HIPCHK(hipSetDevice(c->device));
+    if (launch_gba_correct_points(c->stream, d_Tcw_before, d_Twc_after, nkf, d_ref, d_points, n, d_out))
+        return set_err(ORBG_EIO, "k_gba_correct_points launch failed");
     return ORBG_OK;
 }
 

@@ -49,6 +49,7 @@ struct SchurArgs {
     const int2 *blk_pairs;
     const int32_t *blk_i1, *blk_i2, *blk_seg;  // [nblk]
     const int32_t *blk_order;          // [nblk] k_schur_blocks' dispatch order (a permutation)
+    const int32_t *blk_dst;            // sparse plan only (bsolve_args.h): [nblk] 2 * slot + transposed
     const int32_t *pose_off, *pose_slots;      // active slots per free pose, landmark order
     const int32_t *seg_lo;             // [nseg + 1] free-index range of each segment
     const int64_t *seg_soff;           // [nseg + 1] offset (doubles) of its dense matrix in S
@@ -58,14 +59,18 @@ struct SchurArgs {
     double lambda;
     // scratch
     double *rec;                       // [nslot][24]: B D^-1 (row-major 6x3), B D^-1 b_l (6)
-    double *S;                         // s_total doubles: the segments' dense systems
+    double *S;                         // s_total doubles: the segments' dense systems (sparse
+                                       // plan: the 6x6 blocks of L's pattern, BsArgs.L)
     int64_t s_total;                   // = seg_soff[nseg] (host copy)
     double *x;                         // [6 nfree]  b_schur, then x_p
     int32_t *ok;                       // 1 unless some segment hit a zero / non-finite pivot
     double *dx_pose, *dx_point;        // outputs [npose][6], [npoint][3]
 };
 
-struct Prof;  // the context's profiler (orbg_ctx.h)
-int launch_schur(hipStream_t st, const SchurArgs &A, Prof *prof);
+struct Prof;      // the context's profiler (orbg_ctx.h)
+struct BsLaunch;  // bsolve_args.h
+// bs != nullptr: the sparse plan -- the blocks of S go to their slots of L's pattern and the
+// block-sparse factorisation (launch_bsolve) takes k_schur_ldlt's place
+int launch_schur(hipStream_t st, const SchurArgs &A, Prof *prof, const BsLaunch *bs = nullptr);
 
 }  // namespace orbg

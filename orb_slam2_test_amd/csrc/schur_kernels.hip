@@ -14,7 +14,9 @@
 //                    instruction's four 4x4 blocks, K = the 3 inner terms + a zero), pair t
 //                    into accumulator chain t % 16 = wave t % 16 of the workgroup, the chains
 //                    combined by a pairwise tree; written upper + mirrored into the
-//                    segment's dense system
+//                    segment's dense system (<true>, the sparse plan of a global BA: once
+//                    into the block's slot of L's pattern, bsolve_kernels.hip, which then
+//                    takes k_schur_ldlt's place)
 //   k_schur_rhs      wave per free pose: b_schur = b_p - sum B D^-1 b_l over its landmarks
 //                    (64 lane partials in list order, xor butterfly)
 //   k_schur_ldlt     workgroup per segment: right-looking dense LDLT (no pivoting; each
@@ -33,6 +35,7 @@
 #include "../../include/orbg.h"
 #include "orbg_device.h"
 #include "schur_args.h"
+#include "bsolve_args.h"
 #include "orbg_launch.h"
 
 #pragma clang fp contract(off)
@@ -121,6 +124,33 @@ __global__ __launch_bounds__(256) void k_schur_points(SchurArgs A)
         if (keep[i / (SCHUR_REC / 2)]) out[i] = rec[i];
 }
 
+// entry (ro, co) of upper block bk = (i1 <= i2) to its place.  Dense plan: the segment's
+// matrix, upper + mirrored.  Sparse plan (bsolve_args.h): the block's slot of L's pattern, once,
+// transposed when the elimination order puts i2 first; a diagonal block as upper + mirror (the
+// factorisation reads its lower triangle).
+template <bool SPARSE>
+__device__ __forceinline__ void schur_store(const SchurArgs &A, int bk, int i1, int i2, int ro,
+                                            int co, double v)
+{
+    if (ro >= 6 || co >= 6) return;
+    if (SPARSE) {
+        const int d = A.blk_dst[bk];
+        double *B = A.S + (size_t)(d >> 1) * 36;
+        if (i1 != i2) {
+            B[(d & 1) ? 6 * co + ro : 6 * ro + co] = v;
+        } else if (ro <= co) {
+            B[6 * ro + co] = v;
+            B[6 * co + ro] = v;
+        }
+        return;
+    }
+    const int sg = A.blk_seg[bk], lo = A.seg_lo[sg], n = 6 * (A.seg_lo[sg + 1] - lo);
+    double *S = A.S + A.seg_soff[sg];
+    const int r = 6 * (i1 - lo) + ro, cc = 6 * (i2 - lo) + co;
+    if (i1 != i2 || ro <= co) S[(size_t)r * n + cc] = v;  // upper
+    if (i1 != i2 || ro < co) S[(size_t)cc * n + r] = v;   // lower = mirror of the upper
+}
+
 // workgroup per upper block, wave u = accumulator chain u: the block's pairs t = u, u + 16, ...
 // (landmark order) by one v_mfma_f64_4x4x4f64 each into that wave's chain (16 chains: a
 // diagonal block sums every landmark of its pose, ~3000 in a KITTI window, so its gathers
@@ -136,6 +166,7 @@ __global__ __launch_bounds__(256) void k_schur_points(SchurArgs A)
 #ifndef SCHUR_BATCH
 #define SCHUR_BATCH 11  // pairs per step and chain (11: 62 VGPRs, two 16-wave workgroups per CU; 16: 82)
 #endif  // waves per block workgroup = accumulator chains (the oracle's)
+template <bool SPARSE>
 __global__ __launch_bounds__(64 * SCHUR_CHAINS) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_schur_blocks(SchurArgs A)
 {
     __shared__ double tile[SCHUR_CHAINS][64];
@@ -143,8 +174,7 @@ __global__ __launch_bounds__(64 * SCHUR_CHAINS) __attribute__((amdgpu_waves_per_
     // window's records and H_pl are fetched into one L2 rather than into all eight
     const int lane = threadIdx.x & 63, u = threadIdx.x >> 6,
               bk = A.blk_order[ORBG_SCHUR_XCD ? xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x];
-    const int i1 = A.blk_i1[bk], i2 = A.blk_i2[bk], sg = A.blk_seg[bk];
-    const int lo = A.seg_lo[sg], n = 6 * (A.seg_lo[sg + 1] - lo);
+    const int i1 = A.blk_i1[bk], i2 = A.blk_i2[bk];
     const int k = lane >> 4, b = (lane >> 2) & 3, t = lane & 3;
     const int ra = 4 * (b >> 1) + t, cb = 4 * (b & 1) + t;  // A's row, B's column
     const bool va = ra < 6 && k < 3, vb = k < 3 && cb < 6;
@@ -191,12 +221,7 @@ __global__ __launch_bounds__(64 * SCHUR_CHAINS) __attribute__((amdgpu_waves_per_
 #pragma unroll
     for (int i = 0; i < 4; i++) b4[i] = a8[2 * i] + a8[2 * i + 1];
     const double v = (b4[0] + b4[1]) + (b4[2] + b4[3]);
-    if (ro < 6 && co < 6) {
-        double *S = A.S + A.seg_soff[sg];
-        const int r = 6 * (i1 - lo) + ro, cc = 6 * (i2 - lo) + co;
-        if (i1 != i2 || ro <= co) S[(size_t)r * n + cc] = v;  // upper
-        if (i1 != i2 || ro < co) S[(size_t)cc * n + r] = v;   // lower = mirror of the upper
-    }
+    schur_store<SPARSE>(A, bk, i1, i2, ro, co, v);
 }
 
 // k_schur_blocks with its operands staged: the same chains, pairs and MFMAs (so the same
@@ -212,14 +237,14 @@ __global__ __launch_bounds__(64 * SCHUR_CHAINS) __attribute__((amdgpu_waves_per_
 #endif
 #define SCHUR_SPIECES (2 * 9 * SCHUR_SBATCH)
 #define SCHUR_SLOADS ((SCHUR_SPIECES + 63) / 64)
+template <bool SPARSE>
 __global__ __launch_bounds__(64 * SCHUR_CHAINS) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_schur_blocks_lds(SchurArgs A)
 {
     __shared__ double tile[SCHUR_CHAINS][64];
     __shared__ double2 stage[SCHUR_CHAINS][SCHUR_SPIECES];
     const int lane = threadIdx.x & 63, u = threadIdx.x >> 6,
               bk = A.blk_order[ORBG_SCHUR_XCD ? xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x];
-    const int i1 = A.blk_i1[bk], i2 = A.blk_i2[bk], sg = A.blk_seg[bk];
-    const int lo = A.seg_lo[sg], n = 6 * (A.seg_lo[sg + 1] - lo);
+    const int i1 = A.blk_i1[bk], i2 = A.blk_i2[bk];
     const int k = lane >> 4, b = (lane >> 2) & 3, t = lane & 3;
     const int ra = 4 * (b >> 1) + t, cb = 4 * (b & 1) + t;  // A's row, B's column
     const bool va = ra < 6 && k < 3, vb = k < 3 && cb < 6;
@@ -280,12 +305,7 @@ __global__ __launch_bounds__(64 * SCHUR_CHAINS) __attribute__((amdgpu_waves_per_
 #pragma unroll
     for (int i = 0; i < 4; i++) b4[i] = a8[2 * i] + a8[2 * i + 1];
     const double v = (b4[0] + b4[1]) + (b4[2] + b4[3]);
-    if (ro < 6 && co < 6) {
-        double *S = A.S + A.seg_soff[sg];
-        const int r = 6 * (i1 - lo) + ro, cc = 6 * (i2 - lo) + co;
-        if (i1 != i2 || ro <= co) S[(size_t)r * n + cc] = v;
-        if (i1 != i2 || ro < co) S[(size_t)cc * n + r] = v;
-    }
+    schur_store<SPARSE>(A, bk, i1, i2, ro, co, v);
 }
 
 // b_schur = b_p - coefficients, per free pose: the landmark-ordered B D^-1 b_l terms summed
@@ -503,7 +523,36 @@ __global__ void k_schur_backsub(SchurArgs A)
     for (int r = 0; r < 3; r++) xl[r] = (Di[r * 3] * cl[0] + Di[r * 3 + 1] * cl[1]) + Di[r * 3 + 2] * cl[2];
 }
 
-int launch_schur(hipStream_t st, const SchurArgs &A, Prof *prof)
+// the dense plan's per-segment factorisation and solves
+static int launch_schur_ldlt(hipStream_t st, const SchurArgs &A, Prof *prof)
+{
+    const int T = 256;
+    hipEvent_t ev = nullptr;
+    const int n = 6 * A.max_seg;
+    const size_t lds = ((size_t)n * n + n) * sizeof(double);
+    prof_begin(prof, st, "schur_ldlt", &ev);
+    static const int ldlt_wave = getenv("ORBG_SCHUR_LDLT_WAVE") ? atoi(getenv("ORBG_SCHUR_LDLT_WAVE"))
+                                                                : ORBG_SCHUR_LDLT_WAVE;
+    if (ldlt_wave && lds <= 160 * 1024 - 64) {
+        if (lds > 64 * 1024 &&
+            hipFuncSetAttribute((const void *)k_schur_ldlt_wave,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return ORBG_EIO;
+        hipLaunchKernelGGL(k_schur_ldlt_wave, dim3(A.nseg), dim3(64), lds, st, A);
+    } else if (lds <= 160 * 1024 - 64) {
+        if (lds > 64 * 1024 &&
+            hipFuncSetAttribute((const void *)k_schur_ldlt<true>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return ORBG_EIO;
+        hipLaunchKernelGGL(k_schur_ldlt<true>, dim3(A.nseg), dim3(T), lds, st, A);
+    } else {
+        hipLaunchKernelGGL(k_schur_ldlt<false>, dim3(A.nseg), dim3(T), 0, st, A);
+    }
+    prof_end(prof, st, "schur_ldlt", ev);
+    return ORBG_OK;
+}
+
+int launch_schur(hipStream_t st, const SchurArgs &A, Prof *prof, const BsLaunch *bs)
 {
     const int T = 256;
     hipEvent_t ev = nullptr;
@@ -516,35 +565,21 @@ int launch_schur(hipStream_t st, const SchurArgs &A, Prof *prof)
         static const int stage_env = getenv("ORBG_SCHUR_STAGE") ? atoi(getenv("ORBG_SCHUR_STAGE")) : 1;
         // (b_schur folded into this launch as trailing workgroups measured slower: 0.24 ms
         // against 0.110 + 0.028, r06e)
-        if (stage_env && (A.hpl_stride % 2) == 0)
-            hipLaunchKernelGGL(k_schur_blocks_lds, dim3(A.nblk), dim3(64 * SCHUR_CHAINS), 0, st, A);
+        const bool staged = stage_env && (A.hpl_stride % 2) == 0;
+        const dim3 bg(A.nblk), bt(64 * SCHUR_CHAINS);
+        if (bs && staged)
+            hipLaunchKernelGGL(k_schur_blocks_lds<true>, bg, bt, 0, st, A);
+        else if (bs)
+            hipLaunchKernelGGL(k_schur_blocks<true>, bg, bt, 0, st, A);
+        else if (staged)
+            hipLaunchKernelGGL(k_schur_blocks_lds<false>, bg, bt, 0, st, A);
         else
-            hipLaunchKernelGGL(k_schur_blocks, dim3(A.nblk), dim3(64 * SCHUR_CHAINS), 0, st, A);
+            hipLaunchKernelGGL(k_schur_blocks<false>, bg, bt, 0, st, A);
         prof_end(prof, st, "schur_blocks", ev);
         prof_begin(prof, st, "schur_rhs", &ev);
         hipLaunchKernelGGL(k_schur_rhs, dim3((A.nfree + 3) / 4), dim3(T), 0, st, A);
         prof_end(prof, st, "schur_rhs", ev);
-        const int n = 6 * A.max_seg;
-        const size_t lds = ((size_t)n * n + n) * sizeof(double);
-        prof_begin(prof, st, "schur_ldlt", &ev);
-        static const int ldlt_wave = getenv("ORBG_SCHUR_LDLT_WAVE") ? atoi(getenv("ORBG_SCHUR_LDLT_WAVE"))
-                                                                    : ORBG_SCHUR_LDLT_WAVE;
-        if (ldlt_wave && lds <= 160 * 1024 - 64) {
-            if (lds > 64 * 1024 &&
-                hipFuncSetAttribute((const void *)k_schur_ldlt_wave,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-                return ORBG_EIO;
-            hipLaunchKernelGGL(k_schur_ldlt_wave, dim3(A.nseg), dim3(64), lds, st, A);
-        } else if (lds <= 160 * 1024 - 64) {
-            if (lds > 64 * 1024 &&
-                hipFuncSetAttribute((const void *)k_schur_ldlt<true>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-                return ORBG_EIO;
-            hipLaunchKernelGGL(k_schur_ldlt<true>, dim3(A.nseg), dim3(T), lds, st, A);
-        } else {
-            hipLaunchKernelGGL(k_schur_ldlt<false>, dim3(A.nseg), dim3(T), 0, st, A);
-        }
-        prof_end(prof, st, "schur_ldlt", ev);
+        if (int rc = bs ? launch_bsolve(st, *bs, prof) : launch_schur_ldlt(st, A, prof)) return rc;
     }
     const int m = std::max(A.npoint, A.npose * 6);
     prof_begin(prof, st, "schur_backsub", &ev);

@@ -373,6 +373,102 @@ def CorrectMapPoints(Scw, Siw, ref, points, device=0):
     return d_o.cpu().numpy().reshape(n, 3)
 
 
+TH_HUBER_MONO_GBA = float(np.float32(math.sqrt(5.99)))   # const float thHuber2D (Optimizer.cc:157)
+TH_HUBER_STEREO_GBA = float(np.float32(math.sqrt(7.815)))  # const float thHuber3D (:158)
+
+
+def _stop_flag_address(stop_flag):
+    if stop_flag is None:
+        return None
+    if isinstance(stop_flag, np.ndarray):
+        assert stop_flag.dtype == np.uint8 and stop_flag.size >= 1
+        return stop_flag.ctypes.data
+    return L.C.addressof(stop_flag)
+
+
+def GlobalBundleAdjustment(poses, points, edges, iterations, stop_flag=None, device=0):
+    """The optimisation of Optimizer::BundleAdjustment (Optimizer.cc:113-247,
+    orbg_global_ba_optimize): POSE_DTYPE poses (fixed = 1 for the keyframe with mnId 0),
+    points [n, 3], EDGE_DTYPE edges (one per observation; huber_delta TH_HUBER_*_GBA and
+    robust = bRobust), optimize(iterations) under `stop_flag` (a one-byte host buffer, as
+    DeviceLBA.optimize_ctl).  Returns (poses, points, report): copies with the estimates (a
+    fixed pose and a point without an active edge unchanged) and a dict of the LM report and
+    the sparse plan's figures."""
+    poses = np.array(poses, L.POSE_DTYPE)
+    points = np.array(points, np.float64).reshape(-1, 3)
+    e = np.ascontiguousarray(edges, L.EDGE_DTYPE)
+    rep = L.GbaReport()
+    ctl = L.LmControl()
+    ctl.force_stop = _stop_flag_address(stop_flag)
+    L.check(L.lib().orbg_global_ba_optimize(_ctx(device).handle, L.ptr(poses), len(poses),
+                                            L.ptr(points), len(points), L.ptr(e), len(e),
+                                            int(iterations), L.C.byref(ctl), L.C.byref(rep)),
+            "orbg_global_ba_optimize")
+    r = rep.lm
+    report = dict(iterations=r.iterations, trials=r.trials, terminated=r.terminated,
+                  initial_chi2=r.initial_chi2, final_chi2=r.final_chi2, plan=rep.plan.as_dict(),
+                  **{"lambda": r.lam})
+    return poses, points, report
+
+
+def CorrectPointsGBA(Tcw_before, Twc_after, ref, points, device=0):
+    """The map points global BA did not optimise (LoopClosing.cc:1101-1113,
+    orbg_gba_correct_points_device): Rwc (Rcw X + tcw) + twc per point with its reference
+    keyframe r = ref[p]: Tcw_before[r] = mTcwBefGBA, Twc_after[r] = GetPoseInverse() (float
+    [n, 3, 4] or [n, 4, 4]); ref[p] < 0 leaves the point as it is.  Returns float32 [n, 3]."""
+    import torch
+    Tb = np.ascontiguousarray(np.asarray(Tcw_before, np.float32)[:, :3, :4])
+    Ta = np.ascontiguousarray(np.asarray(Twc_after, np.float32)[:, :3, :4])
+    if len(Tb) != len(Ta):
+        raise ValueError("Tcw_before and Twc_after differ in length")
+    ref = np.ascontiguousarray(ref, np.int32).reshape(-1)
+    pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    if len(ref) != len(pts):
+        raise ValueError("one reference index per point")
+    n = len(pts)
+    if n == 0:
+        return np.zeros((0, 3), np.float32)
+
+    def up(a):
+        return torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).cuda()
+    c_ = _ctx(device)
+    d_b, d_a, d_r, d_p = up(Tb), up(Ta), up(ref), up(pts)
+    d_o = torch.zeros(n * 3, dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    L.check(L.lib().orbg_gba_correct_points_device(c_.handle, d_b.data_ptr(), d_a.data_ptr(), len(Tb),
+                                                   d_r.data_ptr(), d_p.data_ptr(), n, d_o.data_ptr()),
+            "orbg_gba_correct_points_device")
+    c_.sync()
+    return d_o.cpu().numpy().reshape(n, 3)
+
+
+def sparse_symbolic(edges, npose, npoint, fixed):
+    """orbg_ba_sparse_symbolic (host only, no GPU): the symbolic factorisation a sparse Schur
+    plan makes for these edges (`pose`, `point`, `active` fields) and fixed flags.  Returns
+    (order, colptr, rowidx, level, info): the free poses in elimination order, L by columns in
+    elimination positions (rows ascending, the diagonal first), each column's level, and the
+    info dict."""
+    ep = np.ascontiguousarray(edges["pose"], np.int32)
+    eq = np.ascontiguousarray(edges["point"], np.int32)
+    ea = np.ascontiguousarray(np.asarray(edges["active"]) != 0, np.uint8)
+    f = np.ascontiguousarray(np.asarray(fixed) != 0, np.uint8)
+    if len(f) != npose:
+        raise ValueError("one fixed flag per pose")
+    info = L.BaSparseInfo()
+    args = (L.ptr(ep), L.ptr(eq), L.ptr(ea), len(ep), int(npose), int(npoint), L.ptr(f))
+    L.check(L.lib().orbg_ba_sparse_symbolic(*args, None, None, None, 0, None, L.C.byref(info)),
+            "orbg_ba_sparse_symbolic")
+    n, nl = info.nfree, info.l_blocks
+    order = np.zeros(max(n, 1), np.int32)
+    colptr = np.zeros(n + 1, np.int32)
+    rowidx = np.zeros(max(nl, 1), np.int32)
+    level = np.zeros(max(n, 1), np.int32)
+    L.check(L.lib().orbg_ba_sparse_symbolic(*args, L.ptr(order), L.ptr(colptr), L.ptr(rowidx), nl,
+                                            L.ptr(level), L.C.byref(info)),
+            "orbg_ba_sparse_symbolic")
+    return order[:n], colptr, rowidx[:nl], level[:n], info.as_dict()
+
+
 def vertex_csr(edges, field, nvert):
     """Edge lists per vertex (CSR): (off[nvert+1], edge ids[nedge]) int32, edges in input
     order within a vertex -- the layout orbg_ba_linearize_device reduces blocks over."""
@@ -480,19 +576,31 @@ class DeviceLBA:
         L.check(L.lib().orbg_ba_graph_set_active(self.ctx.handle, self.graph, a.ctypes.data),
                 "orbg_ba_graph_set_active")
 
-    def schur_plan(self, fixed):
+    def schur_plan(self, fixed, sparse=False):
         """orbg_ba_graph_schur_plan: the Schur structure of the graph for the free poses
-        (fixed[i] != 0: g2o's fixed vertex), built once; set_active rebuilds it."""
+        (fixed[i] != 0: g2o's fixed vertex), built once; set_active rebuilds it.  sparse=True:
+        orbg_ba_graph_schur_plan_sparse, the block-sparse reduced camera system of a global
+        BA; returns the plan's info dict (nfree, s_blocks, l_blocks, levels, tail_columns,
+        updates)."""
         import torch
         if self.graph is None:
             raise ValueError("schur_plan needs a DeviceLBA built with graph=True")
         f = np.ascontiguousarray(np.asarray(fixed) != 0, np.uint8)
-        L.check(L.lib().orbg_ba_graph_schur_plan(self.ctx.handle, self.graph, f.ctypes.data),
-                "orbg_ba_graph_schur_plan")
+        info = None
+        if sparse:
+            si = L.BaSparseInfo()
+            L.check(L.lib().orbg_ba_graph_schur_plan_sparse(self.ctx.handle, self.graph,
+                                                            f.ctypes.data, L.C.byref(si)),
+                    "orbg_ba_graph_schur_plan_sparse")
+            info = si.as_dict()
+        else:
+            L.check(L.lib().orbg_ba_graph_schur_plan(self.ctx.handle, self.graph, f.ctypes.data),
+                    "orbg_ba_graph_schur_plan")
         dev = self.d_hpose.device
         self.d_dx_pose = torch.zeros((self.np, 6), dtype=torch.float64, device=dev)
         self.d_dx_point = torch.zeros((self.nq, 3), dtype=torch.float64, device=dev)
         self.d_ok = torch.zeros(1, dtype=torch.int32, device=dev)
+        return info
 
     def schur_solve(self, lam):
         """BlockSolver<6,3>::solve on the device blocks of the last build_system()
