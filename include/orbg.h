@@ -76,6 +76,10 @@
  *                                     NonCorrectedSim3, CorrectedSim3, LoopConnections,
  *                                     bFixScale)'s optimisation and write-back arithmetic
  *                                     src/Optimizer.cc:1021-1324 (LoopClosing.cc:914)
+ *   orbg_initialize ................. Initializer(ReferenceFrame, sigma, iterations) +
+ *                                     Initialize(CurrentFrame, vMatches12, R21, t21, vP3D,
+ *                                     vbTriangulated)  src/Initializer.cc:34-1270
+ *                                     (Tracking::MonocularInitialization, Tracking.cc:588-676)
  *
  * Batched, device-resident entry points (orbg_*_device) run the same kernels over many
  * frames at once; they exist for the batched-sequence mode and the bench.
@@ -1687,6 +1691,149 @@ int orbg_global_ba_optimize(orbg_ctx *ctx, orbg_pose *poses, int npose, double *
 int orbg_gba_correct_points_device(orbg_ctx *ctx, const float *d_Tcw_before,
                                    const float *d_Twc_after, int nkf, const int32_t *d_ref,
                                    const float *d_points, int n, float *d_out);
+
+/* ---------------- Initializer (Tracking::MonocularInitialization) ----------------
+ * src/Initializer.cc:73-187 and everything below it, batched over frame pairs:
+ * Initializer::Initialize(CurrentFrame, vMatches12, R21, t21, vP3D, vbTriangulated) with
+ * Normalize (:984-1037), FindHomography / FindFundamental (:201-318), ComputeH21 / ComputeF21
+ * (:328-412), CheckHomography / CheckFundamental (:424-597), ReconstructF (:614-722),
+ * ReconstructH (:743-924), Triangulate (:939-973), CheckRT (:1056-1233) and DecomposeE
+ * (:1245-1270).  Frame 1 is the reference frame, frame 2 the current one.
+ *
+ * Inputs per pair: the problem record (mK, sigma = 1.0 and iterations = mMaxIterations = 200 in
+ * Tracking, minParallax = 1.0 and minTriangulated = 50 as :182-184 pass them), the undistorted
+ * keypoints of both frames (orbg_keypoint: only pt is read), vMatches12 [n1] and the
+ * eight-index sets.  The draws are an input, as in the other two solvers: the reference fills
+ * mvSets before either model runs (:131-150), so sets[it][0 .. 8) serves both H and F.
+ *
+ * The device compacts mvMatches12 itself (:94-109): the pairs (i, vMatches12[i]) with
+ * 0 <= vMatches12[i] < n2 in i order (an index >= n2 is no match); N is their number.
+ * Normalize runs over all keys of each frame, matched or not (:210-211).  Departure: the
+ * reference adds in a float running sum; here the four sums of a frame run in fp64 in a fixed
+ * order (256 strided partial sums, then a binary tree) and mean = (float)(sum / n) is rounded
+ * once; sX = (float)(1.0 / meanDevX) and T's entries are the reference's float expressions.
+ *
+ * Per iteration and model: A of ComputeH21 (16 x 9) / ComputeF21 (8 x 9) holds the reference's
+ * float entries (CV_32F products).  From there the linear algebra is fp64 in a fixed operation
+ * order with a fixed number of Jacobi sweeps: vt.row(8) is the eigenvector of least eigenvalue
+ * of the 9 x 9 A^T A (cyclic Jacobi, round-robin ordering), which for F's 8 x 9 system is its
+ * exact null vector, so no basis has to be completed; the 3 x 3 SVDs are one-sided Jacobi.
+ * ComputeF21 drops the least singular value; H21i = T2inv Hn T1 and F21i = T2^T Fn T1 are
+ * rounded to float once, as the reference holds CV_32F; H12i = H21i.inv() is taken of that float
+ * matrix (adjugate over determinant in fp64) and rounded once.  The sign of a null vector is the SVD routine's choice in the
+ * reference: H21i and H12i change sign together and both are only used as ratios of their rows,
+ * F21i enters CheckFundamental as num^2 / (a^2 + b^2), E21's sign leaves the set {(R1, t),
+ * (R2, t), (R1, -t), (R2, -t)} as it is, and A = K^-1 H21 K changes s, U or Vt by a sign that
+ * cancels in s U Rp Vt and permutes the eight (R, t, n) among themselves, so no score, mask or
+ * final result depends on it.  Which hypothesis index holds which motion does depend on the
+ * signs of the 3 x 3 SVDs' vectors; here every right singular vector has its component of
+ * largest magnitude positive, and DecomposeE takes u.col(2) = u.col(0) x u.col(1) and
+ * vt.row(2) = vt.row(0) x vt.row(1) (E has rank 2; det R = +1 follows).  Even so an index is
+ * not comparable with another implementation's: H21's sign reverses each group of four Faugeras
+ * hypotheses, and E21's two nearly equal singular values let two SVD routines pair their
+ * vectors, and so (R1, R2), differently.  R21, t21, the points and the chosen hypothesis'
+ * counts are comparable.
+ *
+ * CheckHomography / CheckFundamental use the reference's float types and comparisons:
+ * w2in1inv = (float)(1.0 / (double)(...)), invSigmaSquare = (float)(1.0 / (double)(sigma *
+ * sigma)), chiSquare > th rejects (a NaN chi-square takes the else branch and makes the score
+ * NaN), th = 5.991 for H, th = 3.841 and thScore = 5.991 for F.  Departure: a score is the
+ * fixed-order fp64 sum of the float terms (lane l of 64 adds matches l, l + 64, ..., chiSquare1's
+ * term before chiSquare2's; the 64 sums combine in a butterfly), rounded to float once.
+ *
+ * An iteration whose set holds an index outside [0, N) or a repeated one, whose matrix is not
+ * finite, or whose H21i is singular scores 0 with an all-zero mask and matrix, and can never
+ * win.  N < 8 runs nothing.
+ *
+ * A model's best iteration is the first strict maximum over scores from 0 (currentScore >
+ * score: a NaN never wins), -1 if none.  RH = SH / (SH + SF) in float; RH > 0.40 selects
+ * ReconstructH (model 1), otherwise ReconstructF (model 2).  Where neither model scored above
+ * 0 the reference dereferences an empty matrix; here model = 0 and success = 0.
+ *
+ * ReconstructF: E21 = K^T F21 K, DecomposeE (t = u.col(2) / |t|, an R of negative determinant
+ * negated), the four hypotheses (R1, t), (R2, t), (R1, -t), (R2, -t), nMinGood = max((int)(0.9
+ * N), minTriangulated), the > 0.7 maxGood similarity count, the if / else-if chain and
+ * parallax > minParallax exactly as written.  ReconstructH: A = K^-1 H21 K, its SVD, s =
+ * det(U) det(Vt), the early return d1 / d2 < 1.00001 || d2 / d3 < 1.00001 in float, the eight
+ * Faugeras hypotheses (in double, rounded once: the float expressions cancel in d1 - d3 and
+ * leave an R that is no rotation when the singular values are close), best and second best with >, and
+ * secondBestGood < 0.75 bestGood && bestParallax >= minParallax && bestGood > minTriangulated
+ * && bestGood > 0.9 N.  The decompositions run in fp64 on the float matrices and U, w, Vt, R, t
+ * are rounded to float once; matrix products of float matrices accumulate in double and round
+ * once (the cv::gemm rule).
+ *
+ * CheckRT: one pass over the chosen model's inliers per hypothesis.  Triangulate's A holds the
+ * reference's float entries; x3D is the right singular vector of least singular value of a
+ * one-sided Jacobi in fp64, (float)(v[k] / v[3]).  Then in float, in the reference's order: the
+ * isfinite test, cosParallax = (float)(dot / (double)(dist1 * dist2)) with dist = (float) of the
+ * double norm, the two depth tests each paired with cosParallax < 0.99998, the two reprojection
+ * tests against th2 = 4 sigma^2, vP3D[first] and nGood, vbGood[first] only when cosParallax <
+ * 0.99998.  The parallax is the order statistic sorted(vCosParallax)[min(50, size - 1)], found
+ * by an exact selection on the floats' ordered bit patterns, then (float)(acos((double)c) *
+ * 180.0 / pi): the arc cosine in double, rounded once (the reference's float acos differs by an
+ * ulp at most).  A cosine above 1 gives NaN and fails >, as in the reference.
+ *
+ * No atomics and no order-dependent float reduction: results are identical run to run and
+ * independent of the batch a pair is put in. */
+#define ORBG_INIT_MAX_N 8192
+typedef struct {
+    float fx, fy, cx, cy;            /* mK */
+    float sigma;                     /* mSigma (Tracking: 1.0) */
+    float min_parallax;              /* minParallax (:182: 1.0) */
+    int32_t min_triangulated;        /* minTriangulated (:182: 50) */
+    int32_t iterations;              /* mMaxIterations (Tracking: 200) */
+} orbg_init_problem;
+typedef struct {
+    int32_t n;                       /* N = mvMatches12.size() */
+    int32_t best_h, best_f;          /* the iteration FindHomography / FindFundamental kept, -1 if none */
+    float SH, SF, RH;
+    int32_t model;                   /* 0 none, 1 ReconstructH, 2 ReconstructF */
+    int32_t success;                 /* Initialize's return value */
+    float R21[9], t21[3];            /* row-major; zero unless success */
+    int32_t hyp;                     /* the hypothesis the decision rule looked at last, -1 if none */
+    int32_t ntriangulated;           /* true entries of vbTriangulated; zero unless success */
+    int32_t ninliers;                /* the N of ReconstructH / ReconstructF: inliers of the chosen model */
+    int32_t nhyp;                    /* hypotheses checked: 8 (H), 4 (F), 0 (none or the early return) */
+    int32_t ngood[8];                /* CheckRT's return value per hypothesis */
+    float parallax[8];
+    float hyp_R[8][9], hyp_t[8][3];  /* vR / vt of ReconstructH; (R1,t1) (R2,t1) (R1,t2) (R2,t2) */
+} orbg_init_result;
+/* One pair from host arrays: kps1[n1] / kps2[n2] = mvKeysUn of the reference / current frame,
+ * matches12[n1], sets[problem->iterations][8].  Outputs: result, p3d[n1][3] (vP3D),
+ * triangulated[n1] (vbTriangulated as bytes), both zero unless success, and, where not NULL,
+ * scores_h / scores_f [iterations], H21 / F21 [iterations][9] (row-major float) and masks_h /
+ * masks_f [iterations][ceil(N / 64)] (bit i % 64 of word i / 64 = vbCurrentInliers[i]).
+ * ORBG_EINVAL for a NULL context or required pointer or a negative size; ORBG_ENOTSUP for n1 or
+ * n2 past 8192 or more than 2^20 iterations.  A set with an index outside [0, N) or a repeated
+ * one is not an error: that iteration scores 0.  Runs the batched kernels with npairs = 1
+ * (bit-identical results).  Synchronises. */
+int orbg_initialize(orbg_ctx *ctx, const orbg_init_problem *problem, const orbg_keypoint *kps1,
+                    int n1, const orbg_keypoint *kps2, int n2, const int32_t *matches12,
+                    const int32_t *sets, orbg_init_result *result, float *p3d,
+                    uint8_t *triangulated, float *scores_h, float *scores_f, float *H21,
+                    float *F21, uint64_t *masks_h, uint64_t *masks_f);
+/* Batched, device memory, as the arrays lie there after extraction and matching: frame f's
+ * keypoints at d_kps + f * frame_stride with d_counts[f] of them (orbg_batch_outputs /
+ * orbg_batch_keys_un), pair p = frames d_f1[p] (reference) and d_f2[p] (current) with
+ * d_matches12 + p * match_stride (orbg_match_outputs: match_stride = frame_cap) and d_sets +
+ * (p * max_its + it) * 8.  cap, the row length of the outputs, is a multiple of 64
+ * (ORBG_ENOTSUP past 8192); n1 is cut at cap and at match_stride; a frame index outside
+ * [0, nframes) has no keys; d_problems[p].iterations is cut at max_its.  Outputs
+ * d_results[npairs], d_p3d[npairs][cap][3] and d_triangulated[npairs][cap] (every byte of the
+ * row is written) and, where not NULL, d_scores_h / _f [npairs][max_its], d_H21 / d_F21
+ * [npairs][max_its][9], d_masks_h / _f [npairs][max_its][cap / 64]; iterations past a pair's
+ * own and mask words past its N are zero.  Context stream, no host synchronisation; the only
+ * allocation is the growth of the context scratch.  Results equal orbg_initialize's. */
+int orbg_initialize_batch_device(orbg_ctx *ctx, const orbg_init_problem *d_problems,
+                                 const orbg_keypoint *d_kps, int frame_stride,
+                                 const int32_t *d_counts, int nframes, const int32_t *d_f1,
+                                 const int32_t *d_f2, const int32_t *d_matches12,
+                                 int match_stride, const int32_t *d_sets, int npairs, int cap,
+                                 int max_its,
+                                 orbg_init_result *d_results, float *d_p3d,
+                                 uint8_t *d_triangulated, float *d_scores_h, float *d_scores_f,
+                                 float *d_H21, float *d_F21, uint64_t *d_masks_h,
+                                 uint64_t *d_masks_f);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,7 @@ DBoW2's vocabulary transform (Frame::ComputeBoW) and score, KeyFrameDatabase's p
 recognition (DetectRelocalizationCandidates, DetectLoopCandidates), Sim3Solver's RANSAC and
 Optimizer::OptimizeSim3 (LoopClosing::ComputeSim3), Optimizer::OptimizeEssentialGraph
 (LoopClosing::CorrectLoop), Optimizer::GlobalBundleAdjustemnt (a block-sparse Schur solve),
+Initializer's H / F RANSAC and two-view reconstruction (Tracking::MonocularInitialization),
 the LBA Schur solve and
 the per-edge arithmetic of Optimizer::LocalBundleAdjustment, as hand-written HIP
 kernels behind the C ABI in include/orbg.h (lib/liborbg.so).  The Python classes mirror
@@ -23,10 +24,11 @@ from .vocabulary import ORBVocabulary, BowVector, FeatureVector  # noqa: F401
 from .keyframedatabase import KeyFrameDatabase  # noqa: F401
 from .sim3solver import Sim3Solver  # noqa: F401
 from .pnpsolver import PnPsolver  # noqa: F401
+from .initializer import Initializer  # noqa: F401
 
 __all__ = ["ORBextractor", "ORBmatcher", "Frame", "MapPointProjections", "StereoFrame", "PoseOptimization", "linearize_local_ba", "OptimizeSim3", "OptimizeSim3Batch",
            "OptimizeEssentialGraph", "CorrectMapPoints", "EssentialGraph",
            "GlobalBundleAdjustment", "CorrectPointsGBA", "sparse_symbolic",
-           "ORBVocabulary", "BowVector", "FeatureVector", "KeyFrameDatabase", "Sim3Solver", "PnPsolver",
+           "ORBVocabulary", "BowVector", "FeatureVector", "KeyFrameDatabase", "Sim3Solver", "PnPsolver", "Initializer",
            "KP_DTYPE",
            "EDGE_DTYPE", "EDGE_OUT_DTYPE", "POSE_DTYPE"]

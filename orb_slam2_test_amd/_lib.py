@@ -79,6 +79,17 @@ PNP_REFINE_DTYPE = np.dtype([("valid", "<i4"), ("count", "<i4"), ("ok", "<i4"), 
                              ("hyp", PNP_HYP_DTYPE)])
 PNP_RESULT_DTYPE = np.dtype([("hit_iter", "<i4"), ("best_iter", "<i4"), ("ninliers", "<i4"),
                              ("nomore", "<i4"), ("refined", "<i4"), ("Tcw", "<f4", 12)])
+# Initializer records (orbg_init_problem, orbg_init_result)
+INIT_MAX_N = 8192
+INIT_PROBLEM_DTYPE = np.dtype([("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"),
+                               ("sigma", "<f4"), ("min_parallax", "<f4"),
+                               ("min_triangulated", "<i4"), ("iterations", "<i4")])
+INIT_RESULT_DTYPE = np.dtype([("n", "<i4"), ("best_h", "<i4"), ("best_f", "<i4"), ("SH", "<f4"),
+                              ("SF", "<f4"), ("RH", "<f4"), ("model", "<i4"), ("success", "<i4"),
+                              ("R21", "<f4", 9), ("t21", "<f4", 3), ("hyp", "<i4"),
+                              ("ntriangulated", "<i4"), ("ninliers", "<i4"), ("nhyp", "<i4"),
+                              ("ngood", "<i4", 8), ("parallax", "<f4", 8),
+                              ("hyp_R", "<f4", (8, 9)), ("hyp_t", "<f4", (8, 3))])
 # OptimizeSim3 records (orbg_sim3opt_problem, orbg_sim3opt_corr, orbg_sim3opt_result)
 SIM3OPT_PROBLEM_DTYPE = np.dtype([("T1w", "<f4", 12), ("T2w", "<f4", 12), ("fx1", "<f4"),
                                   ("fy1", "<f4"), ("cx1", "<f4"), ("cy1", "<f4"), ("fx2", "<f4"),
@@ -430,6 +441,10 @@ def lib():
         "orbg_pnp_solve": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
         "orbg_pnp_solve_batch_device": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp,
                                               vp, vp, i32]),
+        "orbg_initialize": (i32, [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                  vp, vp]),
+        "orbg_initialize_batch_device": (i32, [vp, vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32,
+                                               i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "orbg_optimize_sim3": (i32, [vp, vp, vp, vp, i32, vp, vp]),
         "orbg_optimize_sim3_batch_device": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, i32]),
         "orbg_eg_graph_create": (i32, [vp, vp, i32, i32, i32, P(vp)]),

@@ -1576,5 +1576,87 @@ private:
     std::vector<uint64_t> masks_, rmasks_;
 };
 
+// Initializer(ReferenceFrame, sigma, iterations) + Initialize (Initializer.cc:34-187;
+// Tracking::MonocularInitialization, Tracking.cc:588-676).  The constructor keeps mK and
+// ReferenceFrame.mvKeysUn; Initialize() draws the mMaxIterations eight-point sets from rand()
+// as the reference does (RandomInt with the swap-remove of :135-150; the reference seeds once
+// with srand(0), which stays the caller's) and runs one orbg_initialize: the device compacts
+// mvMatches12, runs both RANSACs, chooses the model and reconstructs.  As in the reference,
+// vP3D and vbTriangulated are assigned only on success, and ReconstructF leaves R21 and t21
+// empty when it fails (:648-649).
+//
+// MatT: cv::Mat (MatT(3, 3, CV_32F), at<float>); Point3fT: cv::Point3f (x, y, z).
+template <class FrameT, class MatT, class Point3fT>
+class Initializer {
+public:
+    Initializer(orbg_ctx *ctx, const FrameT &ReferenceFrame, float sigma = 1.0, int iterations = 200)
+        : ctx_(ctx), keys1_(keys_of(ReferenceFrame.mvKeysUn))
+    {
+        prob_.fx = ReferenceFrame.mK.template at<float>(0, 0);
+        prob_.fy = ReferenceFrame.mK.template at<float>(1, 1);
+        prob_.cx = ReferenceFrame.mK.template at<float>(0, 2);
+        prob_.cy = ReferenceFrame.mK.template at<float>(1, 2);
+        prob_.sigma = sigma;
+        prob_.iterations = iterations;
+        prob_.min_parallax = 1.0f;  // :182-184
+        prob_.min_triangulated = 50;
+    }
+
+    bool Initialize(const FrameT &CurrentFrame, const std::vector<int> &vMatches12, MatT &R21, MatT &t21,
+                    std::vector<Point3fT> &vP3D, std::vector<bool> &vbTriangulated)
+    {
+        const std::vector<orbg_keypoint> keys2 = keys_of(CurrentFrame.mvKeysUn);
+        const int n1 = (int)keys1_.size(), n2 = (int)keys2.size(), its = std::max(prob_.iterations, 0);
+        std::vector<int32_t> m12((size_t)n1, -1);
+        int N = 0;
+        for (int i = 0; i < n1 && i < (int)vMatches12.size(); i++) {
+            m12[i] = vMatches12[i];
+            if (m12[i] >= 0 && m12[i] < n2) N++;
+        }
+        std::vector<int32_t> sets((size_t)std::max(its, 1) * 8, 0), avail;
+        for (int it = 0; it < its && N >= 8; it++) {
+            avail.resize(N);
+            for (int i = 0; i < N; i++) avail[i] = i;
+            for (int j = 0; j < 8; j++) {
+                const int d = (int)avail.size();
+                const int randi = (int)(((double)rand() / ((double)RAND_MAX + 1.0)) * d);
+                sets[(size_t)it * 8 + j] = avail[randi];
+                avail[randi] = avail.back();
+                avail.pop_back();
+            }
+        }
+        std::vector<float> p3d((size_t)std::max(n1, 1) * 3);
+        std::vector<uint8_t> tri((size_t)std::max(n1, 1));
+        check(orbg_initialize(ctx_, &prob_, keys1_.data(), n1, keys2.data(), n2, m12.data(), sets.data(),
+                              &result, p3d.data(), tri.data(), nullptr, nullptr, nullptr, nullptr,
+                              nullptr, nullptr),
+              "orbg_initialize");
+        if (!result.success) {
+            if (result.model == 2) R21 = MatT(), t21 = MatT();
+            return false;
+        }
+        R21 = MatT(3, 3, CV_32F);
+        t21 = MatT(3, 1, CV_32F);
+        for (int r = 0; r < 3; r++) {
+            for (int c = 0; c < 3; c++) R21.template at<float>(r, c) = result.R21[3 * r + c];
+            t21.template at<float>(r) = result.t21[r];
+        }
+        vP3D.resize((size_t)n1);
+        vbTriangulated.assign((size_t)n1, false);
+        for (int i = 0; i < n1; i++) {
+            vP3D[i] = Point3fT(p3d[3 * (size_t)i], p3d[3 * (size_t)i + 1], p3d[3 * (size_t)i + 2]);
+            vbTriangulated[i] = tri[i] != 0;
+        }
+        return true;
+    }
+
+    orbg_init_result result{};  // the record of the last Initialize()
+
+private:
+    orbg_ctx *ctx_;
+    std::vector<orbg_keypoint> keys1_;
+    orbg_init_problem prob_{};
+};
+
 }  // namespace ref
 }  // namespace orbg_compat
