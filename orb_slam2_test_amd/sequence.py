@@ -316,11 +316,17 @@ class BenchStep:
     @property
     def gathered(self):
         """The last step's gathered outputs (stereo: the [2, N] summary; mono: (summary,
-        vnMatches12 rows[, pose rows])), waiting for the collectives if they are in flight."""
+        vnMatches12 rows[, pose rows])), waiting for the collectives if they are in flight.
+        The tensors are assembled on the match stream; the caller's current stream is ordered
+        after that, so they can be read there (.cpu(), kernels) without a further sync."""
         import torch
         if self._pending is not None:
+            cur = torch.cuda.current_stream()
             with torch.cuda.stream(self.mstream):
                 g = tuple(x.result() for x in self._pending)
+            cur.wait_stream(self.mstream)
+            for t in g:
+                t.record_stream(cur)
             self._gathered = g[0] if self.mode == "stereo" else g
             self._pending = None
         return self._gathered

@@ -294,8 +294,9 @@ def test_ba_huber_and_quadratic_form(oracle):
 
 
 def test_stereo_oracle_recovers_synthetic_disparity(oracle):
-    """Sanity of the ComputeStereoMatches restatement (parity unpinned: the reference ships
-    no stereo fixtures): on a rectified synthetic pair with known disparity the matched
+    """Sanity of the ComputeStereoMatches restatement (the reference ships no stereo fixtures;
+    tests/test_matching_ref.py holds the restatement, rule by rule, to the independent
+    statement in tests/ref_matching.py): on a rectified synthetic pair with known disparity the matched
     keypoints' disparities agree with the truth, every depth is bf / disparity, and a
     featureless right image yields no match."""
     from orb_slam2_test_amd import synthetic as S
