@@ -80,6 +80,14 @@
  *                                     Initialize(CurrentFrame, vMatches12, R21, t21, vP3D,
  *                                     vbTriangulated)  src/Initializer.cc:34-1270
  *                                     (Tracking::MonocularInitialization, Tracking.cc:588-676)
+ *   orbg_map_update_connections ..... KeyFrame::UpdateConnections (+ AddConnection,
+ *                                     UpdateBestCovisibles)  src/KeyFrame.cc:160-205, 375-515
+ *   orbg_map_erase_keyframe ......... KeyFrame::SetBadFlag's EraseConnection loop  src/KeyFrame.cc:618-648
+ *   orbg_map_local_keyframes ........ Tracking::UpdateLocalKeyFrames  src/Tracking.cc:1769-1925
+ *   orbg_map_local_points ........... Tracking::UpdateLocalPoints  src/Tracking.cc:1731-1758
+ *                                     (+ SearchLocalPoints' mnLastFrameSeen test, :1644-1683)
+ *   orbg_map_update_normal_and_depth_batch_device
+ *                                     MapPoint::UpdateNormalAndDepth  src/MapPoint.cc:457-518
  *
  * Batched, device-resident entry points (orbg_*_device) run the same kernels over many
  * frames at once; they exist for the batched-sequence mode and the bench.
@@ -1218,6 +1226,180 @@ int orbg_kfdb_detect_loop(orbg_ctx *ctx, orbg_kfdb *db, const int32_t *words,
                           const double *weights, int n, const int32_t *conn, int nconn,
                           float min_score, const int32_t *neigh, int32_t *cand, int cand_cap,
                           int32_t *ncand, int32_t *max_common, int32_t *nscored);
+
+/* ---------------- the covisibility Map: observations, UpdateConnections, the local map ------
+ * The table "which keyframe slot observes which map point", device-resident on ctx's device,
+ * and the reference functions that count, sort and gather over it: KeyFrame::UpdateConnections
+ * (src/KeyFrame.cc:375-515, with AddConnection / EraseConnection / UpdateBestCovisibles),
+ * Tracking::UpdateLocalKeyFrames / UpdateLocalPoints (src/Tracking.cc:1731-1925) and
+ * MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:457-518).  A KeyFrame is a slot in
+ * [0, max_keyframes) as in orbg_kfdb (the same limit, so the tables interchange); a MapPoint is
+ * an id in [0, max_points).
+ *
+ * Pointer order is slot order.  The reference orders std::map<KeyFrame*, ...> and
+ * std::set<KeyFrame*> by pointer value and breaks weight ties with sort(pair<int, KeyFrame*>),
+ * so by pointer too: an order that differs between two runs of the reference itself.  Here
+ * "ascending pointer" is ascending slot, everywhere (the one departure); a
+ * host that allocates its KeyFrames from an arena in slot order gets the reference's behaviour
+ * exactly.
+ *
+ * Observations are the inverse of the keyframe rows: point p is observed by (slot, idx) if and
+ * only if the slot is live and its row holds p at idx.  A point id occurs at most once per row
+ * (mObservations is a map keyed by KeyFrame): the caller's precondition, not checked.  The
+ * caller uploads a KeyFrame's row once ProcessNewKeyFrame has associated it.  The point ->
+ * observations index (CSR, each point's observations in ascending slot order) is rebuilt on the
+ * device by the first query after a row changed.
+ *
+ * State per slot: live / bad / root (mnId == 0) flags, N, the point-id row (-1 = none), each
+ * feature's mvKeysUn[idx].octave, GetCameraCenter(), the parent slot (-1 = none; the children
+ * set is derived from the parents) and mbFirstConnection.  Per point: an orbg_map_point (the
+ * position, normal, min / max distance; isBad() is the absence of ORBG_MP_VALID), mDescriptor
+ * and the reference KeyFrame's slot.  Covisibility: a dense uint16 W[max_keyframes]
+ * [max_keyframes] = mConnectedKeyFrameWeights (0 = not connected; 128 MiB at the limit, 8 MiB at
+ * 2048), each slot's ordered list (mvpOrderedConnectedKeyFrames / mvOrderedWeights; stored,
+ * because it is not a function of the W row: see orbg_map_update_connections_batch_device) and
+ * its first ten entries neigh[max_keyframes][10], -1 padded.  Beside W the ordered lists take
+ * 4 bytes per W entry and the observation index 12 bytes per row entry.
+ * Limits: max_keyframes <= 8192 (the per-slot counters live in LDS as u32: 32 KiB), kf_cap <=
+ * 8192; larger: ORBG_ENOTSUP.  All work runs on the context stream. */
+typedef struct orbg_map orbg_map;
+#define ORBG_MAP_KF_ROOT 1   /* mnId == 0: never gets a parent */
+#define ORBG_MAP_KF_BAD 2    /* isBad() while its row still stands (SetBadFlag under way) */
+int orbg_map_create(orbg_ctx *ctx, int max_keyframes, int kf_cap, int max_points, orbg_map **out);
+void orbg_map_destroy(orbg_map *map);
+/* live slots, max_keyframes, kf_cap, max_points (any pointer may be NULL).  Waits for the
+ * map's pending work. */
+int orbg_map_info(orbg_map *map, int32_t *nlive, int32_t *max_keyframes, int32_t *kf_cap,
+                  int32_t *max_points);
+
+/* Adds or overwrites slot `slot`: its n features' point ids (-1 = none) and octaves, the camera
+ * centre (3 floats) and flags (ORBG_MAP_KF_*).  A slot that was not live starts without a
+ * parent and with mbFirstConnection set; an overwrite keeps parent, mbFirstConnection, its W row
+ * and its ordered list.  ORBG_EINVAL: slot out of range, n > kf_cap, an id >= max_points. */
+int orbg_map_set_keyframe(orbg_ctx *ctx, orbg_map *map, int slot, const int32_t *point_ids,
+                          const uint8_t *octaves, int n, const float *centre, int flags);
+/* The same for i < n from device memory: slot d_slots[i] <- rows d_point_ids / d_octaves +
+ * i * row_cap with d_counts[i] entries (clamped to row_cap and kf_cap), d_centres + 3 * i,
+ * d_flags[i].  An out-of-range slot is skipped and an id >= max_points stored as -1; nothing
+ * else is checked. */
+int orbg_map_set_keyframes_device(orbg_ctx *ctx, orbg_map *map, const int32_t *d_slots, int n,
+                                  const int32_t *d_point_ids, const uint8_t *d_octaves,
+                                  int row_cap, const int32_t *d_counts, const float *d_centres,
+                                  const int32_t *d_flags);
+/* Records (flags: ORBG_MP_VALID = !isBad(); ORBG_MP_HAS_OBS is ignored, the table knows),
+ * descriptors [n][32] and reference KeyFrame slots of points first .. first + n - 1. */
+int orbg_map_set_points(orbg_ctx *ctx, orbg_map *map, int first, int n, const orbg_map_point *mps,
+                        const uint8_t *desc, const int32_t *ref_kf);
+/* The same from device memory for the ids d_ids[i] (NULL: first + i); an id out of range is
+ * skipped. */
+int orbg_map_set_points_device(orbg_ctx *ctx, orbg_map *map, const int32_t *d_ids, int first,
+                               int n, const orbg_map_point *d_mps, const uint8_t *d_desc,
+                               const int32_t *d_ref_kf);
+/* the stored records of points first .. first + n - 1 (host; after UpdateNormalAndDepth) */
+int orbg_map_get_points(orbg_ctx *ctx, orbg_map *map, int first, int n, orbg_map_point *mps);
+/* SetBadFlag of a MapPoint as far as the table goes: clears ORBG_MP_VALID */
+int orbg_map_set_point_bad(orbg_ctx *ctx, orbg_map *map, int id);
+/* KeyFrame::ChangeParent (parent -1: none) */
+int orbg_map_set_parent(orbg_ctx *ctx, orbg_map *map, int slot, int parent);
+/* The table side of KeyFrame::SetBadFlag (:618-720): the slot becomes dead and bad, its row and
+ * its W row are cleared, and in every row t with W[t][slot] > 0 the entry is zeroed and t's
+ * ordered list re-sorted over all its non-zero weights (EraseConnection -> UpdateBestCovisibles).
+ * The spanning-tree repair of :650-715 stays with the caller, through orbg_map_set_parent:
+ * children of the slot keep it as their parent until then. */
+int orbg_map_erase_keyframe(orbg_ctx *ctx, orbg_map *map, int slot);
+int orbg_map_clear(orbg_ctx *ctx, orbg_map *map);
+/* The observation index and the children lists are rebuilt on the device by the first query
+ * after a change; this does it now (no effect when they are current). */
+int orbg_map_rebuild(orbg_ctx *ctx, orbg_map *map);
+
+/* The device table neigh[max_keyframes][10] (GetBestCovisibilityKeyFrames(10) of every slot),
+ * valid after the context stream's work: the d_neigh of the orbg_kfdb detect calls, unchanged. */
+int orbg_map_neighbours(orbg_map *map, const int32_t **d_neigh);
+/* a host copy of that table (neigh[max_keyframes][10]) */
+int orbg_map_get_neighbours(orbg_ctx *ctx, orbg_map *map, int32_t *neigh);
+/* GetConnectedKeyFrames() of slots d_slots[i], i < n: the non-zeros of the W row in ascending
+ * slot order at d_conn + i * conn_cap, d_nconn[i] the full count (only the first conn_cap are
+ * written): orbg_kfdb_detect_loop_batch_device's d_conn / d_nconn. */
+int orbg_map_connected_device(orbg_ctx *ctx, orbg_map *map, const int32_t *d_slots, int n,
+                              int32_t *d_conn, int conn_cap, int32_t *d_nconn);
+/* A host read of slot's ordered list (GetVectorCovisibleKeyFrames / GetCovisiblesByWeight /
+ * GetWeight in the essential-graph walk) and parent (may be NULL).  *n is the full length;
+ * ORBG_ERANGE when it exceeds cap (the first cap entries are written). */
+int orbg_map_get_connections(orbg_ctx *ctx, orbg_map *map, int slot, int32_t *slots,
+                             int32_t *weights, int cap, int32_t *n, int32_t *parent);
+/* row `slot` of W (weights[max_keyframes], host) */
+int orbg_map_get_weights(orbg_ctx *ctx, orbg_map *map, int slot, uint16_t *weights);
+
+/* KeyFrame::UpdateConnections of the n distinct slots d_slots[i].  For slot s: KFcounter = for
+ * every other live slot the number of s's good points it observes.  Empty: nothing changes for
+ * s.  Else W[s][*] becomes the whole counter (weights below 15 included); vPairs = the slots
+ * with weight >= 15, or if there are none the single pKFmax (strict > in ascending slot order:
+ * the lowest slot among ties); s's ordered list = vPairs by descending weight, ties by
+ * descending slot (the ascending pair sort followed by push_front); for each t in vPairs
+ * AddConnection(s, w): if W[t][s] != w it is set and t's ordered list re-sorted over all
+ * non-zero weights of row t, sub-threshold ones its own last UpdateConnections left there
+ * included, else t's list stays as it is; if mbFirstConnection and s is not root, parent[s] =
+ * the list's head.  With distinct slots the sequential result does not depend on the order:
+ * the counts are symmetric, so a batch member's row entry is overwritten with the value another
+ * member would have written into it, and its list is its own vPairs either way.  The rows of
+ * the slots outside the batch that changed are re-sorted once, by a second kernel. */
+int orbg_map_update_connections_batch_device(orbg_ctx *ctx, orbg_map *map, const int32_t *d_slots,
+                                             int n);
+/* one slot from the host (ORBG_EINVAL out of range); synchronises */
+int orbg_map_update_connections(orbg_ctx *ctx, orbg_map *map, int slot);
+
+/* Tracking::UpdateLocalKeyFrames for nframes frames: frame f's mvpMapPoints as ids (-1 = NULL)
+ * at d_frame_points + f * frame_cap, d_counts[f] of them.  An entry that names a bad point
+ * becomes -1 in place, as the reference nulls it.  The slots with votes follow in ascending
+ * slot order, bad ones skipped; pKFmax (d_ref_kf[f]; -1: none, mpReferenceKF stays) by strict >.
+ * The expansion runs over that initial list only and stops when the list's current size
+ * exceeds 80: the first of the ten best neighbours that is neither bad nor listed, the first
+ * such child in ascending slot order, then the parent if it exists and is not listed, after
+ * which the loop is left (the break of Tracking.cc:1912, reproduced).  Outputs d_local_kfs +
+ * f * lkf_cap, d_nlocal[f] = the full length (only the first lkf_cap are written).  An empty
+ * counter: d_nlocal[f] = d_ref_kf[f] = -1 (the reference returns without touching
+ * mvpLocalKeyFrames). */
+int orbg_map_local_keyframes_batch_device(orbg_ctx *ctx, orbg_map *map, int32_t *d_frame_points,
+                                          int frame_cap, const int32_t *d_counts, int nframes,
+                                          int32_t *d_local_kfs, int lkf_cap, int32_t *d_nlocal,
+                                          int32_t *d_ref_kf);
+/* Tracking::UpdateLocalPoints plus what SearchLocalPoints needs: frame f's local keyframes
+ * (d_local_kfs + f * lkf_cap, d_nlocal[f] of them, clamped to [0, lkf_cap]) in list order,
+ * features in index order, each point at its first occurrence, bad points dropped.  Outputs at
+ * + f * lp_cap: d_local_ids, d_mps (the stored record with flags = ORBG_MP_VALID unless the
+ * point is among the frame's own d_frame_points, mnLastFrameSeen == mCurrentFrame.mnId of
+ * Tracking.cc:1644-1683, | ORBG_MP_HAS_OBS), d_qdesc [lp_cap][32]; d_nlocal_points[f] = the
+ * full count (only the first lp_cap are written).  These are orbg_is_in_frustum_batch_device's
+ * d_mps / d_counts (cap = lp_cap) and orbg_search_by_projection_batch_device(ORBG_TRACK_LOCAL)'s
+ * qdesc / qcounts.  frame_cap <= 8192 (ORBG_ENOTSUP), lkf_cap <= max_keyframes, nframes <=
+ * 65535 (ORBG_EINVAL). */
+int orbg_map_local_points_batch_device(orbg_ctx *ctx, orbg_map *map, const int32_t *d_local_kfs,
+                                       int lkf_cap, const int32_t *d_nlocal,
+                                       const int32_t *d_frame_points, int frame_cap,
+                                       const int32_t *d_counts, int nframes, int32_t *d_local_ids,
+                                       orbg_map_point *d_mps, uint8_t *d_qdesc, int lp_cap,
+                                       int32_t *d_nlocal_points);
+/* One frame from host arrays on the same kernels (frame_points is updated in place).
+ * ORBG_ERANGE when the result exceeds lkf_cap / lp_cap: *nlocal / *nlocal_points hold the
+ * needed count and the first cap entries are written. */
+int orbg_map_local_keyframes(orbg_ctx *ctx, orbg_map *map, int32_t *frame_points, int n,
+                             int32_t *local_kfs, int lkf_cap, int32_t *nlocal, int32_t *ref_kf);
+int orbg_map_local_points(orbg_ctx *ctx, orbg_map *map, const int32_t *local_kfs, int nlocal,
+                          const int32_t *frame_points, int n, int32_t *local_ids,
+                          orbg_map_point *mps, uint8_t *qdesc, int lp_cap, int32_t *nlocal_points);
+
+/* MapPoint::UpdateNormalAndDepth of the points d_point_ids[i] (NULL: i), i < n, into the stored
+ * records.  A bad point, one without observations, or one its reference KeyFrame does not
+ * observe is left untouched.  The cv::Mat arithmetic as the reference evaluates it: normali =
+ * mWorldPos - Owi in float; cv::norm(normali) accumulates the three squares in double, in
+ * order, and takes the double square root; normali / norm is a convertTo with the float alpha
+ * (float)(1. / norm), one rounding per element; normal = normal + that in float, over the
+ * observations in ascending slot order; mNormalVector = normal / n with the float alpha
+ * (float)(1. / n).  dist = (float)cv::norm(Pos - O_ref), the same double norm rounded once;
+ * mfMaxDistance = dist * scaleFactor[octave of the point in its reference KeyFrame] and
+ * mfMinDistance = mfMaxDistance / scaleFactor[nlevels - 1] in float (the context's tables). */
+int orbg_map_update_normal_and_depth_batch_device(orbg_ctx *ctx, orbg_map *map,
+                                                  const int32_t *d_point_ids, int n);
 
 /* ---------------- ORBmatcher::SearchByBoW(KeyFrame*, Frame&) ---------------- */
 /* One side of SearchByBoW pairs, device memory, in orbg_bow_transform_batch_device's layout

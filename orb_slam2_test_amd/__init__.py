@@ -8,6 +8,8 @@ recognition (DetectRelocalizationCandidates, DetectLoopCandidates), Sim3Solver's
 Optimizer::OptimizeSim3 (LoopClosing::ComputeSim3), Optimizer::OptimizeEssentialGraph
 (LoopClosing::CorrectLoop), Optimizer::GlobalBundleAdjustemnt (a block-sparse Schur solve),
 Initializer's H / F RANSAC and two-view reconstruction (Tracking::MonocularInitialization),
+the covisibility Map (KeyFrame::UpdateConnections, Tracking::UpdateLocalMap,
+MapPoint::UpdateNormalAndDepth),
 the LBA Schur solve and
 the per-edge arithmetic of Optimizer::LocalBundleAdjustment, as hand-written HIP
 kernels behind the C ABI in include/orbg.h (lib/liborbg.so).  The Python classes mirror
@@ -25,10 +27,11 @@ from .keyframedatabase import KeyFrameDatabase  # noqa: F401
 from .sim3solver import Sim3Solver  # noqa: F401
 from .pnpsolver import PnPsolver  # noqa: F401
 from .initializer import Initializer  # noqa: F401
+from .map import Map  # noqa: F401
 
 __all__ = ["ORBextractor", "ORBmatcher", "Frame", "MapPointProjections", "StereoFrame", "PoseOptimization", "linearize_local_ba", "OptimizeSim3", "OptimizeSim3Batch",
            "OptimizeEssentialGraph", "CorrectMapPoints", "EssentialGraph",
            "GlobalBundleAdjustment", "CorrectPointsGBA", "sparse_symbolic",
-           "ORBVocabulary", "BowVector", "FeatureVector", "KeyFrameDatabase", "Sim3Solver", "PnPsolver", "Initializer",
+           "ORBVocabulary", "BowVector", "FeatureVector", "KeyFrameDatabase", "Sim3Solver", "PnPsolver", "Initializer", "Map",
            "KP_DTYPE",
            "EDGE_DTYPE", "EDGE_OUT_DTYPE", "POSE_DTYPE"]

@@ -432,6 +432,36 @@ def lib():
                                                      vp, vp, vp, vp, i32, vp, vp, vp]),
         "orbg_kfdb_detect_loop": (i32, [vp, vp, vp, vp, i32, vp, i32, f32, vp, vp, i32,
                                         P(C.c_int32), P(C.c_int32), P(C.c_int32)]),
+        "orbg_map_create": (i32, [vp, i32, i32, i32, P(vp)]),
+        "orbg_map_destroy": (None, [vp]),
+        "orbg_map_info": (i32, [vp, P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_int32)]),
+        "orbg_map_set_keyframe": (i32, [vp, vp, i32, vp, vp, i32, vp, i32]),
+        "orbg_map_set_keyframes_device": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, vp, vp]),
+        "orbg_map_set_points": (i32, [vp, vp, i32, i32, vp, vp, vp]),
+        "orbg_map_set_points_device": (i32, [vp, vp, vp, i32, i32, vp, vp, vp]),
+        "orbg_map_get_points": (i32, [vp, vp, i32, i32, vp]),
+        "orbg_map_set_point_bad": (i32, [vp, vp, i32]),
+        "orbg_map_set_parent": (i32, [vp, vp, i32, i32]),
+        "orbg_map_erase_keyframe": (i32, [vp, vp, i32]),
+        "orbg_map_clear": (i32, [vp, vp]),
+        "orbg_map_rebuild": (i32, [vp, vp]),
+        "orbg_map_neighbours": (i32, [vp, P(vp)]),
+        "orbg_map_get_neighbours": (i32, [vp, vp, vp]),
+        "orbg_map_connected_device":(i32, [vp, vp, vp, i32, vp, i32, vp]),
+        "orbg_map_get_connections": (i32, [vp, vp, i32, vp, vp, i32, P(C.c_int32),
+                                           P(C.c_int32)]),
+        "orbg_map_get_weights": (i32, [vp, vp, i32, vp]),
+        "orbg_map_update_connections_batch_device": (i32, [vp, vp, vp, i32]),
+        "orbg_map_update_connections": (i32, [vp, vp, i32]),
+        "orbg_map_local_keyframes_batch_device": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, vp,
+                                                        vp]),
+        "orbg_map_local_points_batch_device": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, i32, vp,
+                                                     vp, vp, i32, vp]),
+        "orbg_map_local_keyframes": (i32, [vp, vp, vp, i32, vp, i32, P(C.c_int32),
+                                           P(C.c_int32)]),
+        "orbg_map_local_points": (i32, [vp, vp, vp, i32, vp, i32, vp, vp, vp, i32,
+                                        P(C.c_int32)]),
+        "orbg_map_update_normal_and_depth_batch_device": (i32, [vp, vp, vp, i32]),
         "orbg_sim3_ransac_iterations": (i32, [C.c_double, i32, i32, i32]),
         "orbg_sim3_solve": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
         "orbg_sim3_solve_batch_device": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp,

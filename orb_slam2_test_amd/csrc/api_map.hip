@@ -1,0 +1,599 @@
+// api_map.hip -- orbg_map_*
+#include "orbg_ctx.h"
+#include "map_args.h"
+
+#pragma clang fp contract(off)
+
+using namespace orbg;
+
+// ---------------------------------------------------------------------------
+// the covisibility Map: observation table, covisibility graph, local map (map_kernels.hip)
+// ---------------------------------------------------------------------------
+struct orbg_map {
+    int device = 0;
+    MapDev D{};
+    void *d_mem = nullptr;       // one allocation behind every MapDev array
+    size_t mem_bytes = 0, o_zero = 0;
+    bool dirty = true;           // the observation index is stale (a row changed since)
+    bool tree_dirty = true;      // the children lists are stale (a parent may have changed)
+    bool touched = false;        // any device work issued yet
+    int epoch = 0;               // number of the last call that marks rows dirty
+    int32_t *d_cnt = nullptr;    // local_points' per-keyframe counts [nframes][lkf_cap]
+    size_t cnt_n = 0;
+    hipStream_t stream = nullptr;  // the context stream of the last call
+};
+
+static int map_reset(orbg_map *m, hipStream_t st)
+{
+    MapDev &D = m->D;
+    uint8_t *b = (uint8_t *)m->d_mem;
+    HIPCHK(hipMemsetAsync(b + m->o_zero, 0, m->mem_bytes - m->o_zero, st));
+    HIPCHK(hipMemsetAsync(D.kf_points, 0xFF, (size_t)D.K * D.cap * 4, st));
+    HIPCHK(hipMemsetAsync(D.parent, 0xFF, (size_t)D.K * 4, st));
+    HIPCHK(hipMemsetAsync(D.neigh, 0xFF, (size_t)D.K * ORBG_MAP_NEIGH * 4, st));
+    HIPCHK(hipMemsetAsync(D.child_head, 0xFF, (size_t)D.K * 4, st));
+    HIPCHK(hipMemsetAsync(D.child_next, 0xFF, (size_t)D.K * 4, st));
+    m->dirty = m->tree_dirty = true;
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_create(orbg_ctx *c, int max_keyframes, int kf_cap, int max_points,
+                               orbg_map **out)
+{
+    if (!c || !out) return set_err(ORBG_EINVAL, "NULL argument");
+    *out = nullptr;
+    if (max_keyframes < 1 || kf_cap < 1 || max_points < 1)
+        return set_err(ORBG_EINVAL, "max_keyframes / kf_cap / max_points < 1");
+    if (max_keyframes > ORBG_MAP_MAX_KEYFRAMES)
+        return set_err(ORBG_ENOTSUP, "max_keyframes %d (> %d: the per-slot counters live in LDS)",
+                       max_keyframes, ORBG_MAP_MAX_KEYFRAMES);
+    if (kf_cap > ORBG_MAP_MAX_KF_CAP)
+        return set_err(ORBG_ENOTSUP, "kf_cap %d (> %d)", kf_cap, ORBG_MAP_MAX_KF_CAP);
+    HIPCHK(hipSetDevice(c->device));
+    const size_t K = (size_t)max_keyframes, kc = K * (size_t)kf_cap, P = (size_t)max_points;
+    Layout L;
+    const size_t o_kp = L.take(kc * 4), o_ot = L.take(kc * 4), o_ob = L.take(kc * 4);
+    const size_t o_ko = L.take(kc);  // everything from here on starts at zero
+    const size_t o_fl = L.take(K * 4), o_kn = L.take(K * 4), o_ce = L.take(K * 12);
+    const size_t o_pa = L.take(K * 4), o_fc = L.take(K * 4);
+    const size_t o_mp = L.take(P * sizeof(orbg_map_point)), o_md = L.take(P * 32);
+    const size_t o_mr = L.take(P * 4);
+    const size_t o_w = L.take(K * K * 2), o_os = L.take(K * K * 2), o_ow = L.take(K * K * 2);
+    const size_t o_no = L.take(K * 4), o_ng = L.take(K * ORBG_MAP_NEIGH * 4);
+    const size_t o_of = L.take((P + 1) * 4), o_oc = L.take(P * 4);
+    const size_t o_pt = L.take((P / 2048 + 2) * 4);
+    const size_t o_ch = L.take(K * 4), o_cn = L.take(K * 4);
+    const size_t o_di = L.take(K * 4), o_mk = L.take(K * 4), o_nl = L.take(4);
+    auto *m = new orbg_map();
+    m->device = c->device;
+    if (hipMalloc(&m->d_mem, L.total()) != hipSuccess) {
+        delete m;
+        return set_err(ORBG_ENOMEM, "Map: hipMalloc(%zu bytes)", L.total());
+    }
+    m->mem_bytes = L.total();
+    m->o_zero = o_ko;
+    uint8_t *b = (uint8_t *)m->d_mem;
+    MapDev &D = m->D;
+    D.K = max_keyframes;
+    D.cap = kf_cap;
+    D.P = max_points;
+    D.kf_points = L.at<int32_t>(b, o_kp);
+    D.obs_tmp = L.at<uint32_t>(b, o_ot);
+    D.obs = L.at<uint32_t>(b, o_ob);
+    D.kf_oct = L.at<uint8_t>(b, o_ko);
+    D.kf_flags = L.at<int32_t>(b, o_fl);
+    D.kf_n = L.at<int32_t>(b, o_kn);
+    D.kf_centre = L.at<float>(b, o_ce);
+    D.parent = L.at<int32_t>(b, o_pa);
+    D.first_conn = L.at<int32_t>(b, o_fc);
+    D.mp = L.at<orbg_map_point>(b, o_mp);
+    D.mdesc = L.at<uint8_t>(b, o_md);
+    D.mp_ref = L.at<int32_t>(b, o_mr);
+    D.W = L.at<uint16_t>(b, o_w);
+    D.ord_slot = L.at<uint16_t>(b, o_os);
+    D.ord_w = L.at<uint16_t>(b, o_ow);
+    D.nord = L.at<int32_t>(b, o_no);
+    D.neigh = L.at<int32_t>(b, o_ng);
+    D.obs_off = L.at<int32_t>(b, o_of);
+    D.obs_cnt = L.at<int32_t>(b, o_oc);
+    D.part = L.at<int32_t>(b, o_pt);
+    D.child_head = L.at<int32_t>(b, o_ch);
+    D.child_next = L.at<int32_t>(b, o_cn);
+    D.dirty = L.at<int32_t>(b, o_di);
+    D.mark = L.at<int32_t>(b, o_mk);
+    D.nlive = L.at<int32_t>(b, o_nl);
+    int rc = map_reset(m, c->stream);
+    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess)
+        rc = set_err(ORBG_EIO, "Map: the initial clear failed");
+    if (rc) {
+        hipFree(m->d_mem);
+        delete m;
+        return rc;
+    }
+    m->stream = c->stream;
+    *out = m;
+    return ORBG_OK;
+}
+
+extern "C" void orbg_map_destroy(orbg_map *m)
+{
+    if (!m) return;
+    hipSetDevice(m->device);
+    if (m->d_cnt) hipFree(m->d_cnt);
+    if (m->d_mem) hipFree(m->d_mem);
+    delete m;
+}
+
+extern "C" int orbg_map_info(orbg_map *m, int32_t *nlive, int32_t *max_keyframes, int32_t *kf_cap,
+                             int32_t *max_points)
+{
+    if (!m) return set_err(ORBG_EINVAL, "map is NULL");
+    if (max_keyframes) *max_keyframes = m->D.K;
+    if (kf_cap) *kf_cap = m->D.cap;
+    if (max_points) *max_points = m->D.P;
+    if (nlive) {
+        *nlive = 0;
+        if (m->touched) {
+            HIPCHK(hipSetDevice(m->device));
+            if (launch_map_count(m->stream, m->D)) return set_err(ORBG_EIO, "k_map_count launch failed");
+            HIPCHK(hipMemcpyAsync(nlive, m->D.nlive, 4, hipMemcpyDeviceToHost, m->stream));
+            HIPCHK(hipStreamSynchronize(m->stream));
+        }
+    }
+    return ORBG_OK;
+}
+
+static int map_enter(orbg_ctx *c, orbg_map *m)
+{
+    if (!c || !m) return set_err(ORBG_EINVAL, "NULL context or map");
+    if (m->device != c->device) return set_err(ORBG_EINVAL, "map lives on another device");
+    HIPCHK(hipSetDevice(c->device));
+    if (m->stream != c->stream) {  // the context's stream changed: finish what the old one holds
+        if (m->touched) HIPCHK(hipStreamSynchronize(m->stream));
+        m->stream = c->stream;
+    }
+    return ORBG_OK;
+}
+
+static int map_slot_ok(const orbg_map *m, int slot)
+{
+    if (slot < 0 || slot >= m->D.K)
+        return set_err(ORBG_EINVAL, "slot %d outside [0, %d)", slot, m->D.K);
+    return ORBG_OK;
+}
+
+// ---- mutations ----
+extern "C" int orbg_map_set_keyframes_device(orbg_ctx *c, orbg_map *m, const int32_t *d_slots,
+                                             int n, const int32_t *d_point_ids,
+                                             const uint8_t *d_octaves, int row_cap,
+                                             const int32_t *d_counts, const float *d_centres,
+                                             const int32_t *d_flags)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (n < 0) return set_err(ORBG_EINVAL, "negative size");
+    if (n == 0) return ORBG_OK;
+    if (row_cap < 1) return set_err(ORBG_EINVAL, "row_cap < 1");
+    if (!d_slots || !d_point_ids || !d_octaves || !d_counts || !d_centres || !d_flags)
+        return set_err(ORBG_EINVAL, "NULL device array");
+    if ((rc = launch_map_set_keyframes(c->stream, m->D, d_slots, n, d_point_ids, d_octaves, row_cap,
+                                       d_counts, d_centres, d_flags)))
+        return set_err(rc, "k_map_set_kf launch failed");
+    m->dirty = m->tree_dirty = m->touched = true;
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_set_keyframe(orbg_ctx *c, orbg_map *m, int slot, const int32_t *point_ids,
+                                     const uint8_t *octaves, int n, const float *centre, int flags)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_slot_ok(m, slot))) return rc;
+    if (n < 0 || n > m->D.cap) return set_err(ORBG_EINVAL, "%d features (kf_cap %d)", n, m->D.cap);
+    if (!centre || (n && (!point_ids || !octaves))) return set_err(ORBG_EINVAL, "NULL array");
+    for (int i = 0; i < n; i++)
+        if (point_ids[i] >= m->D.P)
+            return set_err(ORBG_EINVAL, "point id %d outside [0, %d)", point_ids[i], m->D.P);
+    const int cap = std::max(n, 1);
+    Layout L;
+    const size_t o_p = L.take((size_t)cap * 4), o_o = L.take(cap), o_c = L.take(12);
+    const size_t o_h = L.take(12);  // slot, count, flags
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
+    const int32_t hdr[3] = {slot, n, flags};
+    if (n) HIPCHK(hipMemcpyAsync(b + o_p, point_ids, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    if (n) HIPCHK(hipMemcpyAsync(b + o_o, octaves, (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(b + o_c, centre, 12, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(b + o_h, hdr, 12, hipMemcpyHostToDevice, c->stream));
+    const int32_t *h = L.at<int32_t>(b, o_h);
+    rc = orbg_map_set_keyframes_device(c, m, h, 1, L.at<int32_t>(b, o_p), L.at<uint8_t>(b, o_o), cap,
+                                       h + 1, L.at<float>(b, o_c), h + 2);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));  // the scratch is the next host call's too
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_set_points_device(orbg_ctx *c, orbg_map *m, const int32_t *d_ids, int first,
+                                          int n, const orbg_map_point *d_mps, const uint8_t *d_desc,
+                                          const int32_t *d_ref_kf)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (n < 0) return set_err(ORBG_EINVAL, "negative size");
+    if (n == 0) return ORBG_OK;
+    if (!d_ids && (first < 0 || (int64_t)first + n > m->D.P))
+        return set_err(ORBG_EINVAL, "ids %d .. %lld outside [0, %d)", first, (long long)first + n, m->D.P);
+    if (!d_mps || !d_desc || !d_ref_kf) return set_err(ORBG_EINVAL, "NULL device array");
+    if ((rc = launch_map_set_points(c->stream, m->D, d_ids, first, n, d_mps, d_desc, d_ref_kf)))
+        return set_err(rc, "k_map_set_points launch failed");
+    m->touched = true;
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_set_points(orbg_ctx *c, orbg_map *m, int first, int n,
+                                   const orbg_map_point *mps, const uint8_t *desc,
+                                   const int32_t *ref_kf)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (n < 0) return set_err(ORBG_EINVAL, "negative size");
+    if (first < 0 || (int64_t)first + n > m->D.P)
+        return set_err(ORBG_EINVAL, "ids %d .. %lld outside [0, %d)", first, (long long)first + n, m->D.P);
+    if (n == 0) return ORBG_OK;
+    if (!mps || !desc || !ref_kf) return set_err(ORBG_EINVAL, "NULL array");
+    Layout L;
+    const size_t o_m = L.take((size_t)n * sizeof(orbg_map_point)), o_d = L.take((size_t)n * 32);
+    const size_t o_r = L.take((size_t)n * 4);
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
+    HIPCHK(hipMemcpyAsync(b + o_m, mps, (size_t)n * sizeof(orbg_map_point), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(b + o_d, desc, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(b + o_r, ref_kf, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    rc = orbg_map_set_points_device(c, m, nullptr, first, n, L.at<orbg_map_point>(b, o_m),
+                                    L.at<uint8_t>(b, o_d), L.at<int32_t>(b, o_r));
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_get_points(orbg_ctx *c, orbg_map *m, int first, int n, orbg_map_point *mps)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (n < 0 || first < 0 || (int64_t)first + n > m->D.P)
+        return set_err(ORBG_EINVAL, "ids %d .. %lld outside [0, %d)", first, (long long)first + n, m->D.P);
+    if (n == 0) return ORBG_OK;
+    if (!mps) return set_err(ORBG_EINVAL, "NULL array");
+    HIPCHK(hipMemcpyAsync(mps, m->D.mp + first, (size_t)n * sizeof(orbg_map_point),
+                          hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_set_point_bad(orbg_ctx *c, orbg_map *m, int id)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (id < 0 || id >= m->D.P) return set_err(ORBG_EINVAL, "point id %d outside [0, %d)", id, m->D.P);
+    if (launch_map_point_bad(c->stream, m->D, id)) return set_err(ORBG_EIO, "k_map_point_bad launch failed");
+    m->touched = true;
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_set_parent(orbg_ctx *c, orbg_map *m, int slot, int parent)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_slot_ok(m, slot))) return rc;
+    if (parent < -1 || parent >= m->D.K)
+        return set_err(ORBG_EINVAL, "parent %d outside [-1, %d)", parent, m->D.K);
+    if (launch_map_set_parent(c->stream, m->D, slot, parent))
+        return set_err(ORBG_EIO, "k_map_set_parent launch failed");
+    m->tree_dirty = m->touched = true;
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_erase_keyframe(orbg_ctx *c, orbg_map *m, int slot)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_slot_ok(m, slot))) return rc;
+    if (launch_map_erase(c->stream, m->D, slot, ++m->epoch))
+        return set_err(ORBG_EIO, "k_map_erase launch failed");
+    m->dirty = m->touched = true;
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_clear(orbg_ctx *c, orbg_map *m)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_reset(m, c->stream))) return rc;
+    m->epoch = 0;
+    m->touched = true;
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_rebuild(orbg_ctx *c, orbg_map *m)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (m->dirty) {
+        if ((rc = launch_map_rebuild(c->stream, m->D, &c->prof)))
+            return set_err(rc, "observation index rebuild launch failed");
+        m->dirty = false;
+        m->touched = true;
+    }
+    if (m->tree_dirty) {
+        if ((rc = launch_map_tree(c->stream, m->D))) return set_err(rc, "k_map_tree launch failed");
+        m->tree_dirty = false;
+        m->touched = true;
+    }
+    return ORBG_OK;
+}
+
+// ---- readers ----
+extern "C" int orbg_map_neighbours(orbg_map *m, const int32_t **d_neigh)
+{
+    if (!m || !d_neigh) return set_err(ORBG_EINVAL, "NULL argument");
+    *d_neigh = m->D.neigh;
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_get_neighbours(orbg_ctx *c, orbg_map *m, int32_t *neigh)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (!neigh) return set_err(ORBG_EINVAL, "NULL array");
+    HIPCHK(hipMemcpyAsync(neigh, m->D.neigh, (size_t)m->D.K * ORBG_MAP_NEIGH * 4,
+                          hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_connected_device(orbg_ctx *c, orbg_map *m, const int32_t *d_slots, int n,
+                                         int32_t *d_conn, int conn_cap, int32_t *d_nconn)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (n < 0 || conn_cap < 0) return set_err(ORBG_EINVAL, "negative size");
+    if (n == 0) return ORBG_OK;
+    if (!d_slots || !d_nconn || (conn_cap && !d_conn)) return set_err(ORBG_EINVAL, "NULL device array");
+    if ((rc = launch_map_connected(c->stream, m->D, d_slots, n, d_conn, conn_cap, d_nconn)))
+        return set_err(rc, "k_map_connected launch failed");
+    m->touched = true;
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_get_connections(orbg_ctx *c, orbg_map *m, int slot, int32_t *slots,
+                                        int32_t *weights, int cap, int32_t *n, int32_t *parent)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_slot_ok(m, slot))) return rc;
+    if (cap < 0 || !n || (cap && (!slots || !weights))) return set_err(ORBG_EINVAL, "bad cap / NULL array");
+    const MapDev &D = m->D;
+    int32_t hdr[2] = {0, -1};
+    HIPCHK(hipMemcpyAsync(&hdr[0], D.nord + slot, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&hdr[1], D.parent + slot, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const int nw = std::min(hdr[0], cap);
+    if (nw > 0) {
+        std::vector<uint16_t> s(nw), w(nw);
+        HIPCHK(hipMemcpy(s.data(), D.ord_slot + (size_t)slot * D.K, (size_t)nw * 2, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(w.data(), D.ord_w + (size_t)slot * D.K, (size_t)nw * 2, hipMemcpyDeviceToHost));
+        for (int i = 0; i < nw; i++) {
+            slots[i] = s[i];
+            weights[i] = w[i];
+        }
+    }
+    *n = hdr[0];
+    if (parent) *parent = hdr[1];
+    if (hdr[0] > cap) return set_err(ORBG_ERANGE, "%d connections (cap %d)", hdr[0], cap);
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_get_weights(orbg_ctx *c, orbg_map *m, int slot, uint16_t *weights)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_slot_ok(m, slot))) return rc;
+    if (!weights) return set_err(ORBG_EINVAL, "NULL array");
+    HIPCHK(hipMemcpyAsync(weights, m->D.W + (size_t)slot * m->D.K, (size_t)m->D.K * 2,
+                          hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return ORBG_OK;
+}
+
+// ---- KeyFrame::UpdateConnections ----
+extern "C" int orbg_map_update_connections_batch_device(orbg_ctx *c, orbg_map *m,
+                                                        const int32_t *d_slots, int n)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (n < 0) return set_err(ORBG_EINVAL, "negative size");
+    if (n == 0) return ORBG_OK;
+    if (!d_slots) return set_err(ORBG_EINVAL, "NULL device array");
+    if ((rc = orbg_map_rebuild(c, m))) return rc;
+    if ((rc = launch_map_update_connections(c->stream, m->D, d_slots, n, ++m->epoch, &c->prof)))
+        return set_err(rc, "k_map_update launch failed");
+    m->tree_dirty = m->touched = true;  // a first connection sets a parent
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_update_connections(orbg_ctx *c, orbg_map *m, int slot)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_slot_ok(m, slot))) return rc;
+    Layout L;
+    const size_t o_s = L.take(4);
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
+    const int32_t sl = slot;
+    HIPCHK(hipMemcpyAsync(b + o_s, &sl, 4, hipMemcpyHostToDevice, c->stream));
+    if ((rc = orbg_map_update_connections_batch_device(c, m, L.at<int32_t>(b, o_s), 1))) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->prof.collect();
+    return ORBG_OK;
+}
+
+// ---- Tracking::UpdateLocalKeyFrames / UpdateLocalPoints ----
+extern "C" int orbg_map_local_keyframes_batch_device(orbg_ctx *c, orbg_map *m,
+                                                     int32_t *d_frame_points, int frame_cap,
+                                                     const int32_t *d_counts, int nframes,
+                                                     int32_t *d_local_kfs, int lkf_cap,
+                                                     int32_t *d_nlocal, int32_t *d_ref_kf)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (nframes < 0 || frame_cap < 1 || lkf_cap < 0) return set_err(ORBG_EINVAL, "bad nframes / cap");
+    if (nframes == 0) return ORBG_OK;
+    if (!d_frame_points || !d_counts || !d_nlocal || !d_ref_kf || (lkf_cap && !d_local_kfs))
+        return set_err(ORBG_EINVAL, "NULL device array");
+    if ((rc = orbg_map_rebuild(c, m))) return rc;
+    if ((rc = launch_map_local_keyframes(c->stream, m->D, d_frame_points, frame_cap, d_counts, nframes,
+                                         d_local_kfs, lkf_cap, d_nlocal, d_ref_kf, &c->prof)))
+        return set_err(rc, "k_map_local_kfs launch failed");
+    m->touched = true;
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_local_points_batch_device(orbg_ctx *c, orbg_map *m,
+                                                  const int32_t *d_local_kfs, int lkf_cap,
+                                                  const int32_t *d_nlocal,
+                                                  const int32_t *d_frame_points, int frame_cap,
+                                                  const int32_t *d_counts, int nframes,
+                                                  int32_t *d_local_ids, orbg_map_point *d_mps,
+                                                  uint8_t *d_qdesc, int lp_cap,
+                                                  int32_t *d_nlocal_points)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (nframes < 0 || nframes > 65535 || frame_cap < 1 || lkf_cap < 1 || lp_cap < 0)
+        return set_err(ORBG_EINVAL, "bad nframes / cap");
+    if (frame_cap > ORBG_MAP_MAX_FRAME_CAP)
+        return set_err(ORBG_ENOTSUP, "frame_cap %d (> %d)", frame_cap, ORBG_MAP_MAX_FRAME_CAP);
+    if (lkf_cap > m->D.K) return set_err(ORBG_EINVAL, "lkf_cap %d above max_keyframes %d", lkf_cap, m->D.K);
+    if (nframes == 0) return ORBG_OK;
+    if (!d_local_kfs || !d_nlocal || !d_frame_points || !d_counts || !d_nlocal_points ||
+        (lp_cap && (!d_local_ids || !d_mps || !d_qdesc)))
+        return set_err(ORBG_EINVAL, "NULL device array");
+    if ((rc = orbg_map_rebuild(c, m))) return rc;
+    const size_t need = (size_t)nframes * lkf_cap;
+    if (need > m->cnt_n) {
+        if (m->d_cnt) {
+            HIPCHK(hipStreamSynchronize(c->stream));
+            HIPCHK(hipFree(m->d_cnt));
+            m->d_cnt = nullptr;
+            m->cnt_n = 0;
+        }
+        if ((rc = dalloc(&m->d_cnt, need))) return rc;
+        m->cnt_n = need;
+    }
+    if ((rc = launch_map_local_points(c->stream, m->D, d_local_kfs, lkf_cap, d_nlocal, d_frame_points,
+                                      frame_cap, d_counts, nframes, m->d_cnt, d_local_ids, d_mps,
+                                      d_qdesc, lp_cap, d_nlocal_points, &c->prof)))
+        return set_err(rc, "k_map_lp launch failed");
+    m->touched = true;
+    return ORBG_OK;
+}
+
+// one frame from host arrays: uploads, runs the batched forms with one frame, downloads
+extern "C" int orbg_map_local_keyframes(orbg_ctx *c, orbg_map *m, int32_t *frame_points, int n,
+                                        int32_t *local_kfs, int lkf_cap, int32_t *nlocal,
+                                        int32_t *ref_kf)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (n < 0 || lkf_cap < 0 || !nlocal) return set_err(ORBG_EINVAL, "bad size / NULL argument");
+    if ((n && !frame_points) || (lkf_cap && !local_kfs)) return set_err(ORBG_EINVAL, "NULL array");
+    const int fc = std::max(n, 1);
+    Layout L;
+    const size_t o_f = L.take((size_t)fc * 4), o_c = L.take(4), o_l = L.take((size_t)lkf_cap * 4);
+    const size_t o_o = L.take(8);
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
+    const int32_t cnt = n;
+    if (n) HIPCHK(hipMemcpyAsync(b + o_f, frame_points, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(b + o_c, &cnt, 4, hipMemcpyHostToDevice, c->stream));
+    int32_t *o = L.at<int32_t>(b, o_o);
+    if ((rc = orbg_map_local_keyframes_batch_device(c, m, L.at<int32_t>(b, o_f), fc,
+                                                    L.at<int32_t>(b, o_c), 1, L.at<int32_t>(b, o_l),
+                                                    lkf_cap, o, o + 1)))
+        return rc;
+    int32_t out[2] = {0, -1};
+    HIPCHK(hipMemcpyAsync(out, o, 8, hipMemcpyDeviceToHost, c->stream));
+    if (n) HIPCHK(hipMemcpyAsync(frame_points, b + o_f, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const int nw = std::min(out[0], lkf_cap);
+    if (nw > 0) HIPCHK(hipMemcpy(local_kfs, b + o_l, (size_t)nw * 4, hipMemcpyDeviceToHost));
+    c->prof.collect();
+    *nlocal = out[0];
+    if (ref_kf) *ref_kf = out[1];
+    if (out[0] > lkf_cap) return set_err(ORBG_ERANGE, "%d local keyframes (cap %d)", out[0], lkf_cap);
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_local_points(orbg_ctx *c, orbg_map *m, const int32_t *local_kfs, int nlocal,
+                                     const int32_t *frame_points, int n, int32_t *local_ids,
+                                     orbg_map_point *mps, uint8_t *qdesc, int lp_cap,
+                                     int32_t *nlocal_points)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (n < 0 || nlocal < 0 || lp_cap < 0 || !nlocal_points)
+        return set_err(ORBG_EINVAL, "bad size / NULL argument");
+    if (nlocal > m->D.K) return set_err(ORBG_EINVAL, "%d local keyframes (max_keyframes %d)", nlocal, m->D.K);
+    if ((n && !frame_points) || (nlocal && !local_kfs) || (lp_cap && (!local_ids || !mps || !qdesc)))
+        return set_err(ORBG_EINVAL, "NULL array");
+    const int fc = std::max(n, 1), lc = std::max(nlocal, 1);
+    Layout L;
+    const size_t o_f = L.take((size_t)fc * 4), o_c = L.take(8), o_l = L.take((size_t)lc * 4);
+    const size_t o_i = L.take((size_t)lp_cap * 4), o_m = L.take((size_t)lp_cap * sizeof(orbg_map_point));
+    const size_t o_d = L.take((size_t)lp_cap * 32), o_o = L.take(4);
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
+    const int32_t cnt[2] = {n, nlocal};
+    if (n) HIPCHK(hipMemcpyAsync(b + o_f, frame_points, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    if (nlocal) HIPCHK(hipMemcpyAsync(b + o_l, local_kfs, (size_t)nlocal * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(b + o_c, cnt, 8, hipMemcpyHostToDevice, c->stream));
+    const int32_t *dc = L.at<int32_t>(b, o_c);
+    if ((rc = orbg_map_local_points_batch_device(c, m, L.at<int32_t>(b, o_l), lc, dc + 1,
+                                                 L.at<int32_t>(b, o_f), fc, dc, 1,
+                                                 L.at<int32_t>(b, o_i), L.at<orbg_map_point>(b, o_m),
+                                                 L.at<uint8_t>(b, o_d), lp_cap, L.at<int32_t>(b, o_o))))
+        return rc;
+    int32_t out = 0;
+    HIPCHK(hipMemcpyAsync(&out, b + o_o, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const int nw = std::min(out, lp_cap);
+    if (nw > 0) {
+        HIPCHK(hipMemcpy(local_ids, b + o_i, (size_t)nw * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(mps, b + o_m, (size_t)nw * sizeof(orbg_map_point), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(qdesc, b + o_d, (size_t)nw * 32, hipMemcpyDeviceToHost));
+    }
+    c->prof.collect();
+    *nlocal_points = out;
+    if (out > lp_cap) return set_err(ORBG_ERANGE, "%d local points (cap %d)", out, lp_cap);
+    return ORBG_OK;
+}
+
+// ---- MapPoint::UpdateNormalAndDepth ----
+extern "C" int orbg_map_update_normal_and_depth_batch_device(orbg_ctx *c, orbg_map *m,
+                                                             const int32_t *d_point_ids, int n)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (n < 0) return set_err(ORBG_EINVAL, "negative size");
+    if (!d_point_ids && n > m->D.P) return set_err(ORBG_EINVAL, "%d points (max_points %d)", n, m->D.P);
+    if (n == 0) return ORBG_OK;
+    if ((rc = orbg_map_rebuild(c, m))) return rc;
+    MapScales S{};
+    S.nlevels = std::min(std::max(c->p.nlevels, 1), 16);
+    for (int i = 0; i < 16; i++) S.scale[i] = c->scale[i];
+    if ((rc = launch_map_normal_depth(c->stream, m->D, d_point_ids, n, S, &c->prof)))
+        return set_err(rc, "k_map_normal_depth launch failed");
+    m->touched = true;
+    return ORBG_OK;
+}

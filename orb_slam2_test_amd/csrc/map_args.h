@@ -1,0 +1,89 @@
+// map_args.h -- device layout and launch arguments of the covisibility Map (map_kernels.hip:
+// KeyFrame::UpdateConnections, Tracking::UpdateLocalKeyFrames / UpdateLocalPoints,
+// MapPoint::UpdateNormalAndDepth), shared with the host entry points (api_map.hip).
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/orbg.h"
+
+namespace orbg {
+
+#define ORBG_MAP_MAX_KEYFRAMES 8192   // = ORBG_KFDB_MAX_KEYFRAMES: a slot is 13 bits of a sort key
+#define ORBG_MAP_MAX_KF_CAP 8192      // a feature index is 13 bits of an observation entry
+#define ORBG_MAP_MAX_FRAME_CAP 8192   // UpdateLocalPoints sorts the frame's own points in LDS
+#define ORBG_MAP_NEIGH 10             // GetBestCovisibilityKeyFrames(10)
+#define ORBG_MAP_TH 15                // UpdateConnections' th
+#define ORBG_MAP_MAX_LOCAL 80         // UpdateLocalKeyFrames' size limit
+#define MAP_KF_LIVE 4                 // kf_flags: beside ORBG_MAP_KF_ROOT (1) and ORBG_MAP_KF_BAD (2)
+
+// An orbg_map's device state.  Slot s (the caller's KeyFrame handle, as orbg_kfdb's) owns row s
+// of kf_points / kf_oct and of W / ord_*; point p owns mp[p], mdesc[p], mp_ref[p].  The
+// observation index is a CSR over the points: obs[obs_off[p] .. obs_off[p + 1]) are p's
+// observations as slot << 16 | feature index, ascending slot, rebuilt from the live rows when
+// stale.  child_head / child_next are the spanning tree's children lists (ascending slot),
+// rebuilt from `parent` when stale.  dirty / mark hold the number of the call that last set
+// them (UpdateConnections' second kernel re-sorts the rows this call marked dirty).
+struct MapDev {
+    int32_t K, cap, P;
+    int32_t *kf_flags;          // [K] MAP_KF_LIVE | ORBG_MAP_KF_*
+    int32_t *kf_n;              // [K]
+    int32_t *kf_points;         // [K][cap] point id, -1 = none
+    uint8_t *kf_oct;            // [K][cap] mvKeysUn[idx].octave
+    float *kf_centre;           // [K][3] GetCameraCenter()
+    int32_t *parent;            // [K] slot or -1
+    int32_t *first_conn;        // [K] mbFirstConnection
+    orbg_map_point *mp;         // [P]
+    uint8_t *mdesc;             // [P][32]
+    int32_t *mp_ref;            // [P] mpRefKF as a slot
+    uint16_t *W;                // [K][K] mConnectedKeyFrameWeights, 0 = not connected
+    uint16_t *ord_slot;         // [K][K] mvpOrderedConnectedKeyFrames
+    uint16_t *ord_w;            // [K][K] mvOrderedWeights
+    int32_t *nord;              // [K]
+    int32_t *neigh;             // [K][10] the first ten of ord_slot, -1 padded
+    int32_t *obs_off;           // [P + 1]
+    int32_t *obs_cnt;           // [P] histogram, then the fill cursors
+    int32_t *part;              // [ceil(P / 2048) + 1] the scan's tile sums
+    uint32_t *obs_tmp;          // [K * cap] the fill, in arrival order
+    uint32_t *obs;              // [K * cap]
+    int32_t *child_head;        // [K]
+    int32_t *child_next;        // [K]
+    int32_t *dirty, *mark;      // [K]
+    int32_t *nlive;             // [1]
+};
+
+struct MapScales {
+    float scale[16];
+    int32_t nlevels;
+};
+
+struct Prof;  // the context's profiler (orbg_ctx.h)
+int launch_map_set_keyframes(hipStream_t st, const MapDev &M, const int32_t *slots, int n,
+                             const int32_t *points, const uint8_t *oct, int row_cap,
+                             const int32_t *counts, const float *centres, const int32_t *flags);
+int launch_map_set_points(hipStream_t st, const MapDev &M, const int32_t *ids, int first, int n,
+                          const orbg_map_point *mps, const uint8_t *desc, const int32_t *ref);
+int launch_map_point_bad(hipStream_t st, const MapDev &M, int id);
+int launch_map_set_parent(hipStream_t st, const MapDev &M, int slot, int parent);
+int launch_map_erase(hipStream_t st, const MapDev &M, int slot, int epoch);
+int launch_map_count(hipStream_t st, const MapDev &M);
+int launch_map_rebuild(hipStream_t st, const MapDev &M, Prof *prof);
+int launch_map_tree(hipStream_t st, const MapDev &M);
+int launch_map_update_connections(hipStream_t st, const MapDev &M, const int32_t *slots, int n,
+                                  int epoch, Prof *prof);
+int launch_map_connected(hipStream_t st, const MapDev &M, const int32_t *slots, int n,
+                         int32_t *conn, int conn_cap, int32_t *nconn);
+int launch_map_local_keyframes(hipStream_t st, const MapDev &M, int32_t *frame_points,
+                               int frame_cap, const int32_t *counts, int nframes,
+                               int32_t *local_kfs, int lkf_cap, int32_t *nlocal, int32_t *ref_kf,
+                               Prof *prof);
+int launch_map_local_points(hipStream_t st, const MapDev &M, const int32_t *local_kfs, int lkf_cap,
+                            const int32_t *nlocal, const int32_t *frame_points, int frame_cap,
+                            const int32_t *counts, int nframes, int32_t *cnt, int32_t *ids,
+                            orbg_map_point *mps, uint8_t *qdesc, int lp_cap, int32_t *nlp,
+                            Prof *prof);
+int launch_map_normal_depth(hipStream_t st, const MapDev &M, const int32_t *ids, int n,
+                            const MapScales &S, Prof *prof);
+
+}  // namespace orbg

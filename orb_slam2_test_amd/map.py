@@ -1,0 +1,267 @@
+"""Map -- ORB-SLAM2's covisibility graph and local map over one device-resident table, "which
+keyframe slot observes which map point" (liborbg's orbg_map_* entry points):
+KeyFrame::UpdateConnections (src/KeyFrame.cc:375-515), Tracking::UpdateLocalKeyFrames /
+UpdateLocalPoints (src/Tracking.cc:1731-1925) and MapPoint::UpdateNormalAndDepth
+(src/MapPoint.cc:457-518).
+
+A KeyFrame is a slot in [0, max_keyframes), as in KeyFrameDatabase; a MapPoint is an id in
+[0, max_points).  Wherever the reference orders by KeyFrame pointer, the order here is the
+ascending slot (include/orbg.h).
+
+    m = Map(max_keyframes=2048, kf_cap=2000, max_points=200000)
+    m.SetPoints(0, records, descriptors, ref_kf)              # MAPPOINT_DTYPE records
+    m.AddKeyFrame(slot, point_ids, octaves, camera_centre)    # after ProcessNewKeyFrame
+    m.UpdateConnections(slot)
+    kfs, ref = m.UpdateLocalKeyFrames(frame_points)           # frame_points nulled in place
+    ids, mps, desc = m.UpdateLocalPoints(kfs, frame_points)
+    db.DetectRelocalizationCandidates(bow, m.neighbours())    # the device table, unchanged
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib as L
+from .orbmatcher import _ctx
+
+NEIGHBOURS = 10
+KF_ROOT, KF_BAD = 1, 2
+
+
+def _i32(a):
+    return np.ascontiguousarray(a, np.int32).reshape(-1)
+
+
+class Map:
+    def __init__(self, max_keyframes, kf_cap, max_points, device=0):
+        self.device = device
+        self._h = None
+        h = C.c_void_p()
+        L.check(L.lib().orbg_map_create(_ctx(device).handle, int(max_keyframes), int(kf_cap),
+                                        int(max_points), C.byref(h)), "orbg_map_create")
+        self._h = h
+        self.max_keyframes, self.kf_cap, self.max_points = (int(max_keyframes), int(kf_cap),
+                                                            int(max_points))
+
+    def __del__(self):
+        try:
+            if self._h is not None and self._h.value:
+                L.lib().orbg_map_destroy(self._h)
+            self._h = None
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    def _c(self, ctx=None):
+        return (ctx if ctx is not None else _ctx(self.device)).handle
+
+    def info(self):
+        """(live slots, max_keyframes, kf_cap, max_points)"""
+        v = [C.c_int32() for _ in range(4)]
+        L.check(L.lib().orbg_map_info(self._h, *[C.byref(x) for x in v]), "orbg_map_info")
+        return tuple(x.value for x in v)
+
+    def __len__(self):
+        return self.info()[0]
+
+    # ---- mutations ----
+    def AddKeyFrame(self, slot, point_ids, octaves, centre, root=False, bad=False):
+        """Adds or overwrites a slot: mvpMapPoints as ids (-1 = NULL), mvKeysUn[i].octave,
+        GetCameraCenter(); root = (mnId == 0)."""
+        p = _i32(point_ids)
+        o = np.ascontiguousarray(octaves, np.uint8).reshape(-1)
+        if len(p) != len(o):
+            raise ValueError("point ids and octaves differ in length")
+        c = np.ascontiguousarray(centre, np.float32).reshape(3)
+        L.check(L.lib().orbg_map_set_keyframe(self._c(), self._h, int(slot), L.ptr(p), L.ptr(o),
+                                              len(p), L.ptr(c),
+                                              (KF_ROOT if root else 0) | (KF_BAD if bad else 0)),
+                "orbg_map_set_keyframe")
+
+    set_keyframe = AddKeyFrame
+
+    def set_keyframes_device(self, d_slots, n, d_point_ids, d_octaves, row_cap, d_counts,
+                             d_centres, d_flags, ctx=None):
+        """orbg_map_set_keyframes_device; device pointers as ints."""
+        L.check(L.lib().orbg_map_set_keyframes_device(self._c(ctx), self._h, d_slots, int(n),
+                                                      d_point_ids, d_octaves, int(row_cap),
+                                                      d_counts, d_centres, d_flags),
+                "orbg_map_set_keyframes_device")
+
+    def SetPoints(self, first, records, descriptors, ref_kf):
+        """MAPPOINT_DTYPE records (flags: MP_VALID = !isBad()), mDescriptor [n][32], mpRefKF
+        slots of the points first .. first + n - 1."""
+        r = np.ascontiguousarray(records, L.MAPPOINT_DTYPE).reshape(-1)
+        d = np.ascontiguousarray(descriptors, np.uint8).reshape(-1, 32)
+        k = _i32(ref_kf)
+        if not (len(r) == len(d) == len(k)):
+            raise ValueError("records, descriptors and reference keyframes differ in length")
+        L.check(L.lib().orbg_map_set_points(self._c(), self._h, int(first), len(r), L.ptr(r),
+                                            L.ptr(d), L.ptr(k)), "orbg_map_set_points")
+
+    set_points = SetPoints
+
+    def set_points_device(self, d_ids, first, n, d_mps, d_desc, d_ref_kf, ctx=None):
+        L.check(L.lib().orbg_map_set_points_device(self._c(ctx), self._h, d_ids, int(first), int(n),
+                                                   d_mps, d_desc, d_ref_kf),
+                "orbg_map_set_points_device")
+
+    def points(self, first=0, n=None):
+        """the stored MAPPOINT_DTYPE records"""
+        n = self.max_points - first if n is None else int(n)
+        out = np.zeros(n, L.MAPPOINT_DTYPE)
+        L.check(L.lib().orbg_map_get_points(self._c(), self._h, int(first), n, L.ptr(out)),
+                "orbg_map_get_points")
+        return out
+
+    def SetPointBad(self, point_id):
+        L.check(L.lib().orbg_map_set_point_bad(self._c(), self._h, int(point_id)),
+                "orbg_map_set_point_bad")
+
+    def ChangeParent(self, slot, parent):
+        L.check(L.lib().orbg_map_set_parent(self._c(), self._h, int(slot),
+                                            -1 if parent is None else int(parent)),
+                "orbg_map_set_parent")
+
+    def EraseKeyFrame(self, slot):
+        """The table side of KeyFrame::SetBadFlag; the spanning-tree repair stays with the
+        caller (ChangeParent)."""
+        L.check(L.lib().orbg_map_erase_keyframe(self._c(), self._h, int(slot)),
+                "orbg_map_erase_keyframe")
+
+    def clear(self):
+        L.check(L.lib().orbg_map_clear(self._c(), self._h), "orbg_map_clear")
+
+    def rebuild(self, ctx=None):
+        L.check(L.lib().orbg_map_rebuild(self._c(ctx), self._h), "orbg_map_rebuild")
+
+    # ---- readers ----
+    def neighbours(self):
+        """Device pointer (int) of neigh[max_keyframes][10]: KeyFrameDatabase's d_neigh."""
+        p = C.c_void_p()
+        L.check(L.lib().orbg_map_neighbours(self._h, C.byref(p)), "orbg_map_neighbours")
+        return p.value
+
+    def neighbours_host(self):
+        """a host copy of neigh[max_keyframes][10] (-1 = unused)"""
+        out = np.zeros((self.max_keyframes, NEIGHBOURS), np.int32)
+        L.check(L.lib().orbg_map_get_neighbours(self._c(), self._h, L.ptr(out)),
+                "orbg_map_get_neighbours")
+        return out
+
+    def connected_device(self,d_slots, n, d_conn, conn_cap, d_nconn, ctx=None):
+        L.check(L.lib().orbg_map_connected_device(self._c(ctx), self._h, d_slots, int(n), d_conn,
+                                                  int(conn_cap), d_nconn),
+                "orbg_map_connected_device")
+
+    def connections(self, slot):
+        """(ordered slots, ordered weights, parent or None): mvpOrderedConnectedKeyFrames,
+        mvOrderedWeights, mpParent."""
+        cap = self.max_keyframes
+        s, w = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        n, par = C.c_int32(), C.c_int32()
+        L.check(L.lib().orbg_map_get_connections(self._c(), self._h, int(slot), L.ptr(s), L.ptr(w),
+                                                 cap, C.byref(n), C.byref(par)),
+                "orbg_map_get_connections")
+        return s[:n.value].tolist(), w[:n.value].tolist(), None if par.value < 0 else par.value
+
+    def GetVectorCovisibleKeyFrames(self, slot):
+        return self.connections(slot)[0]
+
+    def GetBestCovisibilityKeyFrames(self, slot, N=NEIGHBOURS):
+        return self.connections(slot)[0][:N]
+
+    def GetCovisiblesByWeight(self, slot, w):
+        s, ws, _ = self.connections(slot)
+        return [k for k, x in zip(s, ws) if x >= w]
+
+    def GetParent(self, slot):
+        return self.connections(slot)[2]
+
+    def weights(self, slot):
+        """row `slot` of mConnectedKeyFrameWeights as uint16 [max_keyframes] (0 = none)"""
+        out = np.zeros(self.max_keyframes, np.uint16)
+        L.check(L.lib().orbg_map_get_weights(self._c(), self._h, int(slot), L.ptr(out)),
+                "orbg_map_get_weights")
+        return out
+
+    def GetWeight(self, slot, other):
+        return int(self.weights(slot)[other])
+
+    def GetConnectedKeyFrames(self, slot):
+        return np.nonzero(self.weights(slot))[0].tolist()
+
+    # ---- the reference functions ----
+    def UpdateConnections(self, slot):
+        L.check(L.lib().orbg_map_update_connections(self._c(), self._h, int(slot)),
+                "orbg_map_update_connections")
+
+    def update_connections_batch_device(self, d_slots, n, ctx=None):
+        L.check(L.lib().orbg_map_update_connections_batch_device(self._c(ctx), self._h, d_slots,
+                                                                 int(n)),
+                "orbg_map_update_connections_batch_device")
+
+    def UpdateLocalKeyFrames(self, frame_points, lkf_cap=None):
+        """(mvpLocalKeyFrames as slots or None when the vote counter is empty, mpReferenceKF or
+        None); frame_points (int32 array) has its bad points set to -1 in place."""
+        if not (isinstance(frame_points, np.ndarray) and frame_points.dtype == np.int32
+                and frame_points.flags.c_contiguous):
+            raise ValueError("frame_points must be a contiguous int32 array (updated in place)")
+        cap = self.max_keyframes if lkf_cap is None else int(lkf_cap)
+        out = np.full(max(cap, 1), -1, np.int32)
+        n, ref = C.c_int32(), C.c_int32()
+        L.check(L.lib().orbg_map_local_keyframes(self._c(), self._h, L.ptr(frame_points),
+                                                 frame_points.size, L.ptr(out), cap, C.byref(n),
+                                                 C.byref(ref)), "orbg_map_local_keyframes")
+        if n.value < 0:
+            return None, None
+        return out[:n.value].tolist(), None if ref.value < 0 else ref.value
+
+    def UpdateLocalPoints(self, local_kfs, frame_points, lp_cap=None):
+        """(ids, MAPPOINT_DTYPE records, descriptors [n][32]) of mvpLocalMapPoints in the
+        reference's order; flags as Tracking::SearchLocalPoints reads them."""
+        lk, fp = _i32(local_kfs), _i32(frame_points)
+        cap = len(lk) * self.kf_cap if lp_cap is None else int(lp_cap)
+        ids = np.full(max(cap, 1), -1, np.int32)
+        mps = np.zeros(max(cap, 1), L.MAPPOINT_DTYPE)
+        desc = np.zeros((max(cap, 1), 32), np.uint8)
+        n = C.c_int32()
+        L.check(L.lib().orbg_map_local_points(self._c(), self._h, L.ptr(lk), len(lk), L.ptr(fp),
+                                              len(fp), L.ptr(ids), L.ptr(mps), L.ptr(desc), cap,
+                                              C.byref(n)), "orbg_map_local_points")
+        return ids[:n.value], mps[:n.value], desc[:n.value]
+
+    def local_keyframes_batch_device(self, d_frame_points, frame_cap, d_counts, nframes,
+                                     d_local_kfs, lkf_cap, d_nlocal, d_ref_kf, ctx=None):
+        L.check(L.lib().orbg_map_local_keyframes_batch_device(
+            self._c(ctx), self._h, d_frame_points, int(frame_cap), d_counts, int(nframes),
+            d_local_kfs, int(lkf_cap), d_nlocal, d_ref_kf),
+            "orbg_map_local_keyframes_batch_device")
+
+    def local_points_batch_device(self, d_local_kfs, lkf_cap, d_nlocal, d_frame_points, frame_cap,
+                                  d_counts, nframes, d_local_ids, d_mps, d_qdesc, lp_cap,
+                                  d_nlocal_points, ctx=None):
+        L.check(L.lib().orbg_map_local_points_batch_device(
+            self._c(ctx), self._h, d_local_kfs, int(lkf_cap), d_nlocal, d_frame_points,
+            int(frame_cap), d_counts, int(nframes), d_local_ids, d_mps, d_qdesc, int(lp_cap),
+            d_nlocal_points), "orbg_map_local_points_batch_device")
+
+    def update_normal_and_depth_batch_device(self, d_point_ids, n, ctx=None):
+        L.check(L.lib().orbg_map_update_normal_and_depth_batch_device(self._c(ctx), self._h,
+                                                                      d_point_ids, int(n)),
+                "orbg_map_update_normal_and_depth_batch_device")
+
+    def UpdateNormalAndDepth(self, point_ids=None):
+        """MapPoint::UpdateNormalAndDepth of the listed points (None: all) into the stored
+        records (read them with points())."""
+        ctx = _ctx(self.device)
+        if point_ids is None:
+            self.update_normal_and_depth_batch_device(None, self.max_points)
+        else:
+            import torch
+            ids = torch.from_numpy(_i32(point_ids)).to("cuda:%d" % self.device)
+            torch.cuda.synchronize()
+            self.update_normal_and_depth_batch_device(ids.data_ptr(), ids.numel())
+        ctx.sync()
