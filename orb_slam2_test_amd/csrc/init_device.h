@@ -5,8 +5,9 @@
 // where the reference holds CV_32F.  Functions that take (lane, nl) split independent tasks
 // over a group of nl cooperating lanes that share one InitWork (`for (e = lane; e < tasks; e
 // += nl)`), so the results do not depend on nl; the host program calls the same statements
-// with lane = 0, nl = 1.  INIT_SYNC() separates the phases: every lane of the workgroup reaches
-// every one of them (all trip counts are fixed).
+// with lane = 0, nl = 1.  ORBG_GROUP_SYNC() separates the phases: every lane of the workgroup
+// reaches every one of them (all trip counts are fixed).  The eigen and singular value solves
+// are jacobi.h's.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -15,18 +16,13 @@
 #include <string.h>
 
 #include "init_args.h"
+#include "jacobi.h"
 
 namespace orbg {
 
 #define ORBG_INIT_SWEEPS9 12  // round-robin sweeps of the 9x9 eigen solves
 #define ORBG_INIT_SWEEPS3 12  // cyclic sweeps of the one-sided 3x3 Jacobi
 #define ORBG_INIT_SWEEPS4 10  // cyclic sweeps of Triangulate's one-sided 4x4 Jacobi
-
-#ifdef __HIP_DEVICE_COMPILE__
-#define INIT_SYNC() __syncthreads()
-#else
-#define INIT_SYNC() ((void)0)
-#endif
 
 // One (pair, iteration): both models side by side (index 0: H, 1: F).
 struct InitWork {
@@ -38,14 +34,6 @@ struct InitWork {
     int idx[8];
     int ok;
 };
-
-__host__ __device__ static inline void init_rot(double theta, double *c, double *s)
-{
-    const double at = fabs(theta) + sqrt(theta * theta + 1.0);
-    const double t = (theta < 0.0 ? -1.0 : 1.0) / at;
-    *c = 1.0 / sqrt(t * t + 1.0);
-    *s = t * *c;
-}
 
 __host__ __device__ static inline bool init_finite9(const float *m)
 {
@@ -79,92 +67,19 @@ __host__ __device__ static inline void init_rows(InitWork *W, int j)
     f[6] = u1, f[7] = v1, f[8] = 1.f;
 }
 
-// (row, column), row <= column, of the e-th unique entry of a symmetric 9x9
-__host__ __device__ static inline void init_sym_index(int e, int *r, int *c)
-{
-    int row = 0;
-    while (e >= 9 - row) {
-        e -= 9 - row;
-        row++;
-    }
-    *r = row;
-    *c = row + e;
-}
-
 // A^T A of both models: 2 x 45 sums over the rows in index order
 __host__ __device__ static inline void init_ata(InitWork *W, int lane, int nl)
 {
     for (int e = lane; e < 90; e += nl) {
         const int m = e / 45;
         int r, c;
-        init_sym_index(e - 45 * m, &r, &c);
+        sym_index<9>(e - 45 * m, &r, &c);
         const int k0 = m ? 16 : 0, k1 = m ? 24 : 16;
         double s = 0.0;
         for (int k = k0; k < k1; k++) s += (double)W->rows[k][r] * (double)W->rows[k][c];
         W->A[m][9 * r + c] = s;
         W->A[m][9 * c + r] = s;
     }
-}
-
-// The round-robin ordering of nine indices: ten players with a bye, nine rounds of four
-// disjoint rotations.
-__host__ __device__ static inline void init_round_pair(int round, int t, int *p, int *q)
-{
-    const int a = (round + t + 1) % 9, b = (round + 8 - t) % 9;
-    *p = a < b ? a : b;
-    *q = a < b ? b : a;
-}
-
-// Cyclic Jacobi on both 9x9 matrices at once: 8 rotations a round, lanes split them and the
-// 72 column / row updates (one lane runs them in turn to the same bits, as the planes of a
-// round share no entry).
-__host__ __device__ static inline void init_eig9(InitWork *W, int lane, int nl)
-{
-    for (int e = lane; e < 162; e += nl) {
-        const int m = e / 81, k = e - 81 * m;
-        W->V[m][k] = (k / 9 == k % 9) ? 1.0 : 0.0;
-    }
-    INIT_SYNC();
-    for (int sweep = 0; sweep < ORBG_INIT_SWEEPS9; sweep++)
-        for (int round = 0; round < 9; round++) {
-            for (int e = lane; e < 8; e += nl) {
-                const int m = e >> 2, t = e & 3;
-                const double *A = W->A[m];
-                int p, q;
-                init_round_pair(round, t, &p, &q);
-                const double apq = A[9 * p + q];
-                double c = 1.0, s = 0.0;
-                if (apq != 0.0) init_rot((A[10 * q] - A[10 * p]) / (2.0 * apq), &c, &s);
-                W->cs[m][2 * t] = c;
-                W->cs[m][2 * t + 1] = s;
-            }
-            INIT_SYNC();
-            for (int e = lane; e < 72; e += nl) {  // A <- A J, V <- V J
-                const int m = e / 36, r = e - 36 * m, t = r / 9, k = r - 9 * t;
-                double *A = W->A[m], *V = W->V[m];
-                int p, q;
-                init_round_pair(round, t, &p, &q);
-                const double c = W->cs[m][2 * t], s = W->cs[m][2 * t + 1];
-                const double akp = A[9 * k + p], akq = A[9 * k + q];
-                A[9 * k + p] = c * akp - s * akq;
-                A[9 * k + q] = s * akp + c * akq;
-                const double vkp = V[9 * k + p], vkq = V[9 * k + q];
-                V[9 * k + p] = c * vkp - s * vkq;
-                V[9 * k + q] = s * vkp + c * vkq;
-            }
-            INIT_SYNC();
-            for (int e = lane; e < 72; e += nl) {  // A <- J^T A, the rotated entry set to zero
-                const int m = e / 36, r = e - 36 * m, t = r / 9, k = r - 9 * t;
-                double *A = W->A[m];
-                int p, q;
-                init_round_pair(round, t, &p, &q);
-                const double c = W->cs[m][2 * t], s = W->cs[m][2 * t + 1];
-                const double apk = A[9 * p + k], aqk = A[9 * q + k];
-                A[9 * p + k] = k == q ? 0.0 : c * apk - s * aqk;
-                A[9 * q + k] = k == p ? 0.0 : s * apk + c * aqk;
-            }
-            INIT_SYNC();
-        }
 }
 
 // vt.row(8): the eigenvector of least eigenvalue (the first of equals)
@@ -176,63 +91,12 @@ __host__ __device__ static inline void init_null_vector(const InitWork *W, int m
     for (int k = 0; k < 9; k++) h[k] = W->V[m][9 * k + j];
 }
 
-// One-sided Jacobi: the columns of b are rotated until they are orthogonal (b <- b V).
-__host__ __device__ static inline void init_jacobi3(double b[3][3], double v[3][3])
-{
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) v[i][j] = i == j ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < ORBG_INIT_SWEEPS3; sweep++) {
-#pragma unroll
-        for (int p = 0; p < 2; p++)
-#pragma unroll
-            for (int q = p + 1; q < 3; q++) {
-                const double al = (b[0][p] * b[0][p] + b[1][p] * b[1][p]) + b[2][p] * b[2][p];
-                const double be = (b[0][q] * b[0][q] + b[1][q] * b[1][q]) + b[2][q] * b[2][q];
-                const double ga = (b[0][p] * b[0][q] + b[1][p] * b[1][q]) + b[2][p] * b[2][q];
-                if (ga == 0.0) continue;
-                double c, s;
-                init_rot((be - al) / (2.0 * ga), &c, &s);
-#pragma unroll
-                for (int k = 0; k < 3; k++) {
-                    const double bkp = b[k][p], bkq = b[k][q];
-                    b[k][p] = c * bkp - s * bkq;
-                    b[k][q] = s * bkp + c * bkq;
-                    const double vkp = v[k][p], vkq = v[k][q];
-                    v[k][p] = c * vkp - s * vkq;
-                    v[k][q] = s * vkp + c * vkq;
-                }
-            }
-    }
-}
-
-__host__ __device__ static inline double init_colnorm2(const double b[3][3], int k)
-{
-    return (b[0][k] * b[0][k] + b[1][k] * b[1][k]) + b[2][k] * b[2][k];
-}
-
-__host__ __device__ static inline void init_swapcol(double b[3][3], double v[3][3], double n2[3],
-                                                    int i, int j)
-{
-    if (n2[j] > n2[i]) {
-        double x = n2[i];
-        n2[i] = n2[j], n2[j] = x;
-        for (int k = 0; k < 3; k++) {
-            x = b[k][i], b[k][i] = b[k][j], b[k][j] = x;
-            x = v[k][i], v[k][i] = v[k][j], v[k][j] = x;
-        }
-    }
-}
-
-// b <- b V with the columns in descending norm order (stable)
+// One-sided Jacobi, b <- b V, with the columns in descending norm order (stable)
 __host__ __device__ static inline void init_jacobi3_sorted(double b[3][3], double v[3][3], double n2[3])
 {
-    init_jacobi3(b, v);
-    for (int k = 0; k < 3; k++) n2[k] = init_colnorm2(b, k);
-    init_swapcol(b, v, n2, 0, 1);
-    init_swapcol(b, v, n2, 1, 2);
-    init_swapcol(b, v, n2, 0, 1);
+    jacobi_onesided<3, ORBG_INIT_SWEEPS3>(b, v);
+    for (int k = 0; k < 3; k++) n2[k] = jacobi_coldot<3>(b, k, k);
+    sort3_desc(n2, b, v);
 }
 
 // m = T2 side * x * T1 for the 3x3 x (row-major), T1 = [s1x 0 t1x; 0 s1y t1y; 0 0 1]
@@ -305,10 +169,11 @@ __host__ __device__ static inline void init_hypothesis(InitWork *W, const InitNo
                                                        int lane, int nl)
 {
     for (int j = lane; j < 8; j += nl) init_rows(W, j);
-    INIT_SYNC();
+    ORBG_GROUP_SYNC();
     init_ata(W, lane, nl);
-    INIT_SYNC();
-    init_eig9(W, lane, nl);
+    ORBG_GROUP_SYNC();
+    // both 9x9 eigen solves at once: a round's 8 rotations and 72 updates split over the lanes
+    jacobi_eig_lanes<2, 9, ORBG_INIT_SWEEPS9>(W->A[0], W->V[0], W->cs[0], lane, nl);
     for (int m = lane; m < 2; m += nl) {
         double h[9];
         init_null_vector(W, m, h);
@@ -413,10 +278,7 @@ __host__ __device__ static inline void init_svd3(const double a[9], double U[3][
     for (int k = 0; k < 3; k++) {
         w[k] = sqrt(n2[k]);
         const double inv = 1.0 / w[k];
-        double big = V[0][k];
-        if (fabs(V[1][k]) > fabs(big)) big = V[1][k];
-        if (fabs(V[2][k]) > fabs(big)) big = V[2][k];
-        const double sg = big < 0.0 ? -1.0 : 1.0;
+        const double sg = largest_sign3(V, k);
         for (int i = 0; i < 3; i++) {
             U[i][k] = (U[i][k] * inv) * sg;
             V[i][k] = V[i][k] * sg;
@@ -587,6 +449,8 @@ __host__ __device__ static inline void init_triangulate(const float *P2, const o
         b[2][c] = u2 * P2[8 + c] - P2[c];
         b[3][c] = v2 * P2[8 + c] - P2[4 + c];
     }
+    // jacobi_onesided's statements at 4x4, written out: through the call k_init_reconstruct,
+    // whose inner loop this is, measured 0.7 % slower
 #pragma unroll
     for (int i = 0; i < 4; i++)
 #pragma unroll
@@ -601,7 +465,7 @@ __host__ __device__ static inline void init_triangulate(const float *P2, const o
                 const double ga = ((b[0][p] * b[0][q] + b[1][p] * b[1][q]) + b[2][p] * b[2][q]) + b[3][p] * b[3][q];
                 if (ga == 0.0) continue;
                 double c, s;
-                init_rot((be - al) / (2.0 * ga), &c, &s);
+                jacobi_rot((be - al) / (2.0 * ga), &c, &s);
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
                     const double bkp = b[k][p], bkq = b[k][q];

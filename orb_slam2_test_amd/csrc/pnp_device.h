@@ -6,16 +6,18 @@
 // functions take (lane, nl): the caller's position in a group of nl cooperating lanes that
 // share one PnpWork.  Work is split into independent tasks (`for (e = lane; e < tasks; e +=
 // nl)`), each of which computes its outputs alone, so the results do not depend on nl; a
-// host program calls the same statements with lane = 0, nl = 1.  PNP_SYNC() separates the
-// phases: every lane of the workgroup reaches every one of them (all trip counts are fixed).
+// host program calls the same statements with lane = 0, nl = 1.  ORBG_GROUP_SYNC() separates
+// the phases: every lane of the workgroup reaches every one of them (all trip counts are fixed).
 //
 // Runtime-indexed arrays live in PnpWork (LDS on the device); the 3x3 problems are unrolled
-// into registers.
+// into registers.  The eigen and singular value solves are jacobi.h's.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+
+#include "jacobi.h"
 
 namespace orbg {
 
@@ -24,12 +26,6 @@ namespace orbg {
 #endif
 #define ORBG_PNP_SWEEPS3 10   // cyclic sweeps of the 3x3 eigen / singular value solves
 #define ORBG_PNP_GN_STEPS 5   // gauss_newton's iterations_number
-
-#ifdef __HIP_DEVICE_COMPILE__
-#define PNP_SYNC() __syncthreads()
-#else
-#define PNP_SYNC() ((void)0)
-#endif
 
 // One point as the sums see it: the barycentric coordinates a[0..3], du = uc - u, dv = vc - v
 // and d = pw - cws[0].
@@ -58,89 +54,15 @@ struct PnpWork {
     PnpCand c[3];
 };
 
-// ---- 3x3 helpers (registers: every index is a compile-time constant after unrolling) ----
-
-__host__ __device__ static inline void pnp_rot(double theta, double *c, double *s)
-{
-    const double at = fabs(theta) + sqrt(theta * theta + 1.0);
-    const double t = (theta < 0.0 ? -1.0 : 1.0) / at;
-    *c = 1.0 / sqrt(t * t + 1.0);
-    *s = t * *c;
-}
-
-// eigenvectors of the symmetric a (columns of v), eigenvalues left on the diagonal
-__host__ __device__ static inline void pnp_eig3(double a[3][3], double v[3][3])
-{
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) v[i][j] = i == j ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < ORBG_PNP_SWEEPS3; sweep++) {
-#pragma unroll
-        for (int p = 0; p < 2; p++)
-#pragma unroll
-            for (int q = p + 1; q < 3; q++) {
-                const double apq = a[p][q];
-                if (apq == 0.0) continue;
-                double c, s;
-                pnp_rot((a[q][q] - a[p][p]) / (2.0 * apq), &c, &s);
-#pragma unroll
-                for (int k = 0; k < 3; k++) {
-                    const double akp = a[k][p], akq = a[k][q];
-                    a[k][p] = c * akp - s * akq;
-                    a[k][q] = s * akp + c * akq;
-                }
-#pragma unroll
-                for (int k = 0; k < 3; k++) {
-                    const double apk = a[p][k], aqk = a[q][k];
-                    a[p][k] = c * apk - s * aqk;
-                    a[q][k] = s * apk + c * aqk;
-                }
-                a[p][q] = a[q][p] = 0.0;
-#pragma unroll
-                for (int k = 0; k < 3; k++) {
-                    const double vkp = v[k][p], vkq = v[k][q];
-                    v[k][p] = c * vkp - s * vkq;
-                    v[k][q] = s * vkp + c * vkq;
-                }
-            }
-    }
-}
-
-// R = U V^T of b = U S V^T by one-sided Jacobi: the columns of b are rotated until they are
-// orthogonal (b V = U S), then scaled by their norms.  estimate_R_and_t's cvSVD.
+// R = U V^T of b = U S V^T by one-sided Jacobi (b V = U S), the columns then scaled by their
+// norms.  estimate_R_and_t's cvSVD.  In registers: every index is a compile-time constant.
 __host__ __device__ static inline void pnp_polar3(double b[3][3], double R[9])
 {
     double v[3][3];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) v[i][j] = i == j ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < ORBG_PNP_SWEEPS3; sweep++) {
-#pragma unroll
-        for (int p = 0; p < 2; p++)
-#pragma unroll
-            for (int q = p + 1; q < 3; q++) {
-                const double al = (b[0][p] * b[0][p] + b[1][p] * b[1][p]) + b[2][p] * b[2][p];
-                const double be = (b[0][q] * b[0][q] + b[1][q] * b[1][q]) + b[2][q] * b[2][q];
-                const double ga = (b[0][p] * b[0][q] + b[1][p] * b[1][q]) + b[2][p] * b[2][q];
-                if (ga == 0.0) continue;
-                double c, s;
-                pnp_rot((be - al) / (2.0 * ga), &c, &s);
-#pragma unroll
-                for (int k = 0; k < 3; k++) {
-                    const double bkp = b[k][p], bkq = b[k][q];
-                    b[k][p] = c * bkp - s * bkq;
-                    b[k][q] = s * bkp + c * bkq;
-                    const double vkp = v[k][p], vkq = v[k][q];
-                    v[k][p] = c * vkp - s * vkq;
-                    v[k][q] = s * vkp + c * vkq;
-                }
-            }
-    }
+    jacobi_onesided<3, ORBG_PNP_SWEEPS3>(b, v);
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-        const double inv = 1.0 / sqrt((b[0][k] * b[0][k] + b[1][k] * b[1][k]) + b[2][k] * b[2][k]);
+        const double inv = 1.0 / sqrt(jacobi_coldot<3>(b, k, k));
         b[0][k] *= inv;
         b[1][k] *= inv;
         b[2][k] *= inv;
@@ -160,35 +82,18 @@ __host__ __device__ static inline void pnp_control_points(PnpWork *W, const doub
 {
     double a[3][3] = {{cov[0], cov[1], cov[2]}, {cov[1], cov[3], cov[4]}, {cov[2], cov[4], cov[5]}};
     double v[3][3];
-    pnp_eig3(a, v);
+    jacobi_eig_sym<3, ORBG_PNP_SWEEPS3>(a, v);
     double lam[3] = {a[0][0], a[1][1], a[2][2]};
-#define PNP_SWAPCOL(i, j)                          \
-    if (lam[j] > lam[i]) {                         \
-        double x = lam[i];                         \
-        lam[i] = lam[j], lam[j] = x;               \
-        _Pragma("unroll") for (int k = 0; k < 3; k++) \
-        {                                          \
-            x = v[k][i];                           \
-            v[k][i] = v[k][j], v[k][j] = x;        \
-        }                                          \
-    }
-    PNP_SWAPCOL(0, 1)
-    PNP_SWAPCOL(1, 2)
-    PNP_SWAPCOL(0, 1)
-#undef PNP_SWAPCOL
+    sort3_desc(lam, v);
     // An axis' sign is the SVD routine's choice, and with noisy points the pose depends on it
     // (the control tetrahedron is mirrored).  Here: the component of largest magnitude (the
     // first of equals) is positive.
 #pragma unroll
-    for (int j = 0; j < 3; j++) {
-        double big = v[0][j];
-        if (fabs(v[1][j]) > fabs(big)) big = v[1][j];
-        if (fabs(v[2][j]) > fabs(big)) big = v[2][j];
-        if (big < 0.0) {
+    for (int j = 0; j < 3; j++)
+        if (largest_sign3(v, j) < 0.0) {
 #pragma unroll
             for (int k = 0; k < 3; k++) v[k][j] = -v[k][j];
         }
-    }
     W->npts = n;
 #pragma unroll
     for (int k = 0; k < 3; k++) W->cw[0][k] = c0[k];
@@ -219,18 +124,6 @@ __host__ __device__ static inline void pnp_point_rec(const PnpWork *W, double X,
     rec[6] = d0, rec[7] = d1, rec[8] = d2;
 }
 
-// (row, column), row <= column, of the e-th unique entry of the symmetric 12x12
-__host__ __device__ static inline void pnp_sym_index(int e, int *r, int *c)
-{
-    int row = 0;
-    while (e >= 12 - row) {
-        e -= 12 - row;
-        row++;
-    }
-    *r = row;
-    *c = row + e;
-}
-
 // One point's term of sum e: M^T M [3j + p][3k + q] += a_j a_k w_pq with the two rows of
 // fill_M r1 = (fu, 0, du), r2 = (0, fv, dv) and w = r1 r1^T + r2 r2^T; then K and Sa.
 __host__ __device__ static inline double pnp_sum_term(int e, const double *rec, double fu, double fv)
@@ -241,7 +134,7 @@ __host__ __device__ static inline double pnp_sum_term(int e, const double *rec, 
         return rec[m] * rec[6 + k];
     }
     int r, c;
-    pnp_sym_index(e, &r, &c);
+    sym_index<12>(e, &r, &c);
     const int j = r / 3, p = r - 3 * j, k = c / 3, q = c - 3 * k;
     const int lo = p < q ? p : q, hi = p < q ? q : p;
     const double du = rec[4], dv = rec[5];
@@ -261,69 +154,10 @@ __host__ __device__ static inline void pnp_sum_store(PnpWork *W, int e, double s
         (&W->K[0][0])[e - 78] = s;
     } else {
         int r, c;
-        pnp_sym_index(e, &r, &c);
+        sym_index<12>(e, &r, &c);
         W->A[12 * r + c] = s;
         W->A[12 * c + r] = s;
     }
-}
-
-// ---- the 12x12 eigen solve: cyclic Jacobi in the round-robin ordering, whose 11 rounds per
-// sweep hold 6 disjoint rotations each (lanes split them; one lane runs them in turn to the
-// same bits, as the six planes share no entry).
-__host__ __device__ static inline void pnp_round_pair(int round, int t, int *p, int *q)
-{
-    int a, b;
-    if (t == 0) {
-        a = 11, b = round;
-    } else {
-        a = (round + t) % 11;
-        b = (round + 11 - t) % 11;
-    }
-    *p = a < b ? a : b;
-    *q = a < b ? b : a;
-}
-
-__host__ __device__ static inline void pnp_eig12(PnpWork *W, int lane, int nl)
-{
-    double *A = W->A, *V = W->V;
-    for (int e = lane; e < 144; e += nl) V[e] = (e / 12 == e % 12) ? 1.0 : 0.0;
-    PNP_SYNC();
-    for (int sweep = 0; sweep < ORBG_PNP_SWEEPS12; sweep++)
-        for (int round = 0; round < 11; round++) {
-            for (int t = lane; t < 6; t += nl) {
-                int p, q;
-                pnp_round_pair(round, t, &p, &q);
-                const double apq = A[12 * p + q];
-                double c = 1.0, s = 0.0;
-                if (apq != 0.0) pnp_rot((A[13 * q] - A[13 * p]) / (2.0 * apq), &c, &s);
-                W->cs[2 * t] = c;
-                W->cs[2 * t + 1] = s;
-            }
-            PNP_SYNC();
-            for (int e = lane; e < 72; e += nl) {  // A <- A J, V <- V J
-                const int t = e / 12, k = e - 12 * t;
-                int p, q;
-                pnp_round_pair(round, t, &p, &q);
-                const double c = W->cs[2 * t], s = W->cs[2 * t + 1];
-                const double akp = A[12 * k + p], akq = A[12 * k + q];
-                A[12 * k + p] = c * akp - s * akq;
-                A[12 * k + q] = s * akp + c * akq;
-                const double vkp = V[12 * k + p], vkq = V[12 * k + q];
-                V[12 * k + p] = c * vkp - s * vkq;
-                V[12 * k + q] = s * vkp + c * vkq;
-            }
-            PNP_SYNC();
-            for (int e = lane; e < 72; e += nl) {  // A <- J^T A, the rotated entry set to zero
-                const int t = e / 12, k = e - 12 * t;
-                int p, q;
-                pnp_round_pair(round, t, &p, &q);
-                const double c = W->cs[2 * t], s = W->cs[2 * t + 1];
-                const double apk = A[12 * p + k], aqk = A[12 * q + k];
-                A[12 * p + k] = k == q ? 0.0 : c * apk - s * aqk;
-                A[12 * q + k] = k == p ? 0.0 : s * apk + c * aqk;
-            }
-            PNP_SYNC();
-        }
 }
 
 // Least squares of the 6 x nc system a (row-major, stride nc) x = b by Householder
@@ -493,7 +327,8 @@ __host__ __device__ static inline void pnp_candidate(PnpWork *W, int which)
 // candidate poses in W->c[].R / .t.  Every lane of the workgroup calls it.
 __host__ __device__ static inline void pnp_tail(PnpWork *W, int lane, int nl)
 {
-    pnp_eig12(W, lane, nl);
+    // the 12x12 eigen solve: a round's six rotations and 72 updates split over the lanes
+    jacobi_eig_lanes<1, 12, ORBG_PNP_SWEEPS12>(W->A, W->V, W->cs, lane, nl);
     // the four smallest eigenvalues, ascending; ties go to the lower index (every lane)
     int idx[4];
     unsigned used = 0;
@@ -514,11 +349,11 @@ __host__ __device__ static inline void pnp_tail(PnpWork *W, int lane, int nl)
         const int col = i == 0 ? idx[0] : (i == 1 ? idx[1] : (i == 2 ? idx[2] : idx[3]));
         W->nv[i][k] = W->V[12 * k + col];
     }
-    PNP_SYNC();
+    ORBG_GROUP_SYNC();
     pnp_L_rho(W, lane, nl);
-    PNP_SYNC();
+    ORBG_GROUP_SYNC();
     for (int c = lane; c < 3; c += nl) pnp_candidate(W, c);
-    PNP_SYNC();
+    ORBG_GROUP_SYNC();
 }
 
 // reprojection_error's term for one point

@@ -3,13 +3,14 @@
 //
 // The arithmetic is plain fp32 in a fixed operation order (the build has -ffp-contract=off),
 // written as __host__ __device__ functions so that a host program can run the very same
-// statements.
+// statements.  The 4x4 eigen solve is jacobi.h's.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/orbg.h"
+#include "jacobi.h"
 
 namespace orbg {
 
@@ -72,34 +73,6 @@ __host__ __device__ static inline void sim3_project(const float *P, float fx, fl
     *v = fy * (P[1] * invz) + cy;
 }
 
-// One Jacobi rotation of the symmetric 4x4 `a` in the (p, q) plane, accumulated into `v`
-// (columns = eigenvectors).
-__host__ __device__ static inline void sim3_jacobi_rot(float a[4][4], float v[4][4], int p, int q)
-{
-    const float apq = a[p][q];
-    if (apq == 0.0f) return;
-    const float theta = (a[q][q] - a[p][p]) / (2.0f * apq);
-    const float at = fabsf(theta) + sqrtf(theta * theta + 1.0f);
-    const float t = (theta < 0.0f ? -1.0f : 1.0f) / at;
-    const float c = 1.0f / sqrtf(t * t + 1.0f), s = t * c;
-    for (int k = 0; k < 4; k++) {  // A <- A J
-        const float akp = a[k][p], akq = a[k][q];
-        a[k][p] = c * akp - s * akq;
-        a[k][q] = s * akp + c * akq;
-    }
-    for (int k = 0; k < 4; k++) {  // A <- J^T A
-        const float apk = a[p][k], aqk = a[q][k];
-        a[p][k] = c * apk - s * aqk;
-        a[q][k] = s * apk + c * aqk;
-    }
-    a[p][q] = a[q][p] = 0.0f;
-    for (int k = 0; k < 4; k++) {
-        const float vkp = v[k][p], vkq = v[k][q];
-        v[k][p] = c * vkp - s * vkq;
-        v[k][q] = s * vkp + c * vkq;
-    }
-}
-
 // Sim3Solver::ComputeSim3 (:226-337), Horn 1987 on three point pairs: p1[k] / p2[k] = the
 // camera-1 / camera-2 coordinates of sample k.  Writes R12, t12, s12; returns false for a
 // degenerate sample (no positive largest eigenvalue, or a scale that is zero or not finite), where
@@ -131,17 +104,9 @@ __host__ __device__ static inline bool sim3_horn(const float p1[3][3], const flo
     a[2][2] = (-M[0][0] + M[1][1]) - M[2][2];
     a[2][3] = M[1][2] + M[2][1];
     a[3][3] = (-M[0][0] - M[1][1]) + M[2][2];
-    for (int i = 0; i < 4; i++)
-        for (int j = 0; j < 4; j++) {
-            if (j < i) a[i][j] = a[j][i];
-            v[i][j] = i == j ? 1.0f : 0.0f;
-        }
-    for (int sweep = 0; sweep < ORBG_SIM3_JACOBI_SWEEPS; sweep++) {
-#pragma unroll
-        for (int p = 0; p < 3; p++)
-#pragma unroll
-            for (int q = p + 1; q < 4; q++) sim3_jacobi_rot(a, v, p, q);
-    }
+    for (int i = 1; i < 4; i++)
+        for (int j = 0; j < i; j++) a[i][j] = a[j][i];
+    jacobi_eig_sym<4, ORBG_SIM3_JACOBI_SWEEPS>(a, v);
     float lam = a[0][0], qw = v[0][0], qx = v[1][0], qy = v[2][0], qz = v[3][0];
 #pragma unroll
     for (int k = 1; k < 4; k++)  // static indices only: everything stays in registers

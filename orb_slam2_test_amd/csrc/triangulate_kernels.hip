@@ -20,6 +20,7 @@
 #include <cmath>
 
 #include "../../include/orbg.h"
+#include "jacobi.h"
 #include "orbg_device.h"
 #include "orbg_launch.h"
 
@@ -306,6 +307,7 @@ __global__ __launch_bounds__(256) void k_tri_geometry(const orbg_kf_camera *__re
 
 // the null vector of the 4x4 float A (row-major) in double: cyclic Jacobi on A^T A, 12
 // sweeps at most, the column of V at the least diagonal entry (orc_tri_nullvec)
+// (jacobi.h's rotation alone: the loop mirrors the oracle's, early exit and computed entries included)
 __device__ void tri_nullvec(const float *A, double *v)
 {
     double B[16], V[16];
@@ -332,10 +334,8 @@ __device__ void tri_nullvec(const float *A, double *v)
             for (int q = p + 1; q < 4; q++) {
                 const double apq = B[4 * p + q];
                 if (apq == 0.0) continue;
-                const double theta = (B[4 * q + q] - B[4 * p + p]) / (2.0 * apq);
-                double t = 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0));
-                if (theta < 0.0) t = -t;
-                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+                double c, s;
+                jacobi_rot((B[4 * q + q] - B[4 * p + p]) / (2.0 * apq), &c, &s);
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
                     const double bkp = B[4 * k + p], bkq = B[4 * k + q];
