@@ -88,6 +88,10 @@
  *                                     (+ SearchLocalPoints' mnLastFrameSeen test, :1644-1683)
  *   orbg_map_update_normal_and_depth_batch_device
  *                                     MapPoint::UpdateNormalAndDepth  src/MapPoint.cc:457-518
+ *   orbg_map_set_bad_flag ........... KeyFrame::SetBadFlag in full (+ MapPoint::EraseObservation /
+ *                                     SetBadFlag)  src/KeyFrame.cc:622-720, src/MapPoint.cc:159-232
+ *   orbg_map_keyframe_culling ....... LocalMapping::KeyFrameCulling  src/LocalMapping.cc:804-877
+ *   orbg_map_point_culling .......... LocalMapping::MapPointCulling  src/LocalMapping.cc:227-270
  *
  * Batched, device-resident entry points (orbg_*_device) run the same kernels over many
  * frames at once; they exist for the batched-sequence mode and the bench.
@@ -1305,7 +1309,8 @@ int orbg_map_set_parent(orbg_ctx *ctx, orbg_map *map, int slot, int parent);
  * its W row are cleared, and in every row t with W[t][slot] > 0 the entry is zeroed and t's
  * ordered list re-sorted over all its non-zero weights (EraseConnection -> UpdateBestCovisibles).
  * The spanning-tree repair of :650-715 stays with the caller, through orbg_map_set_parent:
- * children of the slot keep it as their parent until then. */
+ * children of the slot keep it as their parent until then.  (orbg_map_set_bad_flag below is
+ * SetBadFlag in full.) */
 int orbg_map_erase_keyframe(orbg_ctx *ctx, orbg_map *map, int slot);
 int orbg_map_clear(orbg_ctx *ctx, orbg_map *map);
 /* The observation index and the children lists are rebuilt on the device by the first query
@@ -1400,6 +1405,113 @@ int orbg_map_local_points(orbg_ctx *ctx, orbg_map *map, const int32_t *local_kfs
  * mfMinDistance = mfMaxDistance / scaleFactor[nlevels - 1] in float (the context's tables). */
 int orbg_map_update_normal_and_depth_batch_device(orbg_ctx *ctx, orbg_map *map,
                                                   const int32_t *d_point_ids, int n);
+
+/* ---- KeyFrame::SetBadFlag, LocalMapping::KeyFrameCulling / MapPointCulling on the Map ----
+ * (src/KeyFrame.cc:560-720, src/LocalMapping.cc:227-270 and 804-877, src/MapPoint.cc:121-232,
+ * 325-329).  Further state, all of it defaulting so that the calls above give what they gave
+ * without it.  Per feature of a row a flags byte (0 when a slot becomes live; an overwrite of a
+ * live slot by orbg_map_set_keyframe* keeps it, these are properties of the keypoints).  Per
+ * slot mbNotErase and mbToBeErased (cleared when a slot becomes live).  Per point mnFirstKFid
+ * (an mnId, not a slot), mnVisible and mnFound: 0, 1 and 1 after orbg_map_create / clear;
+ * orbg_map_set_points* does not touch them.
+ * Observations() of a point is the sum over its observations (the live rows that hold it) of 2
+ * for a STEREO feature and 1 otherwise: MapPoint::nObs.  A point set bad by the calls below
+ * loses ORBG_MP_VALID and is removed from every row that holds it (EraseMapPointMatch). */
+#define ORBG_MAP_FEAT_STEREO 1   /* mvuRight[idx] >= 0: the observation counts twice */
+#define ORBG_MAP_FEAT_CLOSE 2    /* !(mvDepth[idx] > mThDepth || mvDepth[idx] < 0) */
+/* flags[i], i < n, of a live slot's features (the rest of the row: 0).  A dead slot: no change. */
+int orbg_map_set_keyframe_features(orbg_ctx *ctx, orbg_map *map, int slot, const uint8_t *flags,
+                                   int n);
+/* the same for slots d_slots[i], i < n: d_flags + i * row_cap, d_counts[i] entries */
+int orbg_map_set_keyframe_features_device(orbg_ctx *ctx, orbg_map *map, const int32_t *d_slots,
+                                          int n, const uint8_t *d_flags, int row_cap,
+                                          const int32_t *d_counts);
+/* on = 1: KeyFrame::SetNotErase.  on = 0: SetErase once the caller has seen mspLoopEdges.empty():
+ * clears mbNotErase and, if mbToBeErased is set, runs orbg_map_set_bad_flag (*erased = 1, else
+ * 0; may be NULL).  A dead slot: no change.  Synchronises. */
+int orbg_map_set_not_erase(orbg_ctx *ctx, orbg_map *map, int slot, int on, int32_t *erased);
+/* mnFirstKFid / mnVisible / mnFound of points first .. first + n - 1 (a NULL array leaves that
+ * field as it is); the device form takes ids d_ids[i] (NULL: first + i; out of range: skipped) */
+int orbg_map_set_point_stats(orbg_ctx *ctx, orbg_map *map, int first, int n,
+                             const int32_t *first_kf_id, const int32_t *visible,
+                             const int32_t *found);
+int orbg_map_set_point_stats_device(orbg_ctx *ctx, orbg_map *map, const int32_t *d_ids, int first,
+                                    int n, const int32_t *d_first_kf_id, const int32_t *d_visible,
+                                    const int32_t *d_found);
+/* reads them back, with nobs[i] = Observations() (any array may be NULL) */
+int orbg_map_get_point_stats(orbg_ctx *ctx, orbg_map *map, int first, int n, int32_t *first_kf_id,
+                             int32_t *visible, int32_t *found, int32_t *nobs);
+/* MapPoint::IncreaseVisible(amount) of the points d_ids[i], i < n: an id of -1 (or out of
+ * range) is skipped; with d_proj non-NULL entry i counts only if d_proj[i].flags &
+ * ORBG_MP_VALID (what orbg_is_in_frustum_batch_device leaves).  Duplicates add up. */
+int orbg_map_increase_visible_device(orbg_ctx *ctx, orbg_map *map, const int32_t *d_ids,
+                                     const orbg_map_projection *d_proj, int n, int amount);
+/* MapPoint::IncreaseFound(amount), likewise */
+int orbg_map_increase_found_device(orbg_ctx *ctx, orbg_map *map, const int32_t *d_ids, int n,
+                                   int amount);
+/* the row of a slot (mvpMapPoints as ids): *n = its length (0 for a dead slot), the first cap
+ * entries written */
+int orbg_map_get_keyframe_points(orbg_ctx *ctx, orbg_map *map, int slot, int32_t *ids, int cap,
+                                 int32_t *n);
+/* mpRefKF of points first .. first + n - 1 as slots (-1: none) */
+int orbg_map_get_point_refs(orbg_ctx *ctx, orbg_map *map, int first, int n, int32_t *ref);
+
+/* KeyFrame::SetBadFlag in full.  *status (may be NULL): 0 = the root or a dead slot, nothing
+ * happens; 2 = mbNotErase is set: mbToBeErased is set and nothing else; 1 = erased: everything
+ * orbg_map_erase_keyframe does, and for every good point p of the row
+ * MapPoint::EraseObservation: the entry leaves the row; if mpRefKF[p] was the slot it becomes
+ * the lowest remaining observing slot (-1 if none remains: the reference dereferences begin()
+ * of an empty map there); if the remaining Observations(p) <= 2 the point goes bad as above.
+ * A point that is already bad has no observations and is skipped.  Then the spanning-tree
+ * repair of :650-715 over the children (the live slots whose parent is the slot): candidates
+ * start as {parent[slot]}; in each round, over the children in ascending slot order (bad ones
+ * skipped), their ordered lists in list order and the candidates, the triple with the greatest
+ * GetWeight wins by strict >, that is the first one met; that child changes parent and becomes
+ * a candidate; when no child is connected to a candidate the remaining children (bad ones
+ * included) take parent[slot].  The lists read are the children's lists after this erasure's
+ * EraseConnection -> UpdateBestCovisibles (a re-sort over all non-zero weights of the row, so
+ * sub-threshold entries may enter); a child not connected to the slot keeps its stored list.
+ * parent[slot] itself stays (mTcp is the caller's); a dead slot is never returned as a child:
+ * the repair re-parents every live child, and UpdateLocalKeyFrames skips dead and bad ones.
+ * Synchronises. */
+int orbg_map_set_bad_flag(orbg_ctx *ctx, orbg_map *map, int slot, int32_t *status);
+
+typedef struct {
+    int32_t slot;
+    int32_t status;      /* 0 kept, 1 erased, 2 marked to-be-erased (mbNotErase), 3 skipped */
+    int32_t nmps;        /* nMPs and nRedundantObservations as evaluated at the entry's turn */
+    int32_t nredundant;
+} orbg_cull_record;
+/* LocalMapping::KeyFrameCulling with mpCurrentKeyFrame = slot.  vpLocalKeyFrames is the slot's
+ * ordered list as it stands when the call starts.  Per entry t in list order: skipped if root,
+ * dead or bad; else over t's features in index order a NULL or bad point is skipped, with
+ * !monocular a feature that is not CLOSE is skipped, nMPs++, and if Observations(p) > 3 and at
+ * least three other observers have an octave <= this feature's octave + 1 the point is
+ * redundant; if (double)nRedundant > 0.9 * (double)nMPs, orbg_map_set_bad_flag runs on t before
+ * the next entry is scored: the result is the sequential one.  The start-of-call scores of all
+ * entries come from one launch (a workgroup per entry); a sequential pass then re-scores an
+ * entry only if an earlier erasure of this call changed Observations() of one of its points.
+ * One record per list entry in list order; d_nrec[0] = the list length, only the first rec_cap
+ * records are written, the culling acts on all.  The caller forwards status-1 slots to
+ * orbg_kfdb_erase and learns which points went bad from orbg_map_get_points. */
+int orbg_map_keyframe_culling_device(orbg_ctx *ctx, orbg_map *map, int slot, int monocular,
+                                     orbg_cull_record *d_records, int rec_cap, int32_t *d_nrec);
+/* host arrays; synchronises.  ORBG_ERANGE when the list is longer than rec_cap. */
+int orbg_map_keyframe_culling(orbg_ctx *ctx, orbg_map *map, int slot, int monocular,
+                              orbg_cull_record *records, int rec_cap, int32_t *nrec);
+/* LocalMapping::MapPointCulling over mlpRecentAddedMapPoints = the n distinct ids d_recent[i],
+ * mpCurrentKeyFrame->mnId = current_kf_id.  Per point, in this order: bad (or an id out of
+ * range): dropped, status 1; (float)mnFound / (float)mnVisible < 0.25f (the IEEE float
+ * division): set bad, 2; current_kf_id - mnFirstKFid >= 2 && Observations() <= (monocular ? 2 :
+ * 3): set bad, 3; current_kf_id - mnFirstKFid >= 3: dropped, 4; else kept, 0.  d_recent comes
+ * back compacted in its original order, d_nout[0] entries; d_status (may be NULL) is indexed
+ * by input position. */
+int orbg_map_point_culling_device(orbg_ctx *ctx, orbg_map *map, int32_t *d_recent, int n,
+                                  int current_kf_id, int monocular, int32_t *d_nout,
+                                  int32_t *d_status);
+/* host arrays (recent in place; status may be NULL); synchronises */
+int orbg_map_point_culling(orbg_ctx *ctx, orbg_map *map, int32_t *recent, int n,
+                           int current_kf_id, int monocular, int32_t *nout, int32_t *status);
 
 /* ---------------- ORBmatcher::SearchByBoW(KeyFrame*, Frame&) ---------------- */
 /* One side of SearchByBoW pairs, device memory, in orbg_bow_transform_batch_device's layout

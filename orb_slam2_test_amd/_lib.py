@@ -108,6 +108,10 @@ EG_EDGE_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("kind", "<i4")])
 EG_MAX_BLOCKS = 262144   # blocks of H or of L per graph (ORBG_ENOTSUP past it)
 RELOC_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("min_dist", "<f4"),
                         ("max_dist", "<f4"), ("angle", "<f4"), ("flags", "<i4")])
+# orbg_cull_record (orbg_map_keyframe_culling): status 0 kept, 1 erased, 2 marked, 3 skipped
+CULL_RECORD_DTYPE = np.dtype([("slot", "<i4"), ("status", "<i4"), ("nmps", "<i4"),
+                              ("nredundant", "<i4")])
+MAP_FEAT_STEREO, MAP_FEAT_CLOSE = 1, 2
 MAPPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"),
                            ("ny", "<f4"), ("nz", "<f4"), ("min_dist", "<f4"),
                            ("max_dist", "<f4"), ("flags", "<i4")])
@@ -462,6 +466,21 @@ def lib():
         "orbg_map_local_points": (i32, [vp, vp, vp, i32, vp, i32, vp, vp, vp, i32,
                                         P(C.c_int32)]),
         "orbg_map_update_normal_and_depth_batch_device": (i32, [vp, vp, vp, i32]),
+        "orbg_map_set_keyframe_features": (i32, [vp, vp, i32, vp, i32]),
+        "orbg_map_set_keyframe_features_device": (i32, [vp, vp, vp, i32, vp, i32, vp]),
+        "orbg_map_set_not_erase": (i32, [vp, vp, i32, i32, P(C.c_int32)]),
+        "orbg_map_set_point_stats": (i32, [vp, vp, i32, i32, vp, vp, vp]),
+        "orbg_map_set_point_stats_device": (i32, [vp, vp, vp, i32, i32, vp, vp, vp]),
+        "orbg_map_get_point_stats": (i32, [vp, vp, i32, i32, vp, vp, vp, vp]),
+        "orbg_map_increase_visible_device": (i32, [vp, vp, vp, vp, i32, i32]),
+        "orbg_map_increase_found_device": (i32, [vp, vp, vp, i32, i32]),
+        "orbg_map_get_keyframe_points": (i32, [vp, vp, i32, vp, i32, P(C.c_int32)]),
+        "orbg_map_get_point_refs": (i32, [vp, vp, i32, i32, vp]),
+        "orbg_map_set_bad_flag": (i32, [vp, vp, i32, P(C.c_int32)]),
+        "orbg_map_keyframe_culling_device": (i32, [vp, vp, i32, i32, vp, i32, vp]),
+        "orbg_map_keyframe_culling": (i32, [vp, vp, i32, i32, vp, i32, P(C.c_int32)]),
+        "orbg_map_point_culling_device": (i32, [vp, vp, vp, i32, i32, i32, vp, vp]),
+        "orbg_map_point_culling": (i32, [vp, vp, vp, i32, i32, i32, P(C.c_int32), vp]),
         "orbg_sim3_ransac_iterations": (i32, [C.c_double, i32, i32, i32]),
         "orbg_sim3_solve": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
         "orbg_sim3_solve_batch_device": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp,

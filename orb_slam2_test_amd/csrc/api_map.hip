@@ -33,6 +33,7 @@ static int map_reset(orbg_map *m, hipStream_t st)
     HIPCHK(hipMemsetAsync(D.neigh, 0xFF, (size_t)D.K * ORBG_MAP_NEIGH * 4, st));
     HIPCHK(hipMemsetAsync(D.child_head, 0xFF, (size_t)D.K * 4, st));
     HIPCHK(hipMemsetAsync(D.child_next, 0xFF, (size_t)D.K * 4, st));
+    if (launch_map_point_defaults(st, D)) return set_err(ORBG_EIO, "k_map_point_defaults launch failed");
     m->dirty = m->tree_dirty = true;
     return ORBG_OK;
 }
@@ -64,6 +65,9 @@ extern "C" int orbg_map_create(orbg_ctx *c, int max_keyframes, int kf_cap, int m
     const size_t o_pt = L.take((P / 2048 + 2) * 4);
     const size_t o_ch = L.take(K * 4), o_cn = L.take(K * 4);
     const size_t o_di = L.take(K * 4), o_mk = L.take(K * 4), o_nl = L.take(4);
+    const size_t o_kf = L.take(kc), o_ke = L.take(K * 4);
+    const size_t o_pf = L.take(P * 4), o_pv = L.take(P * 4), o_pn = L.take(P * 4);
+    const size_t o_rt = L.take(K * 4), o_cl = L.take(K * 4), o_cs = L.take(K * 8), o_co = L.take(16);
     auto *m = new orbg_map();
     m->device = c->device;
     if (hipMalloc(&m->d_mem, L.total()) != hipSuccess) {
@@ -102,6 +106,15 @@ extern "C" int orbg_map_create(orbg_ctx *c, int max_keyframes, int kf_cap, int m
     D.dirty = L.at<int32_t>(b, o_di);
     D.mark = L.at<int32_t>(b, o_mk);
     D.nlive = L.at<int32_t>(b, o_nl);
+    D.kf_feat = L.at<uint8_t>(b, o_kf);
+    D.kf_erase = L.at<int32_t>(b, o_ke);
+    D.mp_first = L.at<int32_t>(b, o_pf);
+    D.mp_visible = L.at<int32_t>(b, o_pv);
+    D.mp_found = L.at<int32_t>(b, o_pn);
+    D.row_touch = L.at<int32_t>(b, o_rt);
+    D.cull_list = L.at<int32_t>(b, o_cl);
+    D.cull_score = L.at<int32_t>(b, o_cs);
+    D.cull_out = L.at<int32_t>(b, o_co);
     int rc = map_reset(m, c->stream);
     if (!rc && hipStreamSynchronize(c->stream) != hipSuccess)
         rc = set_err(ORBG_EIO, "Map: the initial clear failed");
@@ -595,5 +608,292 @@ extern "C" int orbg_map_update_normal_and_depth_batch_device(orbg_ctx *c, orbg_m
     if ((rc = launch_map_normal_depth(c->stream, m->D, d_point_ids, n, S, &c->prof)))
         return set_err(rc, "k_map_normal_depth launch failed");
     m->touched = true;
+    return ORBG_OK;
+}
+
+// ---------------------------------------------------------------------------
+// KeyFrame::SetBadFlag, LocalMapping::KeyFrameCulling / MapPointCulling (map_cull_kernels.hip)
+// ---------------------------------------------------------------------------
+static int map_range_ok(const orbg_map *m, int first, int n)
+{
+    if (n < 0 || first < 0 || (int64_t)first + n > m->D.P)
+        return set_err(ORBG_EINVAL, "ids %d .. %lld outside [0, %d)", first, (long long)first + n, m->D.P);
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_set_keyframe_features_device(orbg_ctx *c, orbg_map *m,
+                                                     const int32_t *d_slots, int n,
+                                                     const uint8_t *d_flags, int row_cap,
+                                                     const int32_t *d_counts)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (n < 0) return set_err(ORBG_EINVAL, "negative size");
+    if (n == 0) return ORBG_OK;
+    if (row_cap < 1) return set_err(ORBG_EINVAL, "row_cap < 1");
+    if (!d_slots || !d_flags || !d_counts) return set_err(ORBG_EINVAL, "NULL device array");
+    if (launch_map_set_features(c->stream, m->D, d_slots, n, d_flags, row_cap, d_counts))
+        return set_err(ORBG_EIO, "k_map_set_features launch failed");
+    m->touched = true;
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_set_keyframe_features(orbg_ctx *c, orbg_map *m, int slot,
+                                              const uint8_t *flags, int n)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_slot_ok(m, slot))) return rc;
+    if (n < 0 || n > m->D.cap) return set_err(ORBG_EINVAL, "%d features (kf_cap %d)", n, m->D.cap);
+    if (n && !flags) return set_err(ORBG_EINVAL, "NULL array");
+    const int cap = std::max(n, 1);
+    Layout L;
+    const size_t o_f = L.take(cap), o_h = L.take(8);  // slot, count
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
+    const int32_t hdr[2] = {slot, n};
+    if (n) HIPCHK(hipMemcpyAsync(b + o_f, flags, (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(b + o_h, hdr, 8, hipMemcpyHostToDevice, c->stream));
+    const int32_t *h = L.at<int32_t>(b, o_h);
+    if ((rc = orbg_map_set_keyframe_features_device(c, m, h, 1, b + o_f, cap, h + 1))) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_set_point_stats_device(orbg_ctx *c, orbg_map *m, const int32_t *d_ids,
+                                               int first, int n, const int32_t *d_first_kf_id,
+                                               const int32_t *d_visible, const int32_t *d_found)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (n < 0) return set_err(ORBG_EINVAL, "negative size");
+    if (!d_ids && (rc = map_range_ok(m, first, n))) return rc;
+    if (n == 0) return ORBG_OK;
+    if (launch_map_set_point_stats(c->stream, m->D, d_ids, first, n, d_first_kf_id, d_visible, d_found))
+        return set_err(ORBG_EIO, "k_map_set_point_stats launch failed");
+    m->touched = true;
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_set_point_stats(orbg_ctx *c, orbg_map *m, int first, int n,
+                                        const int32_t *first_kf_id, const int32_t *visible,
+                                        const int32_t *found)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_range_ok(m, first, n))) return rc;
+    if (n == 0) return ORBG_OK;
+    Layout L;
+    const size_t o[3] = {L.take((size_t)n * 4), L.take((size_t)n * 4), L.take((size_t)n * 4)};
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
+    const int32_t *src[3] = {first_kf_id, visible, found};
+    const int32_t *d[3];
+    for (int k = 0; k < 3; k++) {
+        d[k] = src[k] ? L.at<int32_t>(b, o[k]) : nullptr;
+        if (src[k]) HIPCHK(hipMemcpyAsync(b + o[k], src[k], (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    if ((rc = orbg_map_set_point_stats_device(c, m, nullptr, first, n, d[0], d[1], d[2]))) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_get_point_stats(orbg_ctx *c, orbg_map *m, int first, int n,
+                                        int32_t *first_kf_id, int32_t *visible, int32_t *found,
+                                        int32_t *nobs)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_range_ok(m, first, n))) return rc;
+    if (n == 0) return ORBG_OK;
+    const MapDev &D = m->D;
+    const size_t nb = (size_t)n * 4;
+    if (first_kf_id) HIPCHK(hipMemcpyAsync(first_kf_id, D.mp_first + first, nb, hipMemcpyDeviceToHost, c->stream));
+    if (visible) HIPCHK(hipMemcpyAsync(visible, D.mp_visible + first, nb, hipMemcpyDeviceToHost, c->stream));
+    if (found) HIPCHK(hipMemcpyAsync(found, D.mp_found + first, nb, hipMemcpyDeviceToHost, c->stream));
+    if (nobs) {
+        if ((rc = orbg_map_rebuild(c, m))) return rc;
+        Layout L;
+        const size_t o_n = L.take(nb);
+        uint8_t *b;
+        if ((rc = L.device(c, &b))) return rc;
+        if (launch_map_point_nobs(c->stream, D, first, n, L.at<int32_t>(b, o_n)))
+            return set_err(ORBG_EIO, "k_map_point_nobs launch failed");
+        m->touched = true;
+        HIPCHK(hipMemcpyAsync(nobs, b + o_n, nb, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return ORBG_OK;
+}
+
+static int map_increase(orbg_ctx *c, orbg_map *m, int32_t *counter, const int32_t *d_ids,
+                        const orbg_map_projection *d_proj, int n, int amount)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (n < 0) return set_err(ORBG_EINVAL, "negative size");
+    if (n == 0) return ORBG_OK;
+    if (!d_ids) return set_err(ORBG_EINVAL, "NULL device array");
+    if (launch_map_increase(c->stream, counter, m->D.P, d_ids, d_proj, n, amount))
+        return set_err(ORBG_EIO, "k_map_increase launch failed");
+    m->touched = true;
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_increase_visible_device(orbg_ctx *c, orbg_map *m, const int32_t *d_ids,
+                                                const orbg_map_projection *d_proj, int n,
+                                                int amount)
+{
+    return map_increase(c, m, m ? m->D.mp_visible : nullptr, d_ids, d_proj, n, amount);
+}
+
+extern "C" int orbg_map_increase_found_device(orbg_ctx *c, orbg_map *m, const int32_t *d_ids, int n,
+                                              int amount)
+{
+    return map_increase(c, m, m ? m->D.mp_found : nullptr, d_ids, nullptr, n, amount);
+}
+
+extern "C" int orbg_map_get_keyframe_points(orbg_ctx *c, orbg_map *m, int slot, int32_t *ids,
+                                            int cap, int32_t *n)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_slot_ok(m, slot))) return rc;
+    if (cap < 0 || !n || (cap && !ids)) return set_err(ORBG_EINVAL, "bad cap / NULL array");
+    int32_t cnt = 0;
+    HIPCHK(hipMemcpyAsync(&cnt, m->D.kf_n + slot, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const int nw = std::min(cnt, cap);
+    if (nw > 0)
+        HIPCHK(hipMemcpy(ids, m->D.kf_points + (size_t)slot * m->D.cap, (size_t)nw * 4, hipMemcpyDeviceToHost));
+    *n = cnt;
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_get_point_refs(orbg_ctx *c, orbg_map *m, int first, int n, int32_t *ref)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_range_ok(m, first, n))) return rc;
+    if (n == 0) return ORBG_OK;
+    if (!ref) return set_err(ORBG_EINVAL, "NULL array");
+    HIPCHK(hipMemcpyAsync(ref, m->D.mp_ref + first, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return ORBG_OK;
+}
+
+// on: 1 SetNotErase, 0 SetErase, -1 SetBadFlag; the kernel's status comes back through cull_out
+static int map_set_bad(orbg_ctx *c, orbg_map *m, int slot, int on, int32_t *status)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_slot_ok(m, slot))) return rc;
+    if (on != 1 && (rc = orbg_map_rebuild(c, m))) return rc;
+    if ((rc = launch_map_set_bad(c->stream, m->D, slot, on, ++m->epoch, m->D.cull_out, &c->prof)))
+        return set_err(rc, "k_map_set_bad launch failed");
+    m->touched = true;
+    if (on != 1) m->dirty = m->tree_dirty = true;  // rows lost entries, parents may have changed
+    int32_t st = 0;
+    HIPCHK(hipMemcpyAsync(&st, m->D.cull_out, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->prof.collect();
+    if (status) *status = st;
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_set_not_erase(orbg_ctx *c, orbg_map *m, int slot, int on, int32_t *erased)
+{
+    return map_set_bad(c, m, slot, on ? 1 : 0, erased);
+}
+
+extern "C" int orbg_map_set_bad_flag(orbg_ctx *c, orbg_map *m, int slot, int32_t *status)
+{
+    return map_set_bad(c, m, slot, -1, status);
+}
+
+extern "C" int orbg_map_keyframe_culling_device(orbg_ctx *c, orbg_map *m, int slot, int monocular,
+                                                orbg_cull_record *d_records, int rec_cap,
+                                                int32_t *d_nrec)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_slot_ok(m, slot))) return rc;
+    if (rec_cap < 0 || !d_nrec || (rec_cap && !d_records))
+        return set_err(ORBG_EINVAL, "bad rec_cap / NULL device array");
+    if ((rc = orbg_map_rebuild(c, m))) return rc;
+    if ((rc = launch_map_keyframe_culling(c->stream, m->D, slot, monocular != 0, ++m->epoch,
+                                          d_records, rec_cap, d_nrec, &c->prof)))
+        return set_err(rc, "KeyFrameCulling launch failed");
+    m->dirty = m->tree_dirty = m->touched = true;
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_keyframe_culling(orbg_ctx *c, orbg_map *m, int slot, int monocular,
+                                         orbg_cull_record *records, int rec_cap, int32_t *nrec)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (rec_cap < 0 || !nrec || (rec_cap && !records))
+        return set_err(ORBG_EINVAL, "bad rec_cap / NULL array");
+    Layout L;
+    const size_t o_r = L.take((size_t)rec_cap * sizeof(orbg_cull_record)), o_n = L.take(4);
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
+    if ((rc = orbg_map_keyframe_culling_device(c, m, slot, monocular, L.at<orbg_cull_record>(b, o_r),
+                                               rec_cap, L.at<int32_t>(b, o_n))))
+        return rc;
+    int32_t n = 0;
+    HIPCHK(hipMemcpyAsync(&n, b + o_n, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const int nw = std::min(n, rec_cap);
+    if (nw > 0) HIPCHK(hipMemcpy(records, b + o_r, (size_t)nw * sizeof(orbg_cull_record), hipMemcpyDeviceToHost));
+    c->prof.collect();
+    *nrec = n;
+    if (n > rec_cap) return set_err(ORBG_ERANGE, "%d list entries (rec_cap %d)", n, rec_cap);
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_point_culling_device(orbg_ctx *c, orbg_map *m, int32_t *d_recent, int n,
+                                             int current_kf_id, int monocular, int32_t *d_nout,
+                                             int32_t *d_status)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (n < 0) return set_err(ORBG_EINVAL, "negative size");
+    if (!d_nout || (n && !d_recent)) return set_err(ORBG_EINVAL, "NULL device array");
+    if ((rc = orbg_map_rebuild(c, m))) return rc;
+    if ((rc = launch_map_point_culling(c->stream, m->D, d_recent, n, current_kf_id, monocular != 0,
+                                       d_nout, d_status, &c->prof)))
+        return set_err(rc, "MapPointCulling launch failed");
+    m->dirty = m->touched = true;
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_point_culling(orbg_ctx *c, orbg_map *m, int32_t *recent, int n,
+                                      int current_kf_id, int monocular, int32_t *nout,
+                                      int32_t *status)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (n < 0 || !nout || (n && !recent)) return set_err(ORBG_EINVAL, "negative size / NULL array");
+    for (int i = 0; i < n; i++)
+        if (recent[i] < 0 || recent[i] >= m->D.P)
+            return set_err(ORBG_EINVAL, "point id %d outside [0, %d)", recent[i], m->D.P);
+    const size_t nb = (size_t)std::max(n, 1) * 4;
+    Layout L;
+    const size_t o_r = L.take(nb), o_s = L.take(nb), o_n = L.take(4);
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
+    if (n) HIPCHK(hipMemcpyAsync(b + o_r, recent, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    if ((rc = orbg_map_point_culling_device(c, m, L.at<int32_t>(b, o_r), n, current_kf_id, monocular,
+                                            L.at<int32_t>(b, o_n), L.at<int32_t>(b, o_s))))
+        return rc;
+    int32_t k = 0;
+    HIPCHK(hipMemcpyAsync(&k, b + o_n, 4, hipMemcpyDeviceToHost, c->stream));
+    if (n && status) HIPCHK(hipMemcpyAsync(status, b + o_s, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (k > 0) HIPCHK(hipMemcpy(recent, b + o_r, (size_t)k * 4, hipMemcpyDeviceToHost));
+    c->prof.collect();
+    *nout = k;
     return ORBG_OK;
 }

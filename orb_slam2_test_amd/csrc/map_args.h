@@ -17,6 +17,8 @@ namespace orbg {
 #define ORBG_MAP_TH 15                // UpdateConnections' th
 #define ORBG_MAP_MAX_LOCAL 80         // UpdateLocalKeyFrames' size limit
 #define MAP_KF_LIVE 4                 // kf_flags: beside ORBG_MAP_KF_ROOT (1) and ORBG_MAP_KF_BAD (2)
+#define MAP_NOT_ERASE 1               // kf_erase: mbNotErase
+#define MAP_TO_BE_ERASED 2            //           mbToBeErased
 
 // An orbg_map's device state.  Slot s (the caller's KeyFrame handle, as orbg_kfdb's) owns row s
 // of kf_points / kf_oct and of W / ord_*; point p owns mp[p], mdesc[p], mp_ref[p].  The
@@ -24,7 +26,9 @@ namespace orbg {
 // observations as slot << 16 | feature index, ascending slot, rebuilt from the live rows when
 // stale.  child_head / child_next are the spanning tree's children lists (ascending slot),
 // rebuilt from `parent` when stale.  dirty / mark hold the number of the call that last set
-// them (UpdateConnections' second kernel re-sorts the rows this call marked dirty).
+// them (UpdateConnections' second kernel re-sorts the rows this call marked dirty).  row_touch
+// holds the number of the culling call in which an erasure last changed Observations() of one
+// of the row's points or removed one from it.
 struct MapDev {
     int32_t K, cap, P;
     int32_t *kf_flags;          // [K] MAP_KF_LIVE | ORBG_MAP_KF_*
@@ -51,6 +55,15 @@ struct MapDev {
     int32_t *child_next;        // [K]
     int32_t *dirty, *mark;      // [K]
     int32_t *nlive;             // [1]
+    uint8_t *kf_feat;           // [K][cap] ORBG_MAP_FEAT_*
+    int32_t *kf_erase;          // [K] MAP_NOT_ERASE | MAP_TO_BE_ERASED
+    int32_t *mp_first;          // [P] mnFirstKFid
+    int32_t *mp_visible;        // [P] mnVisible
+    int32_t *mp_found;          // [P] mnFound
+    int32_t *row_touch;         // [K]
+    int32_t *cull_list;         // [K] KeyFrameCulling's copy of the ordered list
+    int32_t *cull_score;        // [K][2] nMPs, nRedundant of the list entries at the call's start
+    int32_t *cull_out;          // [4] a status for the host forms
 };
 
 struct MapScales {
@@ -66,6 +79,7 @@ int launch_map_set_points(hipStream_t st, const MapDev &M, const int32_t *ids, i
                           const orbg_map_point *mps, const uint8_t *desc, const int32_t *ref);
 int launch_map_point_bad(hipStream_t st, const MapDev &M, int id);
 int launch_map_set_parent(hipStream_t st, const MapDev &M, int slot, int parent);
+int launch_map_resort(hipStream_t st, const MapDev &M, int epoch);
 int launch_map_erase(hipStream_t st, const MapDev &M, int slot, int epoch);
 int launch_map_count(hipStream_t st, const MapDev &M);
 int launch_map_rebuild(hipStream_t st, const MapDev &M, Prof *prof);
@@ -85,5 +99,26 @@ int launch_map_local_points(hipStream_t st, const MapDev &M, const int32_t *loca
                             Prof *prof);
 int launch_map_normal_depth(hipStream_t st, const MapDev &M, const int32_t *ids, int n,
                             const MapScales &S, Prof *prof);
+
+// map_cull_kernels.hip
+int launch_map_point_defaults(hipStream_t st, const MapDev &M);
+int launch_map_set_features(hipStream_t st, const MapDev &M, const int32_t *slots, int n,
+                            const uint8_t *flags, int row_cap, const int32_t *counts);
+int launch_map_set_point_stats(hipStream_t st, const MapDev &M, const int32_t *ids, int first, int n,
+                               const int32_t *first_kf, const int32_t *visible,
+                               const int32_t *found);
+int launch_map_point_nobs(hipStream_t st, const MapDev &M, int first, int n, int32_t *nobs);
+int launch_map_increase(hipStream_t st, int32_t *counter, int P, const int32_t *ids,
+                        const orbg_map_projection *proj, int n, int amount);
+// on: 1 SetNotErase, 0 SetErase, -1 SetBadFlag; status (device): SetBadFlag's, or 1 when
+// SetErase erased
+int launch_map_set_bad(hipStream_t st, const MapDev &M, int slot, int on, int epoch,
+                       int32_t *status, Prof *prof);
+int launch_map_keyframe_culling(hipStream_t st, const MapDev &M, int slot, int monocular,
+                                int epoch, orbg_cull_record *rec, int rec_cap, int32_t *nrec,
+                                Prof *prof);
+int launch_map_point_culling(hipStream_t st, const MapDev &M, int32_t *recent, int n,
+                             int current_kf_id, int monocular, int32_t *nout, int32_t *status,
+                             Prof *prof);
 
 }  // namespace orbg

@@ -29,117 +29,20 @@
 //                    records and descriptors.
 //   k_map_normal_depth  one thread per point, its observations in ascending slot order.
 // No result depends on thread order: the atomics are integer counters.
+// The workgroup scan, the LDS sort and the ordered-list store are in map_device.h, shared with
+// map_cull_kernels.hip (SetBadFlag, KeyFrameCulling, MapPointCulling over the same table).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
 #include "../../include/orbg.h"
 #include "map_args.h"
+#include "map_device.h"
 #include "orbg_launch.h"
 
 #pragma clang fp contract(off)
 
 namespace orbg {
-
-#define MAP_T 256
-#define MAP_SLOT_MASK 0x1FFFu
-#define MAP_BADBIT 0x40000000u
-#define MAP_MARKBIT 0x80000000u
-#define MAP_VOTES 0x3FFFFFFFu
-#define MAP_PRE 12            // staged per initial local keyframe: 10 neighbours, first child, parent
-#define MAP_SCAN_TILE 2048
-
-extern __shared__ __attribute__((aligned(16))) char map_smem[];
-
-// LDS of the workgroup kernels: a [K] u32, b [bn] u32, pre [81 * 12] i32, scr [16] i32
-static __host__ __device__ inline size_t map_off_b(int K) { return ((size_t)K * 4 + 15) & ~(size_t)15; }
-static __host__ __device__ inline size_t map_off_pre(int K, int bn) { return map_off_b(K) + (size_t)bn * 4; }
-static __host__ __device__ inline size_t map_off_scr(int K, int bn)
-{
-    return map_off_pre(K, bn) + (size_t)(ORBG_MAP_MAX_LOCAL + 1) * MAP_PRE * 4;
-}
-static size_t map_lds(int K, int bn) { return map_off_scr(K, bn) + 16 * 4; }
-static int map_pow2(int n)
-{
-    int p = 1;
-    while (p < n) p <<= 1;
-    return p;
-}
-
-// exclusive prefix of one value per thread over the workgroup (all threads call it); scr: 4 ints
-__device__ __forceinline__ int block_scan(int v, int *scr, int *total)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int incl = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += o;
-    }
-    __syncthreads();
-    if (lane == 63) scr[w] = incl;
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int i = 0; i < MAP_T / 64; i++) {
-        const int s = scr[i];
-        if (i < w) base += s;
-        tot += s;
-    }
-    *total = tot;
-    return base + incl - v;
-}
-
-// bitonic sort, descending, of a[0 .. n2) in LDS (n2 a power of two)
-__device__ __forceinline__ void lds_sort_desc(uint32_t *a, int n2)
-{
-    for (int k = 2; k <= n2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            __syncthreads();
-            for (int i = threadIdx.x; i < n2; i += MAP_T) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const uint32_t x = a[i], y = a[l];
-                    if ((i & k) == 0 ? x < y : x > y) {
-                        a[i] = y;
-                        a[l] = x;
-                    }
-                }
-            }
-        }
-    __syncthreads();
-}
-
-// The ordered list of slot s from keys[t] (weight << 13 | t, 0 = not in the list) in LDS:
-// compacted in slot order into srt, sorted descending, stored with nord and neigh.
-__device__ void map_store_order(const MapDev &M, int s, const uint32_t *keys, uint32_t *srt,
-                                int *scr)
-{
-    const int C = (M.K + MAP_T - 1) / MAP_T;
-    const int t0 = min((int)threadIdx.x * C, M.K), t1 = min(t0 + C, M.K);
-    int c = 0;
-    for (int t = t0; t < t1; t++) c += keys[t] != 0;
-    int total;
-    int pos = block_scan(c, scr, &total);
-    for (int t = t0; t < t1; t++)
-        if (keys[t]) srt[pos++] = keys[t];
-    int n2 = 1;
-    while (n2 < total) n2 <<= 1;
-    for (int i = total + threadIdx.x; i < n2; i += MAP_T) srt[i] = 0;
-    lds_sort_desc(srt, n2);
-    uint16_t *os = M.ord_slot + (size_t)s * M.K, *ow = M.ord_w + (size_t)s * M.K;
-    for (int i = threadIdx.x; i < total; i += MAP_T) {
-        os[i] = (uint16_t)(srt[i] & MAP_SLOT_MASK);
-        ow[i] = (uint16_t)(srt[i] >> 13);
-    }
-    if (threadIdx.x < ORBG_MAP_NEIGH)
-        M.neigh[s * ORBG_MAP_NEIGH + threadIdx.x] =
-            (int)threadIdx.x < total ? (int32_t)(srt[threadIdx.x] & MAP_SLOT_MASK) : -1;
-    if (threadIdx.x == 0) M.nord[s] = total;
-}
-
-__device__ __forceinline__ bool map_point_ok(const MapDev &M, int p)
-{
-    return p >= 0 && p < M.P && (M.mp[p].flags & ORBG_MP_VALID);
-}
 
 // ---------------------------------------------------------------------------
 // mutations
@@ -161,14 +64,18 @@ __global__ __launch_bounds__(MAP_T) void k_map_set_kf(MapDev M, const int32_t *s
         dp[k] = p < 0 ? -1 : p;
         dq[k] = k < n ? oct[(size_t)i * row_cap + k] : 0;
     }
+    const int was = M.kf_flags[s];
+    if (!(was & MAP_KF_LIVE))  // a new KeyFrame's keypoints: no feature flags yet
+        for (int k = threadIdx.x; k < M.cap; k += MAP_T) M.kf_feat[(size_t)s * M.cap + k] = 0;
+    __syncthreads();  // every thread has read kf_flags[s]
     if (threadIdx.x == 0) {
-        const int was = M.kf_flags[s];
         M.kf_flags[s] = MAP_KF_LIVE | (flags[i] & (ORBG_MAP_KF_ROOT | ORBG_MAP_KF_BAD));
         M.kf_n[s] = n;
         for (int k = 0; k < 3; k++) M.kf_centre[s * 3 + k] = centres[i * 3 + k];
         if (!(was & MAP_KF_LIVE)) {  // a new KeyFrame: no parent yet, mbFirstConnection
             M.parent[s] = -1;
             M.first_conn[s] = 1;
+            M.kf_erase[s] = 0;
         }
     }
 }
@@ -724,15 +631,6 @@ __global__ __launch_bounds__(MAP_T) void k_map_normal_depth(MapDev M, const int3
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
-static int last_rc() { return hipGetLastError() == hipSuccess ? ORBG_OK : ORBG_EIO; }
-
-static int map_attr(const void *fn, size_t lds)
-{
-    return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess
-               ? ORBG_OK
-               : ORBG_EIO;
-}
-
 int launch_map_set_keyframes(hipStream_t st, const MapDev &M, const int32_t *slots, int n,
                              const int32_t *points, const uint8_t *oct, int row_cap,
                              const int32_t *counts, const float *centres, const int32_t *flags)
@@ -764,7 +662,7 @@ int launch_map_set_parent(hipStream_t st, const MapDev &M, int slot, int parent)
     return last_rc();
 }
 
-static int launch_map_resort(hipStream_t st, const MapDev &M, int epoch)
+int launch_map_resort(hipStream_t st, const MapDev &M, int epoch)
 {
     const int bn = map_pow2(M.K);
     const size_t lds = map_lds(M.K, bn);

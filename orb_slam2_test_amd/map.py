@@ -1,8 +1,9 @@
 """Map -- ORB-SLAM2's covisibility graph and local map over one device-resident table, "which
 keyframe slot observes which map point" (liborbg's orbg_map_* entry points):
 KeyFrame::UpdateConnections (src/KeyFrame.cc:375-515), Tracking::UpdateLocalKeyFrames /
-UpdateLocalPoints (src/Tracking.cc:1731-1925) and MapPoint::UpdateNormalAndDepth
-(src/MapPoint.cc:457-518).
+UpdateLocalPoints (src/Tracking.cc:1731-1925), MapPoint::UpdateNormalAndDepth
+(src/MapPoint.cc:457-518), KeyFrame::SetBadFlag (src/KeyFrame.cc:622-720) and
+LocalMapping::KeyFrameCulling / MapPointCulling (src/LocalMapping.cc:227-270, 804-877).
 
 A KeyFrame is a slot in [0, max_keyframes), as in KeyFrameDatabase; a MapPoint is an id in
 [0, max_points).  Wherever the reference orders by KeyFrame pointer, the order here is the
@@ -15,6 +16,9 @@ ascending slot (include/orbg.h).
     kfs, ref = m.UpdateLocalKeyFrames(frame_points)           # frame_points nulled in place
     ids, mps, desc = m.UpdateLocalPoints(kfs, frame_points)
     db.DetectRelocalizationCandidates(bow, m.neighbours())    # the device table, unchanged
+    recent, status = m.MapPointCulling(recent, current_kf_id, monocular)
+    for r in m.KeyFrameCulling(slot, monocular):              # CULL_RECORD_DTYPE records
+        if r["status"] == 1: db.erase(r["slot"])
 """
 import ctypes as C
 
@@ -25,6 +29,7 @@ from .orbmatcher import _ctx
 
 NEIGHBOURS = 10
 KF_ROOT, KF_BAD = 1, 2
+FEAT_STEREO, FEAT_CLOSE = L.MAP_FEAT_STEREO, L.MAP_FEAT_CLOSE
 
 
 def _i32(a):
@@ -265,3 +270,132 @@ class Map:
             torch.cuda.synchronize()
             self.update_normal_and_depth_batch_device(ids.data_ptr(), ids.numel())
         ctx.sync()
+
+    # ---- KeyFrame::SetBadFlag, LocalMapping::KeyFrameCulling / MapPointCulling ----
+    def SetKeyFrameFeatures(self, slot, flags):
+        """per feature: FEAT_STEREO (mvuRight[i] >= 0) | FEAT_CLOSE (depth within mThDepth)"""
+        f = np.ascontiguousarray(flags, np.uint8).reshape(-1)
+        L.check(L.lib().orbg_map_set_keyframe_features(self._c(), self._h, int(slot), L.ptr(f),
+                                                       len(f)), "orbg_map_set_keyframe_features")
+
+    def set_keyframe_features_device(self, d_slots, n, d_flags, row_cap, d_counts, ctx=None):
+        L.check(L.lib().orbg_map_set_keyframe_features_device(self._c(ctx), self._h, d_slots,
+                                                              int(n), d_flags, int(row_cap),
+                                                              d_counts),
+                "orbg_map_set_keyframe_features_device")
+
+    def _not_erase(self, slot, on):
+        erased = C.c_int32()
+        L.check(L.lib().orbg_map_set_not_erase(self._c(), self._h, int(slot), on,
+                                               C.byref(erased)), "orbg_map_set_not_erase")
+        return bool(erased.value)
+
+    def SetNotErase(self, slot):
+        self._not_erase(slot, 1)
+
+    def SetErase(self, slot):
+        """once mspLoopEdges is empty; True if the pending SetBadFlag ran"""
+        return self._not_erase(slot, 0)
+
+    def SetBadFlag(self, slot):
+        """KeyFrame::SetBadFlag in full; 0 nothing (root / dead), 1 erased, 2 marked"""
+        st = C.c_int32()
+        L.check(L.lib().orbg_map_set_bad_flag(self._c(), self._h, int(slot), C.byref(st)),
+                "orbg_map_set_bad_flag")
+        return st.value
+
+    def KeyFrameCulling(self, slot, monocular):
+        """CULL_RECORD_DTYPE records, one per entry of slot's ordered list"""
+        rec = np.zeros(self.max_keyframes, L.CULL_RECORD_DTYPE)
+        n = C.c_int32()
+        L.check(L.lib().orbg_map_keyframe_culling(self._c(), self._h, int(slot), int(bool(monocular)),
+                                                  L.ptr(rec), len(rec), C.byref(n)),
+                "orbg_map_keyframe_culling")
+        return rec[:n.value]
+
+    def keyframe_culling_device(self, slot, monocular, d_records, rec_cap, d_nrec, ctx=None):
+        L.check(L.lib().orbg_map_keyframe_culling_device(self._c(ctx), self._h, int(slot),
+                                                         int(bool(monocular)), d_records,
+                                                         int(rec_cap), d_nrec),
+                "orbg_map_keyframe_culling_device")
+
+    def MapPointCulling(self, recent, current_kf_id, monocular):
+        """(mlpRecentAddedMapPoints after the call, status per input position)"""
+        r = _i32(recent).copy()
+        st = np.zeros(len(r), np.int32)
+        n = C.c_int32()
+        L.check(L.lib().orbg_map_point_culling(self._c(), self._h, L.ptr(r), len(r),
+                                               int(current_kf_id), int(bool(monocular)),
+                                               C.byref(n), L.ptr(st)), "orbg_map_point_culling")
+        return r[:n.value], st
+
+    def point_culling_device(self, d_recent, n, current_kf_id, monocular, d_nout, d_status,
+                             ctx=None):
+        L.check(L.lib().orbg_map_point_culling_device(self._c(ctx), self._h, d_recent, int(n),
+                                                      int(current_kf_id), int(bool(monocular)),
+                                                      d_nout, d_status),
+                "orbg_map_point_culling_device")
+
+    def SetPointStats(self, first, first_kf_id=None, visible=None, found=None):
+        a = [None if x is None else _i32(x) for x in (first_kf_id, visible, found)]
+        n = {len(x) for x in a if x is not None}
+        if len(n) != 1:
+            raise ValueError("the given arrays differ in length (or none is given)")
+        L.check(L.lib().orbg_map_set_point_stats(self._c(), self._h, int(first), n.pop(),
+                                                 *[None if x is None else L.ptr(x) for x in a]),
+                "orbg_map_set_point_stats")
+
+    def set_point_stats_device(self, d_ids, first, n, d_first_kf_id, d_visible, d_found, ctx=None):
+        L.check(L.lib().orbg_map_set_point_stats_device(self._c(ctx), self._h, d_ids, int(first),
+                                                        int(n), d_first_kf_id, d_visible, d_found),
+                "orbg_map_set_point_stats_device")
+
+    def point_stats(self, first=0, n=None):
+        """(mnFirstKFid, mnVisible, mnFound, Observations()) as int32 arrays"""
+        n = self.max_points - first if n is None else int(n)
+        out = [np.zeros(n, np.int32) for _ in range(4)]
+        L.check(L.lib().orbg_map_get_point_stats(self._c(), self._h, int(first), n,
+                                                 *[L.ptr(x) for x in out]),
+                "orbg_map_get_point_stats")
+        return tuple(out)
+
+    def increase_visible_device(self, d_ids, d_proj, n, amount=1, ctx=None):
+        L.check(L.lib().orbg_map_increase_visible_device(self._c(ctx), self._h, d_ids, d_proj,
+                                                         int(n), int(amount)),
+                "orbg_map_increase_visible_device")
+
+    def increase_found_device(self, d_ids, n, amount=1, ctx=None):
+        L.check(L.lib().orbg_map_increase_found_device(self._c(ctx), self._h, d_ids, int(n),
+                                                       int(amount)),
+                "orbg_map_increase_found_device")
+
+    def _increase(self, fn, point_ids, amount):
+        import torch
+        ids = torch.from_numpy(_i32(point_ids)).to("cuda:%d" % self.device)
+        torch.cuda.synchronize()
+        fn(ids.data_ptr(), ids.numel(), amount)
+        _ctx(self.device).sync()
+
+    def IncreaseVisible(self, point_ids, amount=1):
+        self._increase(lambda p, n, a: self.increase_visible_device(p, None, n, a), point_ids,
+                       amount)
+
+    def IncreaseFound(self, point_ids, amount=1):
+        self._increase(self.increase_found_device, point_ids, amount)
+
+    def keyframe_points(self, slot):
+        """mvpMapPoints of a slot as ids (-1 = NULL); empty for a dead slot"""
+        out = np.full(self.kf_cap, -1, np.int32)
+        n = C.c_int32()
+        L.check(L.lib().orbg_map_get_keyframe_points(self._c(), self._h, int(slot), L.ptr(out),
+                                                     len(out), C.byref(n)),
+                "orbg_map_get_keyframe_points")
+        return out[:n.value]
+
+    def point_refs(self, first=0, n=None):
+        """mpRefKF as slots (-1: none)"""
+        n = self.max_points - first if n is None else int(n)
+        out = np.zeros(n, np.int32)
+        L.check(L.lib().orbg_map_get_point_refs(self._c(), self._h, int(first), n, L.ptr(out)),
+                "orbg_map_get_point_refs")
+        return out
