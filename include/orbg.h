@@ -1513,6 +1513,105 @@ int orbg_map_point_culling_device(orbg_ctx *ctx, orbg_map *map, int32_t *d_recen
 int orbg_map_point_culling(orbg_ctx *ctx, orbg_map *map, int32_t *recent, int n,
                            int current_kf_id, int monocular, int32_t *nout, int32_t *status);
 
+/* ---- MapPoint::AddObservation / Replace, ORBmatcher::Fuse(pKF, vpMapPoints, th) and
+ * LocalMapping::SearchInNeighbors on the Map ----
+ * (src/MapPoint.cc:121-142, 253-303, 342-425, src/ORBmatcher.cc:968-1125, src/LocalMapping.cc:
+ * 583-683).  Further state, defaulting so that the calls above give what they gave: per point
+ * mpReplaced as an id (-1 = none after orbg_map_create / clear), and the keyframe data that
+ * the search and ComputeDistinctiveDescriptors read, attached and not owned.  All calls run on
+ * the context stream; the device forms do not synchronise, the host forms do.  After a call
+ * that edited rows the observation index is stale and the next query rebuilds it.
+ *
+ * Replace, as the table sees it: for each observation (KF, idx) of the old point, if the new
+ * point is not in KF the row entry becomes the new point (the feature index, and with it the
+ * STEREO weight in Observations(), stays), else the entry becomes none; the old point goes bad,
+ * mpReplaced[old] = new, the new point gains the old point's mnFound and mnVisible; mpRefKF of
+ * both, W, the ordered lists and the parents do not change (only UpdateConnections changes
+ * them).  The survivor's ComputeDistinctiveDescriptors runs once per call, after the last pair
+ * (after the sequential pass of a Fuse call): its observation set then is the one it has after
+ * the last Replace into it, and a survivor that was itself replaced later in the call is bad
+ * and keeps the descriptor it had (the reference recomputes it in between; nothing reads it). */
+/* mpReplaced of points first .. first + n - 1 as ids (-1: none) */
+int orbg_map_get_point_replaced(orbg_ctx *ctx, orbg_map *map, int first, int n, int32_t *replaced);
+/* mDescriptor of points first .. first + n - 1 ([n][32], host) */
+int orbg_map_get_point_descriptors(orbg_ctx *ctx, orbg_map *map, int first, int n, uint8_t *desc);
+/* Attaches the keyframes' data: *kfs is copied, its device arrays (rows of `cap`) and d_cams
+ * are indexed by slot and must stay valid while attached; desc, kps, uright (may be NULL) and
+ * counts are read, has_mp and fv_* are not.  d_cams[slot] = the keyframe's pose, intrinsics
+ * and bounds as orbg_fuse reads them.  kfs == NULL detaches.  The calls below return
+ * ORBG_EINVAL while nothing is attached (orbg_map_add_observations* needs nothing attached). */
+int orbg_map_attach_keyframes(orbg_ctx *ctx, orbg_map *map, const orbg_keyframes *kfs, int cap,
+                              const orbg_frustum_camera *d_cams);
+/* pMP->AddObservation(pKF, idx) + pKF->AddMapPoint(pMP, idx) for entries i < n in order:
+ * CreateNewMapPoints' insertion (after orbg_map_set_points_device wrote the new records) and
+ * Fuse's else-branch.  d_status[i] (may be NULL): 0 added; skipped: 1 the slot is dead or out
+ * of range, 2 idx outside the slot's N, 3 the id is out of range, 4 the point is bad, 5 the
+ * slot already observes the point (mObservations.count(pKF)), 6 the feature holds another
+ * point. */
+int orbg_map_add_observations_device(orbg_ctx *ctx, orbg_map *map, const int32_t *d_slots,
+                                     const int32_t *d_idx, const int32_t *d_point_ids, int n,
+                                     int32_t *d_status);
+int orbg_map_add_observations(orbg_ctx *ctx, orbg_map *map, const int32_t *slots,
+                              const int32_t *idx, const int32_t *point_ids, int n,
+                              int32_t *status);
+/* MapPoint::ComputeDistinctiveDescriptors of the points d_point_ids[i], i < n, into the map's
+ * mDescriptor: the descriptors of the point's observations in ascending slot order, slots
+ * flagged ORBG_MAP_KF_BAD (or features past the attached counts) left out, through
+ * orbg_distinctive_descriptors_batch_device's kernel.  A bad point, an id out of range or a
+ * point with no usable observation keeps its descriptor. */
+int orbg_map_distinctive_descriptors_device(orbg_ctx *ctx, orbg_map *map,
+                                            const int32_t *d_point_ids, int n);
+/* d_old[i]->Replace(d_new[i]) for i < n in order (above), then ComputeDistinctiveDescriptors
+ * of the survivors.  d_status[i] (may be NULL): 0 replaced; 1 old == new, nothing; 2 new is bad
+ * or out of range, skipped (a precondition of every caller); 3 old is out of range, skipped;
+ * 4 old was already bad: it has no observations, so only mpReplaced and the found / visible
+ * transfer happen.  Also what LoopClosing::SearchAndFuse applies to vpReplacePoint after
+ * orbg_fuse_sim3_batch_device. */
+int orbg_map_replace_device(orbg_ctx *ctx, orbg_map *map, const int32_t *d_old,
+                            const int32_t *d_new, int n, int32_t *d_status);
+int orbg_map_replace(orbg_ctx *ctx, orbg_map *map, const int32_t *olds, const int32_t *news, int n,
+                     int32_t *status);
+/* ORBmatcher::Fuse(pKF = slot, vpMapPoints = d_point_ids, th) in full.  The search inputs are
+ * gathered from the map: the record and mDescriptor of each id, ORBG_MP_VALID = in range, good
+ * and not in the slot's row when the call starts (-1 is NULL); orbg_fuse_batch_device's kernel
+ * runs with the attached keyframe and d_cams[slot]; then the update of :1100-1125 in
+ * vpMapPoints order by one workgroup.  d_status[i]: 0 no target (bestDist > TH_LOW = 50, or a
+ * feature index outside the slot's N); 1 AddObservation; 2 the point was replaced by the
+ * feature's point (pMPinKF->Observations() > pMP->Observations(), strict, as they stand at
+ * that moment); 3 the feature's point was replaced by the point; 4 the feature held a bad
+ * point (counted, nothing done); 5 it had a target but was bad or in the keyframe by its turn
+ * (not counted).  d_nfused[0] = the return value = the number of statuses 1 to 4.  d_best_idx /
+ * d_best_dist / d_status [n] may be NULL.  A dead slot: every status 0. */
+int orbg_map_fuse_device(orbg_ctx *ctx, orbg_map *map, int slot, const int32_t *d_point_ids, int n,
+                         float th, int32_t *d_best_idx, int32_t *d_best_dist, int32_t *d_status,
+                         int32_t *d_nfused);
+int orbg_map_fuse(orbg_ctx *ctx, orbg_map *map, int slot, const int32_t *point_ids, int n,
+                  float th, int32_t *best_idx, int32_t *best_dist, int32_t *status,
+                  int32_t *nfused);
+/* LocalMapping::SearchInNeighbors with mpCurrentKeyFrame = slot, mnId = current_kf_id (only
+ * whether it is 0 matters: mnFuseTargetForKF starts at 0, so with id 0 every keyframe counts as
+ * marked and both lists are empty).  vpTargetKFs from the stored ordered lists: the first nn =
+ * monocular ? 20 : 10 entries of the slot's list, each skipped if bad or marked, else pushed
+ * and marked, followed by the first 5 of its own list, each skipped if bad, marked or the slot
+ * itself and NOT marked when pushed, so an entry can occur again.  Fuse(target, the slot's row
+ * as it stood at the start, th) once per list entry, each with its survivors' descriptors
+ * before the next search reads them; vpFuseCandidates = the good points of the entries' rows
+ * as they stand then, in list and feature order, each at its first occurrence;
+ * Fuse(slot, candidates, th); ComputeDistinctiveDescriptors and UpdateNormalAndDepth of the
+ * good points of the slot's row, re-read; UpdateConnections(slot).  d_targets: the first
+ * target_cap entries, d_ntargets[0] the full length (at most 120); d_nfused [121]:
+ * d_nfused[t] = the return value of entry t's Fuse, d_nfused[ntargets] the second pass's, the
+ * rest 0.  The device form never synchronises: the launches are sized by the bounds (6 nn
+ * entries, 120 * kf_cap candidates) and the lengths stay on the device.  The workspace
+ * belongs to the map and is allocated by the first call. */
+int orbg_map_search_in_neighbors_device(orbg_ctx *ctx, orbg_map *map, int slot, int current_kf_id,
+                                        int monocular, float th, int32_t *d_targets,
+                                        int target_cap, int32_t *d_ntargets, int32_t *d_nfused);
+/* host arrays (nfused [121]); ORBG_ERANGE when the list is longer than target_cap */
+int orbg_map_search_in_neighbors(orbg_ctx *ctx, orbg_map *map, int slot, int current_kf_id,
+                                 int monocular, float th, int32_t *targets, int target_cap,
+                                 int32_t *ntargets, int32_t *nfused);
+
 /* ---------------- ORBmatcher::SearchByBoW(KeyFrame*, Frame&) ---------------- */
 /* One side of SearchByBoW pairs, device memory, in orbg_bow_transform_batch_device's layout
  * (frame f's rows at + f * cap, fv_off at + f * (cap + 1)): descriptors [cap][32], keypoints

@@ -481,6 +481,19 @@ def lib():
         "orbg_map_keyframe_culling": (i32, [vp, vp, i32, i32, vp, i32, P(C.c_int32)]),
         "orbg_map_point_culling_device": (i32, [vp, vp, vp, i32, i32, i32, vp, vp]),
         "orbg_map_point_culling": (i32, [vp, vp, vp, i32, i32, i32, P(C.c_int32), vp]),
+        "orbg_map_get_point_replaced": (i32, [vp, vp, i32, i32, vp]),
+        "orbg_map_get_point_descriptors": (i32, [vp, vp, i32, i32, vp]),
+        "orbg_map_attach_keyframes": (i32, [vp, vp, P(KeyFrames), i32, vp]),
+        "orbg_map_add_observations_device": (i32, [vp, vp, vp, vp, vp, i32, vp]),
+        "orbg_map_add_observations": (i32, [vp, vp, vp, vp, vp, i32, vp]),
+        "orbg_map_distinctive_descriptors_device": (i32, [vp, vp, vp, i32]),
+        "orbg_map_replace_device": (i32, [vp, vp, vp, vp, i32, vp]),
+        "orbg_map_replace": (i32, [vp, vp, vp, vp, i32, vp]),
+        "orbg_map_fuse_device": (i32, [vp, vp, i32, vp, i32, f32, vp, vp, vp, vp]),
+        "orbg_map_fuse": (i32, [vp, vp, i32, vp, i32, f32, vp, vp, vp, P(C.c_int32)]),
+        "orbg_map_search_in_neighbors_device": (i32, [vp, vp, i32, i32, i32, f32, vp, i32, vp, vp]),
+        "orbg_map_search_in_neighbors": (i32, [vp, vp, i32, i32, i32, f32, vp, i32, P(C.c_int32),
+                                               vp]),
         "orbg_sim3_ransac_iterations": (i32, [C.c_double, i32, i32, i32]),
         "orbg_sim3_solve": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
         "orbg_sim3_solve_batch_device": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp,

@@ -21,6 +21,10 @@ struct orbg_map {
     int32_t *d_cnt = nullptr;    // local_points' per-keyframe counts [nframes][lkf_cap]
     size_t cnt_n = 0;
     hipStream_t stream = nullptr;  // the context stream of the last call
+    MapAttach att{};             // orbg_map_attach_keyframes: not owned
+    bool attached = false;
+    MapEditWs W{};               // Fuse / SearchInNeighbors workspace, allocated at the first call
+    void *d_ws = nullptr;
 };
 
 static int map_reset(orbg_map *m, hipStream_t st)
@@ -33,6 +37,7 @@ static int map_reset(orbg_map *m, hipStream_t st)
     HIPCHK(hipMemsetAsync(D.neigh, 0xFF, (size_t)D.K * ORBG_MAP_NEIGH * 4, st));
     HIPCHK(hipMemsetAsync(D.child_head, 0xFF, (size_t)D.K * 4, st));
     HIPCHK(hipMemsetAsync(D.child_next, 0xFF, (size_t)D.K * 4, st));
+    HIPCHK(hipMemsetAsync(D.mp_replaced, 0xFF, (size_t)D.P * 4, st));
     if (launch_map_point_defaults(st, D)) return set_err(ORBG_EIO, "k_map_point_defaults launch failed");
     m->dirty = m->tree_dirty = true;
     return ORBG_OK;
@@ -68,6 +73,9 @@ extern "C" int orbg_map_create(orbg_ctx *c, int max_keyframes, int kf_cap, int m
     const size_t o_kf = L.take(kc), o_ke = L.take(K * 4);
     const size_t o_pf = L.take(P * 4), o_pv = L.take(P * 4), o_pn = L.take(P * 4);
     const size_t o_rt = L.take(K * 4), o_cl = L.take(K * 4), o_cs = L.take(K * 8), o_co = L.take(16);
+    const size_t o_rp = L.take(P * 4), o_en = L.take(P * 4), o_et = L.take(P * 4);
+    const size_t o_ec = L.take(P * 4), o_ei = L.take(P * 4), o_em = L.take(P * 4);
+    const size_t o_ef = L.take(P * 4);
     auto *m = new orbg_map();
     m->device = c->device;
     if (hipMalloc(&m->d_mem, L.total()) != hipSuccess) {
@@ -115,6 +123,13 @@ extern "C" int orbg_map_create(orbg_ctx *c, int max_keyframes, int kf_cap, int m
     D.cull_list = L.at<int32_t>(b, o_cl);
     D.cull_score = L.at<int32_t>(b, o_cs);
     D.cull_out = L.at<int32_t>(b, o_co);
+    D.mp_replaced = L.at<int32_t>(b, o_rp);
+    D.ed_next = L.at<int32_t>(b, o_en);
+    D.ed_tail = L.at<int32_t>(b, o_et);
+    D.ed_chain = L.at<int32_t>(b, o_ec);
+    D.ed_inkf = L.at<int32_t>(b, o_ei);
+    D.ed_mark = L.at<int32_t>(b, o_em);
+    D.ed_first = L.at<int32_t>(b, o_ef);
     int rc = map_reset(m, c->stream);
     if (!rc && hipStreamSynchronize(c->stream) != hipSuccess)
         rc = set_err(ORBG_EIO, "Map: the initial clear failed");
@@ -133,6 +148,7 @@ extern "C" void orbg_map_destroy(orbg_map *m)
     if (!m) return;
     hipSetDevice(m->device);
     if (m->d_cnt) hipFree(m->d_cnt);
+    if (m->d_ws) hipFree(m->d_ws);
     if (m->d_mem) hipFree(m->d_mem);
     delete m;
 }
@@ -895,5 +911,352 @@ extern "C" int orbg_map_point_culling(orbg_ctx *c, orbg_map *m, int32_t *recent,
     if (k > 0) HIPCHK(hipMemcpy(recent, b + o_r, (size_t)k * 4, hipMemcpyDeviceToHost));
     c->prof.collect();
     *nout = k;
+    return ORBG_OK;
+}
+
+// ---------------------------------------------------------------------------
+// MapPoint::Replace, Fuse's map update, SearchInNeighbors (map_edit_kernels.hip)
+// ---------------------------------------------------------------------------
+extern "C" int orbg_map_get_point_replaced(orbg_ctx *c, orbg_map *m, int first, int n,
+                                           int32_t *replaced)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_range_ok(m, first, n))) return rc;
+    if (n == 0) return ORBG_OK;
+    if (!replaced) return set_err(ORBG_EINVAL, "NULL array");
+    HIPCHK(hipMemcpyAsync(replaced, m->D.mp_replaced + first, (size_t)n * 4, hipMemcpyDeviceToHost,
+                          c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_get_point_descriptors(orbg_ctx *c, orbg_map *m, int first, int n,
+                                              uint8_t *desc)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_range_ok(m, first, n))) return rc;
+    if (n == 0) return ORBG_OK;
+    if (!desc) return set_err(ORBG_EINVAL, "NULL array");
+    HIPCHK(hipMemcpyAsync(desc, m->D.mdesc + (size_t)first * 32, (size_t)n * 32, hipMemcpyDeviceToHost,
+                          c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_attach_keyframes(orbg_ctx *c, orbg_map *m, const orbg_keyframes *kfs, int cap,
+                                         const orbg_frustum_camera *d_cams)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (!kfs) {
+        m->attached = false;
+        m->att = MapAttach{};
+        return ORBG_OK;
+    }
+    if (cap < 1 || cap > ORBG_MAP_MAX_KF_CAP) return set_err(ORBG_EINVAL, "cap %d outside [1, %d]", cap, ORBG_MAP_MAX_KF_CAP);
+    if (!kfs->desc || !kfs->kps || !kfs->counts || !d_cams)
+        return set_err(ORBG_EINVAL, "NULL device array (desc, kps, counts and the cameras are read)");
+    m->att.kfs = *kfs;
+    m->att.cap = cap;
+    m->att.cams = d_cams;
+    m->attached = true;
+    return ORBG_OK;
+}
+
+static int map_attached(const orbg_map *m)
+{
+    return m->attached ? ORBG_OK : set_err(ORBG_EINVAL, "no keyframe data attached (orbg_map_attach_keyframes)");
+}
+
+// the workspace of one Fuse / SearchInNeighbors call over up to ncap points
+static int map_edit_ws(orbg_ctx *c, orbg_map *m, int ncap)
+{
+    if (m->d_ws && ncap <= m->W.ncap) return ORBG_OK;
+    if (m->d_ws) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipFree(m->d_ws));
+        m->d_ws = nullptr;
+        m->W = MapEditWs{};
+    }
+    const size_t n = (size_t)ncap;
+    Layout L;
+    const size_t o_h = L.take(16 * 4), o_c = L.take(sizeof(orbg_frustum_camera));
+    const size_t o_t = L.take((ORBG_MAP_MAX_TARGETS + 8) * 4), o_s = L.take(((size_t)m->D.cap + 1) * 4);
+    const size_t o_i = L.take((n + 1) * 4), o_m = L.take(n * sizeof(orbg_map_point)), o_d = L.take(n * 32);
+    const size_t o_bi = L.take(n * 4), o_bd = L.take(n * 4), o_st = L.take(n * 4), o_sv = L.take(n * 4);
+    const size_t o_do = L.take((n + 1) * 4), o_db = L.take(n * 4), o_dd = L.take(n * 32);
+    if (hipMalloc(&m->d_ws, L.total()) != hipSuccess) {
+        m->d_ws = nullptr;
+        return set_err(ORBG_ENOMEM, "Map: hipMalloc(%zu bytes) for the edit workspace", L.total());
+    }
+    HIPCHK(hipMemsetAsync(m->d_ws, 0, L.total(), c->stream));
+    uint8_t *b = (uint8_t *)m->d_ws;
+    MapEditWs &W = m->W;
+    W.ncap = ncap;
+    W.hdr = L.at<int32_t>(b, o_h);
+    W.cam = L.at<orbg_frustum_camera>(b, o_c);
+    W.targets = L.at<int32_t>(b, o_t);
+    W.snap = L.at<int32_t>(b, o_s);
+    W.ids = L.at<int32_t>(b, o_i);
+    W.mps = L.at<orbg_map_point>(b, o_m);
+    W.mdesc = L.at<uint8_t>(b, o_d);
+    W.bidx = L.at<int32_t>(b, o_bi);
+    W.bdist = L.at<int32_t>(b, o_bd);
+    W.hits = L.at<int32_t>(b, o_st);
+    W.surv = L.at<int32_t>(b, o_sv);
+    W.dd_off = L.at<int32_t>(b, o_do);
+    W.dd_best = L.at<int32_t>(b, o_db);
+    W.dd_desc = L.at<uint8_t>(b, o_dd);
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_add_observations_device(orbg_ctx *c, orbg_map *m, const int32_t *d_slots,
+                                                const int32_t *d_idx, const int32_t *d_point_ids,
+                                                int n, int32_t *d_status)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (n < 0) return set_err(ORBG_EINVAL, "negative size");
+    if (n == 0) return ORBG_OK;
+    if (!d_slots || !d_idx || !d_point_ids) return set_err(ORBG_EINVAL, "NULL device array");
+    if (launch_map_add_observations(c->stream, m->D, d_slots, d_idx, d_point_ids, n, d_status))
+        return set_err(ORBG_EIO, "k_map_add_obs launch failed");
+    m->dirty = m->touched = true;
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_add_observations(orbg_ctx *c, orbg_map *m, const int32_t *slots,
+                                         const int32_t *idx, const int32_t *point_ids, int n,
+                                         int32_t *status)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (n < 0) return set_err(ORBG_EINVAL, "negative size");
+    if (n == 0) return ORBG_OK;
+    if (!slots || !idx || !point_ids) return set_err(ORBG_EINVAL, "NULL array");
+    const size_t nb = (size_t)n * 4;
+    Layout L;
+    const size_t o_s = L.take(nb), o_i = L.take(nb), o_p = L.take(nb), o_st = L.take(nb);
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
+    HIPCHK(hipMemcpyAsync(b + o_s, slots, nb, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(b + o_i, idx, nb, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(b + o_p, point_ids, nb, hipMemcpyHostToDevice, c->stream));
+    if ((rc = orbg_map_add_observations_device(c, m, L.at<int32_t>(b, o_s), L.at<int32_t>(b, o_i),
+                                               L.at<int32_t>(b, o_p), n, L.at<int32_t>(b, o_st))))
+        return rc;
+    if (status) HIPCHK(hipMemcpyAsync(status, b + o_st, nb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return ORBG_OK;
+}
+
+// ComputeDistinctiveDescriptors of d_ids[i], i < min(n, d_n[0]); the workspace holds n entries
+static int map_distinctive(orbg_ctx *c, orbg_map *m, const int32_t *d_ids, int n, const int32_t *d_n)
+{
+    int rc = orbg_map_rebuild(c, m);
+    if (rc) return rc;
+    const MapEditWs &W = m->W;
+    hipStream_t st = c->stream;
+    PROF_LAUNCH(c, "map_distinctive",
+                rc = launch_map_distinctive(st, m->D, m->att, d_ids, n, d_n, ++m->epoch, W.dd_off,
+                                            W.hdr + MAP_HDR_TOT, W.dd_best, W.dd_desc));
+    if (rc) return set_err(rc, "ComputeDistinctiveDescriptors launch failed");
+    m->touched = true;
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_distinctive_descriptors_device(orbg_ctx *c, orbg_map *m,
+                                                       const int32_t *d_point_ids, int n)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (n < 0) return set_err(ORBG_EINVAL, "negative size");
+    if ((rc = map_attached(m))) return rc;
+    if (n == 0) return ORBG_OK;
+    if (!d_point_ids) return set_err(ORBG_EINVAL, "NULL device array");
+    if ((rc = map_edit_ws(c, m, n))) return rc;
+    return map_distinctive(c, m, d_point_ids, n, nullptr);
+}
+
+extern "C" int orbg_map_replace_device(orbg_ctx *c, orbg_map *m, const int32_t *d_old,
+                                       const int32_t *d_new, int n, int32_t *d_status)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (n < 0) return set_err(ORBG_EINVAL, "negative size");
+    if ((rc = map_attached(m))) return rc;
+    if (n == 0) return ORBG_OK;
+    if (!d_old || !d_new) return set_err(ORBG_EINVAL, "NULL device array");
+    if ((rc = map_edit_ws(c, m, n))) return rc;
+    if ((rc = orbg_map_rebuild(c, m))) return rc;
+    hipStream_t st = c->stream;
+    PROF_LAUNCH(c, "map_replace", rc = launch_map_replace(st, m->D, d_old, d_new, n, ++m->epoch,
+                                                         d_status, m->W.surv));
+    if (rc) return set_err(rc, "k_map_replace launch failed");
+    m->dirty = m->touched = true;
+    return map_distinctive(c, m, m->W.surv, n, nullptr);
+}
+
+extern "C" int orbg_map_replace(orbg_ctx *c, orbg_map *m, const int32_t *olds, const int32_t *news,
+                                int n, int32_t *status)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (n < 0) return set_err(ORBG_EINVAL, "negative size");
+    if ((rc = map_attached(m))) return rc;
+    if (n == 0) return ORBG_OK;
+    if (!olds || !news) return set_err(ORBG_EINVAL, "NULL array");
+    const size_t nb = (size_t)n * 4;
+    Layout L;
+    const size_t o_o = L.take(nb), o_n = L.take(nb), o_st = L.take(nb);
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
+    HIPCHK(hipMemcpyAsync(b + o_o, olds, nb, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(b + o_n, news, nb, hipMemcpyHostToDevice, c->stream));
+    if ((rc = orbg_map_replace_device(c, m, L.at<int32_t>(b, o_o), L.at<int32_t>(b, o_n), n,
+                                      L.at<int32_t>(b, o_st))))
+        return rc;
+    if (status) HIPCHK(hipMemcpyAsync(status, b + o_st, nb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->prof.collect();
+    return ORBG_OK;
+}
+
+// One Fuse call: the job (slot >= 0 from the host, else an entry of SearchInNeighbors' device
+// lists), the gather, the existing search, the sequential update, the survivors' descriptors.
+static int map_fuse_core(orbg_ctx *c, orbg_map *m, int slot, const int32_t *d_ids, int n, int nmax,
+                         int entry, int cur, float th, int32_t *d_best_idx, int32_t *d_best_dist,
+                         int32_t *d_status, int32_t *d_nfused, int at_ntargets)
+{
+    int rc = orbg_map_rebuild(c, m);
+    if (rc) return rc;
+    const MapEditWs &W = m->W;
+    hipStream_t st = c->stream;
+    if (launch_map_fuse_job(st, m->D, m->att, W, slot, n, entry, cur) ||
+        launch_map_fuse_gather(st, m->D, W, d_ids, nmax))
+        return set_err(ORBG_EIO, "k_fuse_gather launch failed");
+    PROF_LAUNCH(c, "map_fuse_search",
+                rc = launch_fuse(st, m->att.kfs, m->att.cap, W.hdr + MAP_HDR_SLOT, W.cam, W.mps,
+                                 W.mdesc, W.hdr + MAP_HDR_N, W.ncap, 1, th, c->scale, c->inv_sigma2,
+                                 c->p.nlevels, 0, W.bidx, W.bdist, W.hdr + MAP_HDR_SEARCH, c->d_err));
+    if (rc == -95) return set_err(ORBG_ENOTSUP, "Fuse: more than 8192 keypoints per KeyFrame");
+    if (rc) return set_err(ORBG_EIO, "k_fuse launch failed");
+    PROF_LAUNCH(c, "map_fuse_update",
+                rc = launch_map_fuse_update(st, m->D, W, d_ids, nmax, ++m->epoch, d_best_idx,
+                                            d_best_dist, d_status, d_nfused, at_ntargets));
+    if (rc) return set_err(rc, "k_fuse_update launch failed");
+    m->dirty = m->touched = true;
+    return map_distinctive(c, m, W.surv, nmax, W.hdr + MAP_HDR_N);
+}
+
+extern "C" int orbg_map_fuse_device(orbg_ctx *c, orbg_map *m, int slot, const int32_t *d_point_ids,
+                                    int n, float th, int32_t *d_best_idx, int32_t *d_best_dist,
+                                    int32_t *d_status, int32_t *d_nfused)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_slot_ok(m, slot))) return rc;
+    if (n < 0) return set_err(ORBG_EINVAL, "negative size");
+    if ((rc = map_attached(m))) return rc;
+    if (!d_nfused) return set_err(ORBG_EINVAL, "NULL device array");
+    if (n == 0) {
+        HIPCHK(hipMemsetAsync(d_nfused, 0, 4, c->stream));
+        return ORBG_OK;
+    }
+    if (!d_point_ids) return set_err(ORBG_EINVAL, "NULL device array");
+    if ((rc = map_edit_ws(c, m, n))) return rc;
+    return map_fuse_core(c, m, slot, d_point_ids, n, n, 0, slot, th, d_best_idx, d_best_dist, d_status,
+                         d_nfused, 0);
+}
+
+extern "C" int orbg_map_fuse(orbg_ctx *c, orbg_map *m, int slot, const int32_t *point_ids, int n,
+                             float th, int32_t *best_idx, int32_t *best_dist, int32_t *status,
+                             int32_t *nfused)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (n < 0 || !nfused || (n && !point_ids)) return set_err(ORBG_EINVAL, "negative size / NULL array");
+    const size_t nb = (size_t)std::max(n, 1) * 4;
+    Layout L;
+    const size_t o_p = L.take(nb), o_bi = L.take(nb), o_bd = L.take(nb), o_st = L.take(nb);
+    const size_t o_n = L.take(4);
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
+    if (n) HIPCHK(hipMemcpyAsync(b + o_p, point_ids, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    if ((rc = orbg_map_fuse_device(c, m, slot, L.at<int32_t>(b, o_p), n, th, L.at<int32_t>(b, o_bi),
+                                   L.at<int32_t>(b, o_bd), L.at<int32_t>(b, o_st),
+                                   L.at<int32_t>(b, o_n))))
+        return rc;
+    HIPCHK(hipMemcpyAsync(nfused, b + o_n, 4, hipMemcpyDeviceToHost, c->stream));
+    if (n && best_idx) HIPCHK(hipMemcpyAsync(best_idx, b + o_bi, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (n && best_dist) HIPCHK(hipMemcpyAsync(best_dist, b + o_bd, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (n && status) HIPCHK(hipMemcpyAsync(status, b + o_st, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->prof.collect();
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_search_in_neighbors_device(orbg_ctx *c, orbg_map *m, int slot,
+                                                   int current_kf_id, int monocular, float th,
+                                                   int32_t *d_targets, int target_cap,
+                                                   int32_t *d_ntargets, int32_t *d_nfused)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_slot_ok(m, slot))) return rc;
+    if ((rc = map_attached(m))) return rc;
+    if (target_cap < 0 || !d_ntargets || !d_nfused || (target_cap && !d_targets))
+        return set_err(ORBG_EINVAL, "bad target_cap / NULL device array");
+    const int bound = monocular ? ORBG_MAP_MAX_TARGETS : ORBG_MAP_MAX_TARGETS / 2;  // nn + 5 nn
+    if ((rc = map_edit_ws(c, m, ORBG_MAP_MAX_TARGETS * m->D.cap))) return rc;
+    const MapEditWs &W = m->W;
+    hipStream_t st = c->stream;
+    if (launch_map_sin_targets(st, m->D, W, slot, current_kf_id, monocular != 0, d_targets, target_cap,
+                               d_ntargets, d_nfused))
+        return set_err(ORBG_EIO, "k_sin_targets launch failed");
+    m->touched = true;
+    for (int t = 0; t < bound; t++)
+        if ((rc = map_fuse_core(c, m, -1, W.snap, 0, m->D.cap, t, slot, th, nullptr, nullptr, nullptr,
+                                d_nfused + t, 0)))
+            return rc;
+    if (launch_map_sin_candidates(st, m->D, W)) return set_err(ORBG_EIO, "k_sin_candidates launch failed");
+    if ((rc = map_fuse_core(c, m, -1, W.ids, 0, W.ncap, ORBG_MAP_MAX_TARGETS, slot, th, nullptr, nullptr,
+                            nullptr, d_nfused, 1)))
+        return rc;
+    // ComputeDistinctiveDescriptors and UpdateNormalAndDepth of the row as it stands now
+    if (launch_map_sin_row(st, m->D, W, slot)) return set_err(ORBG_EIO, "k_sin_row launch failed");
+    if ((rc = map_distinctive(c, m, W.snap, m->D.cap, nullptr))) return rc;
+    if ((rc = orbg_map_update_normal_and_depth_batch_device(c, m, W.snap, m->D.cap))) return rc;
+    return orbg_map_update_connections_batch_device(c, m, W.hdr + MAP_HDR_CUR, 1);
+}
+
+extern "C" int orbg_map_search_in_neighbors(orbg_ctx *c, orbg_map *m, int slot, int current_kf_id,
+                                            int monocular, float th, int32_t *targets,
+                                            int target_cap, int32_t *ntargets, int32_t *nfused)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (target_cap < 0 || !ntargets || !nfused || (target_cap && !targets))
+        return set_err(ORBG_EINVAL, "bad target_cap / NULL array");
+    Layout L;
+    const size_t o_t = L.take((size_t)target_cap * 4), o_n = L.take(4);
+    const size_t o_f = L.take((ORBG_MAP_MAX_TARGETS + 1) * 4);
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
+    if ((rc = orbg_map_search_in_neighbors_device(c, m, slot, current_kf_id, monocular, th,
+                                                  L.at<int32_t>(b, o_t), target_cap,
+                                                  L.at<int32_t>(b, o_n), L.at<int32_t>(b, o_f))))
+        return rc;
+    int32_t nt = 0;
+    HIPCHK(hipMemcpyAsync(&nt, b + o_n, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(nfused, b + o_f, (ORBG_MAP_MAX_TARGETS + 1) * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const int nw = std::min(nt, target_cap);
+    if (nw > 0) HIPCHK(hipMemcpy(targets, b + o_t, (size_t)nw * 4, hipMemcpyDeviceToHost));
+    c->prof.collect();
+    *ntargets = nt;
+    if (nt > target_cap) return set_err(ORBG_ERANGE, "%d target entries (target_cap %d)", nt, target_cap);
     return ORBG_OK;
 }

@@ -1,6 +1,7 @@
 // map_args.h -- device layout and launch arguments of the covisibility Map (map_kernels.hip:
 // KeyFrame::UpdateConnections, Tracking::UpdateLocalKeyFrames / UpdateLocalPoints,
-// MapPoint::UpdateNormalAndDepth), shared with the host entry points (api_map.hip).
+// MapPoint::UpdateNormalAndDepth; map_cull_kernels.hip; map_edit_kernels.hip), shared with the
+// host entry points (api_map.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -64,6 +65,13 @@ struct MapDev {
     int32_t *cull_list;         // [K] KeyFrameCulling's copy of the ordered list
     int32_t *cull_score;        // [K][2] nMPs, nRedundant of the list entries at the call's start
     int32_t *cull_out;          // [4] a status for the host forms
+    int32_t *mp_replaced;       // [P] mpReplaced as an id, -1 = none
+    // map_edit_kernels.hip: valid where the stamp equals the number of the running call
+    int32_t *ed_next, *ed_tail; // [P] the points merged into a point during this call, as a list
+    int32_t *ed_chain;          // [P] stamp of ed_next / ed_tail
+    int32_t *ed_inkf;           // [P] stamp: the point entered the Fuse keyframe's row in this call
+    int32_t *ed_mark;           // [P] stamp: the point is already listed for its descriptor
+    int32_t *ed_first;          // [P] SearchInNeighbors: first position of a fuse candidate
 };
 
 struct MapScales {
@@ -120,5 +128,58 @@ int launch_map_keyframe_culling(hipStream_t st, const MapDev &M, int slot, int m
 int launch_map_point_culling(hipStream_t st, const MapDev &M, int32_t *recent, int n,
                              int current_kf_id, int monocular, int32_t *nout, int32_t *status,
                              Prof *prof);
+
+// map_edit_kernels.hip: the attached keyframe data, the map-owned workspace of one Fuse /
+// SearchInNeighbors call (ncap entries per array) and the launches
+#define ORBG_MAP_MAX_TARGETS 120      // SearchInNeighbors: 20 first-level + 20 * 5 second-level
+#define ORBG_MAP_TH_LOW 50            // ORBmatcher::TH_LOW
+struct MapAttach {
+    orbg_keyframes kfs;               // indexed by slot, rows of `cap`
+    int32_t cap;
+    const orbg_frustum_camera *cams;  // [K]
+};
+struct MapEditWs {
+    int32_t ncap;
+    int32_t *hdr;                     // [16] MAP_HDR_*: the job (slot, count, active), the search's own count
+    orbg_frustum_camera *cam;         // [1] the job's camera
+    int32_t *targets;                 // [ORBG_MAP_MAX_TARGETS + 8], ntargets behind them
+    int32_t *snap;                    // [cap + 1] the slot's row, its length behind it
+    int32_t *ids;                     // [ncap + 1] fuse candidates, their count behind them
+    orbg_map_point *mps;              // [ncap] the search inputs
+    uint8_t *mdesc;                   // [ncap][32]
+    int32_t *bidx, *bdist;            // [ncap] the search outputs
+    int32_t *hits, *surv;             // [ncap] the points with a target, the survivors
+    int32_t *dd_off, *dd_best;        // [ncap + 1], [ncap]
+    uint8_t *dd_desc;                 // [ncap][32]
+};
+#define MAP_HDR_SLOT 0
+#define MAP_HDR_N 1
+#define MAP_HDR_ACTIVE 2
+#define MAP_HDR_SEARCH 3
+#define MAP_HDR_CUR 8                 // the searched slot, for UpdateConnections
+#define MAP_HDR_TOT 10                // [2] launch_map_distinctive's totals
+int launch_map_add_observations(hipStream_t st, const MapDev &M, const int32_t *slots,
+                                const int32_t *idx, const int32_t *ids, int n, int32_t *status);
+// ComputeDistinctiveDescriptors of ids[i], i < min(n, dn[0]) (dn NULL: n), over a current
+// observation index; rows = M.obs_tmp, off [n + 1] / tot [2] / best [n] / desc [n][32] workspace
+int launch_map_distinctive(hipStream_t st, const MapDev &M, const MapAttach &A, const int32_t *ids,
+                           int n, const int32_t *dn, int epoch, int32_t *off, int32_t *tot,
+                           int32_t *best, uint8_t *desc);
+int launch_map_replace(hipStream_t st, const MapDev &M, const int32_t *olds, const int32_t *news,
+                       int n, int epoch, int32_t *status, int32_t *surv);
+// job: slot >= 0: that slot with n ids; slot < 0: entry `entry` of W.targets with W.snap
+// (entry < ORBG_MAP_MAX_TARGETS) or the slot `cur` with W.ids (entry == ORBG_MAP_MAX_TARGETS)
+int launch_map_fuse_job(hipStream_t st, const MapDev &M, const MapAttach &A, const MapEditWs &W,
+                        int slot, int n, int entry, int cur);
+int launch_map_fuse_gather(hipStream_t st, const MapDev &M, const MapEditWs &W, const int32_t *ids,
+                           int nmax);
+int launch_map_fuse_update(hipStream_t st, const MapDev &M, const MapEditWs &W, const int32_t *ids,
+                           int nmax, int epoch, int32_t *best_idx, int32_t *best_dist,
+                           int32_t *status, int32_t *nfused, int nfused_at_ntargets);
+int launch_map_sin_targets(hipStream_t st, const MapDev &M, const MapEditWs &W, int slot,
+                           int current_kf_id, int monocular, int32_t *targets, int target_cap,
+                           int32_t *ntargets, int32_t *nfused);
+int launch_map_sin_candidates(hipStream_t st, const MapDev &M, const MapEditWs &W);
+int launch_map_sin_row(hipStream_t st, const MapDev &M, const MapEditWs &W, int slot);
 
 }  // namespace orbg

@@ -68,19 +68,6 @@ __device__ __forceinline__ CullLds cull_lds_of(int K, int bn)
     return L;
 }
 
-// entry ob of point p's (possibly stale) index segment still stands; its slot and feature
-__device__ __forceinline__ bool cull_obs(const MapDev &M, uint32_t ob, int p, int *u, int *j)
-{
-    *u = (int)(ob >> 16);
-    *j = (int)(ob & 0xFFFFu);
-    return (M.kf_flags[*u] & MAP_KF_LIVE) && M.kf_points[(size_t)*u * M.cap + *j] == p;
-}
-
-__device__ __forceinline__ int cull_weight(const MapDev &M, int u, int j)
-{
-    return (M.kf_feat[(size_t)u * M.cap + j] & ORBG_MAP_FEAT_STEREO) ? 2 : 1;
-}
-
 // MapPoint::SetBadFlag: bad, and out of every row that holds it
 __device__ __forceinline__ void cull_point_bad(const MapDev &M, int p)
 {

@@ -1,6 +1,7 @@
-// map_device.h -- what the Map's kernel files share (map_kernels.hip, map_cull_kernels.hip): the
-// workgroup size, the sort-key layout, the workgroup scan, the LDS bitonic sort and the store of
-// an ordered list.  Every kernel file that includes it has its own map_smem.
+// map_device.h -- what the Map's kernel files share (map_kernels.hip, map_cull_kernels.hip,
+// map_edit_kernels.hip): the workgroup size, the sort-key layout, the workgroup scan, the LDS
+// bitonic sort, the store of an ordered list and the test of an entry of a stale observation
+// index.  Every kernel file that includes it has its own map_smem.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -108,6 +109,19 @@ static __device__ void map_store_order(const MapDev &M, int s, const uint32_t *k
 __device__ __forceinline__ bool map_point_ok(const MapDev &M, int p)
 {
     return p >= 0 && p < M.P && (M.mp[p].flags & ORBG_MP_VALID);
+}
+
+// entry ob of point p's (possibly stale) index segment still stands; its slot and feature
+__device__ __forceinline__ bool cull_obs(const MapDev &M, uint32_t ob, int p, int *u, int *j)
+{
+    *u = (int)(ob >> 16);
+    *j = (int)(ob & 0xFFFFu);
+    return (M.kf_flags[*u] & MAP_KF_LIVE) && M.kf_points[(size_t)*u * M.cap + *j] == p;
+}
+
+__device__ __forceinline__ int cull_weight(const MapDev &M, int u, int j)
+{
+    return (M.kf_feat[(size_t)u * M.cap + j] & ORBG_MAP_FEAT_STEREO) ? 2 : 1;
 }
 
 static inline int last_rc() { return hipGetLastError() == hipSuccess ? ORBG_OK : ORBG_EIO; }

@@ -83,3 +83,20 @@ class LocalMapping:
                                          L.ptr(ca), L.ptr(cb), L.ptr(m), L.ptr(x), L.ptr(st),
                                          C.byref(n)), "orbg_triangulate")
         return n.value, x[:a.n].copy(), st[:a.n].copy()
+
+    def RunOnMap(self, m, slot, current_kf_id, monocular, recent, create_new_map_points=None,
+                 local_bundle_adjustment=None, th=3.0):
+        """One keyframe's pass of LocalMapping::Run (src/LocalMapping.cc:55-120) over a device
+        Map `m` whose row `slot` ProcessNewKeyFrame has uploaded: MapPointCulling of `recent`,
+        create_new_map_points(recent) -> recent (the caller's: the triangulation above, then
+        Map.SetPoints and Map.AddObservations for the new ids), SearchInNeighbors,
+        local_bundle_adjustment() (the caller's), KeyFrameCulling.  Every step edits the one
+        table in HBM.  Returns (mlpRecentAddedMapPoints, vpTargetKFs, the nFused of each
+        target's Fuse, the second pass's, the CULL_RECORD_DTYPE records)."""
+        recent, _ = m.MapPointCulling(recent, current_kf_id, monocular)
+        if create_new_map_points is not None:
+            recent = create_new_map_points(recent)
+        targets, nfused, second = m.SearchInNeighbors(slot, current_kf_id, monocular, th)
+        if local_bundle_adjustment is not None:
+            local_bundle_adjustment()
+        return recent, targets, nfused, second, m.KeyFrameCulling(slot, monocular)

@@ -28,6 +28,7 @@ from . import _lib as L
 from .orbmatcher import _ctx
 
 NEIGHBOURS = 10
+SIN_MAX_TARGETS = 120     # SearchInNeighbors: 20 first-level + 20 * 5 second-level entries
 KF_ROOT, KF_BAD = 1, 2
 FEAT_STEREO, FEAT_CLOSE = L.MAP_FEAT_STEREO, L.MAP_FEAT_CLOSE
 
@@ -391,6 +392,115 @@ class Map:
                                                      len(out), C.byref(n)),
                 "orbg_map_get_keyframe_points")
         return out[:n.value]
+
+    # ---- MapPoint::Replace, ORBmatcher::Fuse, LocalMapping::SearchInNeighbors ----
+    def AttachKeyFrames(self, d_desc, d_kps, d_uright, d_counts, cap, d_cams):
+        """The keyframes' data the search and ComputeDistinctiveDescriptors read, as device
+        pointers (ints) indexed by slot: mDescriptors [K][cap][32], mvKeysUn [K][cap]
+        (KEYPOINT records), mvuRight [K][cap] (None: monocular), N [K], FRUSTUM_DTYPE cameras
+        [K].  Not owned: the arrays must outlive the attachment.  d_desc None detaches."""
+        if d_desc is None:
+            L.check(L.lib().orbg_map_attach_keyframes(self._c(), self._h, None, 0, None),
+                    "orbg_map_attach_keyframes")
+            return
+        k = L.KeyFrames(d_desc, d_kps, d_uright, None, d_counts, None, None, None, None)
+        L.check(L.lib().orbg_map_attach_keyframes(self._c(), self._h, C.byref(k), int(cap), d_cams),
+                "orbg_map_attach_keyframes")
+
+    def AddObservations(self, slots, idx, point_ids):
+        """AddObservation + AddMapPoint, entries in order; the status per entry (0 = added)"""
+        s, i, p = _i32(slots), _i32(idx), _i32(point_ids)
+        if not (len(s) == len(i) == len(p)):
+            raise ValueError("slots, feature indices and point ids differ in length")
+        st = np.zeros(len(s), np.int32)
+        L.check(L.lib().orbg_map_add_observations(self._c(), self._h, L.ptr(s), L.ptr(i), L.ptr(p),
+                                                  len(s), L.ptr(st)), "orbg_map_add_observations")
+        return st
+
+    def add_observations_device(self, d_slots, d_idx, d_point_ids, n, d_status, ctx=None):
+        L.check(L.lib().orbg_map_add_observations_device(self._c(ctx), self._h, d_slots, d_idx,
+                                                         d_point_ids, int(n), d_status),
+                "orbg_map_add_observations_device")
+
+    def Replace(self, old_ids, new_ids):
+        """old->Replace(new) pair by pair, then the survivors' descriptors; the status per pair
+        (0 replaced, 1 same point, 2 new bad, 3 old out of range, 4 old already bad)"""
+        o, w = _i32(old_ids), _i32(new_ids)
+        if len(o) != len(w):
+            raise ValueError("old and new ids differ in length")
+        st = np.zeros(len(o), np.int32)
+        L.check(L.lib().orbg_map_replace(self._c(), self._h, L.ptr(o), L.ptr(w), len(o), L.ptr(st)),
+                "orbg_map_replace")
+        return st
+
+    def replace_device(self, d_old, d_new, n, d_status, ctx=None):
+        L.check(L.lib().orbg_map_replace_device(self._c(ctx), self._h, d_old, d_new, int(n),
+                                                d_status), "orbg_map_replace_device")
+
+    def distinctive_descriptors_device(self, d_point_ids, n, ctx=None):
+        L.check(L.lib().orbg_map_distinctive_descriptors_device(self._c(ctx), self._h, d_point_ids,
+                                                                int(n)),
+                "orbg_map_distinctive_descriptors_device")
+
+    def ComputeDistinctiveDescriptors(self, point_ids):
+        """MapPoint::ComputeDistinctiveDescriptors of the listed points into the map"""
+        import torch
+        ids = torch.from_numpy(_i32(point_ids)).to("cuda:%d" % self.device)
+        torch.cuda.synchronize()
+        self.distinctive_descriptors_device(ids.data_ptr(), ids.numel())
+        _ctx(self.device).sync()
+
+    def Fuse(self, slot, point_ids, th=3.0):
+        """ORBmatcher::Fuse(pKF, vpMapPoints, th) on the map: (nFused, status, best_idx,
+        best_dist), status per point as include/orbg.h lists it"""
+        p = _i32(point_ids)
+        bi, bd, st = (np.zeros(len(p), np.int32) for _ in range(3))
+        n = C.c_int32()
+        L.check(L.lib().orbg_map_fuse(self._c(), self._h, int(slot), L.ptr(p), len(p), float(th),
+                                      L.ptr(bi), L.ptr(bd), L.ptr(st), C.byref(n)), "orbg_map_fuse")
+        return n.value, st, bi, bd
+
+    def fuse_device(self, slot, d_point_ids, n, th, d_best_idx, d_best_dist, d_status, d_nfused,
+                    ctx=None):
+        L.check(L.lib().orbg_map_fuse_device(self._c(ctx), self._h, int(slot), d_point_ids, int(n),
+                                             float(th), d_best_idx, d_best_dist, d_status,
+                                             d_nfused), "orbg_map_fuse_device")
+
+    def SearchInNeighbors(self, slot, current_kf_id, monocular, th=3.0):
+        """LocalMapping::SearchInNeighbors: (vpTargetKFs as slots, duplicates included, the
+        return value of each entry's Fuse, the second pass's)"""
+        t = np.full(SIN_MAX_TARGETS, -1, np.int32)
+        nf = np.zeros(SIN_MAX_TARGETS + 1, np.int32)
+        n = C.c_int32()
+        L.check(L.lib().orbg_map_search_in_neighbors(self._c(), self._h, int(slot),
+                                                     int(current_kf_id), int(bool(monocular)),
+                                                     float(th), L.ptr(t), len(t), C.byref(n),
+                                                     L.ptr(nf)), "orbg_map_search_in_neighbors")
+        return t[:n.value].tolist(), nf[:n.value].tolist(), int(nf[n.value])
+
+    def search_in_neighbors_device(self, slot, current_kf_id, monocular, th, d_targets, target_cap,
+                                   d_ntargets, d_nfused, ctx=None):
+        L.check(L.lib().orbg_map_search_in_neighbors_device(
+            self._c(ctx), self._h, int(slot), int(current_kf_id), int(bool(monocular)), float(th),
+            d_targets, int(target_cap), d_ntargets, d_nfused),
+            "orbg_map_search_in_neighbors_device")
+
+    def replaced(self, first=0, n=None):
+        """mpReplaced as ids (-1: none)"""
+        n = self.max_points - first if n is None else int(n)
+        out = np.zeros(n, np.int32)
+        L.check(L.lib().orbg_map_get_point_replaced(self._c(), self._h, int(first), n, L.ptr(out)),
+                "orbg_map_get_point_replaced")
+        return out
+
+    def descriptors(self, first=0, n=None):
+        """mDescriptor of the points, uint8 [n][32]"""
+        n = self.max_points - first if n is None else int(n)
+        out = np.zeros((n, 32), np.uint8)
+        L.check(L.lib().orbg_map_get_point_descriptors(self._c(), self._h, int(first), n,
+                                                       L.ptr(out)),
+                "orbg_map_get_point_descriptors")
+        return out
 
     def point_refs(self, first=0, n=None):
         """mpRefKF as slots (-1: none)"""
