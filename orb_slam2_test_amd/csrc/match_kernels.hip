@@ -82,22 +82,13 @@ __device__ __forceinline__ unsigned long long row16_min_u64(unsigned long long m
 //
 // best/second (ORBmatcher.cc:541-556's strict-< scan in train order): the smallest key is
 // (min distance, first index); the distance of the second smallest key is the multiset
-// second minimum, which is what the in-order rule leaves in bestDist2.  Per value: a max and
-// a min (second) and a min (best).
+// second minimum, which is what the in-order rule leaves in bestDist2.  Both are order-free
+// over the keys, so the loop takes them four at a time (update4 in knn2_block_fp4).
 typedef int knn_v4i __attribute__((ext_vector_type(4)));
 typedef int knn_v16i __attribute__((ext_vector_type(16)));
 
 #define KNN_MAX_TRAIN 8192   // train index in the 13 low key bits
 #define KNN_NONE 0x40000000  // C tag of the rows past nt: keys above any real one
-
-// key is read straight out of the MFMA result, so everything here stays compiler-visible (the
-// compiler places the MFMA -> VALU wait states; it does not for inline asm).  Three VOP2
-// ops: med3(k1, k2, key) with k1 <= k2, then the new minimum.
-__device__ __forceinline__ void knn_key_update(int key, int &k1, int &k2)
-{
-    k2 = min(k2, max(k1, key));
-    k1 = min(k1, key);
-}
 
 // knn2 on the fp4 matrix cores: v_mfma_scale_f32_32x32x64_f8f6f4 with e2m1 operands runs
 // K = 64 in the cycles the i8 form needs for K = 32, so K = 256 is four MFMAs (round 1's i8
@@ -108,17 +99,27 @@ __device__ __forceinline__ void knn_key_update(int key, int &k1, int &k2)
 // index + 2^20, so the key is 8192 d + index >= 0.  Every partial sum is an integer below
 // 2^22 in magnitude, exact in the f32 accumulator whatever the summation order; a
 // non-negative f32 orders like its bit pattern, so the top-2 runs on the u32 bits (integer
-// min / med3: no NaN canonicalisation).  Past-nt rows carry 2^30 (rounded sums stay
-// >= 2^30 - 2^20, above every real key).  k order (A and B alike): step s, lane half h -> descriptor dword 2s + h; VGPR
-// q, nibble j -> bit 4j + q of that dword.
+// min3 / med3: no NaN canonicalisation).  Past-nt rows carry 2^30 (rounded sums stay
+// >= 2^30 - 2^20, above every real key).  k order (A and B alike): step s, lane half h ->
+// descriptor dword 2s + h; VGPR q, nibble j -> bit 4j + q of that dword.
+//
+// Schedule of the train loop, as the binary has it (profiles/knn2_overlap_isa.txt): per
+// 64-row stage one barrier, the expansion of the next stage, then two 32-row subtiles of
+// eight MFMAs each; after every MFMA come five VALU ops, the top-2 update of four keys of the
+// subtile before, and after every other one a ds_read_b128 of the A fragment two MFMAs
+// ahead.  No accumulator is read before a whole subtile of MFMAs has been issued behind
+// its last one.  The C tags are 16 integer adds into the registers the first MFMA reads.
+// 127 VGPRs, no scratch, 4 waves per SIMD.
 typedef int knn_v8i __attribute__((ext_vector_type(8)));
 typedef float knn_v16f __attribute__((ext_vector_type(16)));
-#ifndef ORBG_KNN_MED3
-#define ORBG_KNN_MED3 1
+#ifndef KNN4_STAGE
+#define KNN4_STAGE 64  // train rows per barrier: 64 or 128
 #endif
+#define KNN4_NSUB (KNN4_STAGE / 32)
 #define KNN4_ROWB 144  // expanded train row: 128 B + 16 B pad (16 lanes' b128 reads: 64 banks)
 #define KNN4_SCALE_A (127 + 12)  // E8M0 2^12
 #define KNN4_SCALE_B 127         // E8M0 1.0
+#define KNN4_TAG0_BITS 0x49800000  // f32 bits of 2^20, the C tag of train row 0
 
 // e2m1 nibbles of bits q, q+4, .., q+28 of x: b=1 -> 0xA (-1.0), b=0 -> 0x2 (+1.0)
 __device__ __forceinline__ uint32_t knn4_neg(uint32_t x, int q)
@@ -135,7 +136,7 @@ __device__ __forceinline__ void knn2_block_fp4(const uint8_t *__restrict__ q, in
                                                const uint8_t *__restrict__ t, int nt,
                                                int32_t *__restrict__ out, int qbase)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t tile[2][64 * KNN4_ROWB];
+    __shared__ __attribute__((aligned(16))) uint8_t tile[2][KNN4_STAGE * KNN4_ROWB];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int col = lane & 31, h = lane >> 5;
     // B fragments: query qbase + 64 wv + 32 u + col, step s: dword 2s + h
@@ -158,13 +159,13 @@ __device__ __forceinline__ void knn2_block_fp4(const uint8_t *__restrict__ q, in
             }
         }
     }
-    uint32_t k1[2] = {UINT_MAX, UINT_MAX}, k2[2] = {UINT_MAX, UINT_MAX};
+    uint32_t k1[2] = {INT_MAX, INT_MAX}, k2[2] = {UINT_MAX, UINT_MAX};  // k1 <= k2, k1 < 2^31
 
-    // expansion of stage s0 (64 rows) into buffer bf: thread -> rows (tid >> 3) and
-    // (tid >> 3) + 32, dword tid & 7 -> 16 bytes at row offset 16 * dword
+    // expansion of one stage (KNN4_STAGE rows) into buffer bf: thread -> rows (tid >> 3) + 32 k,
+    // dword tid & 7 -> 16 bytes at row offset 16 * dword
     const int er = tid >> 3, esd = tid & 7;
     auto fetch1 = [&](int row) -> uint32_t {
-        return ((const uint32_t *)(t + (size_t)min(row, nt - 1) * 32))[esd];
+        return *(const uint32_t *)(t + (uint32_t)(min(row, nt - 1) * 32 + esd * 4));
     };
     auto expand1 = [&](uint32_t x, uint8_t *dst) {
         uint4 w;
@@ -172,79 +173,130 @@ __device__ __forceinline__ void knn2_block_fp4(const uint8_t *__restrict__ q, in
         w.z = knn4_neg(x, 2); w.w = knn4_neg(x, 3);
         *(uint4 *)dst = w;
     };
-    auto expand = [&](uint32_t x0, uint32_t x1, int bf) {
-        expand1(x0, tile[bf] + er * KNN4_ROWB + esd * 16);
-        expand1(x1, tile[bf] + (er + 32) * KNN4_ROWB + esd * 16);
+    auto expand = [&](const uint32_t (&x)[KNN4_NSUB], int bf) {
+#pragma unroll
+        for (int k = 0; k < KNN4_NSUB; k++)
+            expand1(x[k], tile[bf] + (er + 32 * k) * KNN4_ROWB + esd * 16);
     };
-    uint32_t xr0 = 0, xr1 = 0;
+    uint32_t xr[KNN4_NSUB] = {};
     if (nt > 0) {
-        expand(fetch1(er), fetch1(er + 32), 0);
-        xr0 = fetch1(64 + er);
-        xr1 = fetch1(96 + er);
+#pragma unroll
+        for (int k = 0; k < KNN4_NSUB; k++) xr[k] = fetch1(er + 32 * k);
+        expand(xr, 0);
+#pragma unroll
+        for (int k = 0; k < KNN4_NSUB; k++) xr[k] = fetch1(KNN4_STAGE + er + 32 * k);
     }
-    // two accumulator sets, one per 32-row subtile of a stage: the top-2 epilogue of one set
-    // runs while the MFMAs of the other are in flight (no accumulator copies)
+    // Two accumulator sets, alternating over the 32-row subtiles.  subtile() issues the eight
+    // MFMAs of one set and, in the gap after each, four key updates (5 VALU ops) out of the
+    // other set, whose last MFMA was issued a whole subtile earlier; every other gap also
+    // loads the A fragment of the next MFMA pair.  A sched_barrier closes each gap, so the
+    // binary keeps this order (the scheduler otherwise gathers the MFMAs into one run).
+    // accB starts as 2^30, a key above every real one, so the first subtile has an epilogue
+    // to run like any other.
     knn_v16f accA[2], accB[2];
+#pragma unroll
+    for (int r = 0; r < 16; r++) accB[0][r] = accB[1][r] = (float)KNN_NONE;
+    // four keys a, b, c, d of query u at a time, five ops.  With k1 <= k2 the smallest of
+    // {k1, k2, a, b} is min3(k1, a, b), and the second smallest is k2 or the middle one of
+    // {k1, a, b}, whichever is smaller; the same again for c, d on the new minimum, and one
+    // min3 takes both middle ones into k2.  Written as the min / max forms the backend folds
+    // to v_med3_u32 and v_min3_u32 (wait states after the MFMA by the compiler).
+    auto med3 = [](uint32_t x, uint32_t y, uint32_t z) {
+        return max(min(x, y), min(max(x, y), z));
+    };
+    auto update4 = [&](const knn_v16f (&acc)[2], int r, int u) {
+        // (via scalars: __builtin_bit_cast of an ext_vector element lvalue reads element 0
+        // under this clang)
+        const float f0 = acc[u][r], f1 = acc[u][r + 1], f2 = acc[u][r + 2], f3 = acc[u][r + 3];
+        const uint32_t a = __float_as_uint(f0), b = __float_as_uint(f1);
+        const uint32_t c = __float_as_uint(f2), d = __float_as_uint(f3);
+        // (the minimum runs on signed compares -- every key and k1 is below 2^31 -- so that
+        // the optimiser finds no min to share with the unsigned med3: shared, the min3 comes
+        // out as two v_min)
+        const uint32_t m1 = med3(a, b, k1[u]);
+        const uint32_t k1a = (uint32_t)min(min((int)k1[u], (int)a), (int)b);
+        const uint32_t m2 = med3(c, d, k1a);
+        k1[u] = (uint32_t)min(min((int)k1a, (int)c), (int)d);
+        k2[u] = min(min(k2[u], m1), m2);
+    };
     auto epilogue = [&](const knn_v16f (&acc)[2]) {
 #pragma unroll
-        for (int r = 0; r < 16; r++) {
-#pragma unroll
-            for (int u = 0; u < 2; u++) {
-                // k1 <= k2: the new second key is med3(k1, k2, key), then the new minimum
-                // (via a scalar: __builtin_bit_cast of an ext_vector element lvalue reads
-                // element 0 under this clang)
-                const float kf = acc[u][r];
-                const uint32_t key = __float_as_uint(kf);
-#if ORBG_KNN_MED3
-                // the min reads the MFMA result first (the compiler places the MFMA -> VALU
-                // wait states there); v_med3_u32 of (k1, k2, key) with k1 <= k2 is the new
-                // second key -- one op where the compiler's min/max form takes two
-                const uint32_t k1o = k1[u];
-                k1[u] = min(k1o, key);
-                asm volatile("v_med3_u32 %0, %1, %2, %3" : "=v"(k2[u]) : "v"(k1o), "v"(k2[u]), "v"(key));
-#else
-                k2[u] = min(k2[u], max(k1[u], key));
-                k1[u] = min(k1[u], key);
-#endif
-            }
+        for (int r = 0; r < 16; r += 4) {
+            update4(acc, r, 0);
+            update4(acc, r, 1);
         }
     };
-    auto subtile = [&](int tb, int bf, int sub, knn_v16f (&acc)[2]) {
+    auto afrag = [&](int bf, int sub, int s) -> knn_v4i {
+        return *(const knn_v4i *)(tile[bf] + (32 * sub + col) * KNN4_ROWB + h * 16 + s * 32);
+    };
+    knn_v4i a0 = {0, 0, 0, 0};  // first A fragment of the coming subtile
+    // last: rows past nt may be in it; next: subtile sub + 1 of this stage follows, so its
+    // first A fragment is loaded here (after a barrier the caller loads it)
+    auto subtile = [&](int tb, int bf, int sub, bool last, bool next, knn_v16f (&acc)[2],
+                       const knn_v16f (&old)[2]) {
+        // C tags: train index + 2^20, built on the bit pattern: in [2^20, 2^21) one unit is
+        // 8 in the f32 bits, so a tag is the base's bits + 8 * row constant, one integer add
+        // each into the registers the first MFMA reads as C (v_pk_add_f32 on the values
+        // costs several issue slots apiece beside the MFMAs).  The empty asm keeps the tags of
+        // a later subtile from being built, and held, ahead of this point.
+        __builtin_amdgcn_sched_barrier(0);
+        int tagb = KNN4_TAG0_BITS + 8 * (tb + 4 * h);
+        asm volatile("" : "+v"(tagb));
         knn_v16f ctag;
-        const float tbh = (float)(tb + 4 * h + (1 << 20));
 #pragma unroll
-        for (int r = 0; r < 16; r++) ctag[r] = tbh + (float)((r & 3) + 8 * (r >> 2));
-        if (tb + 32 > nt) {  // last subtile: rows past nt get keys above every real one
+        for (int r = 0; r < 16; r++) ctag[r] = __int_as_float(tagb + 8 * ((r & 3) + 8 * (r >> 2)));
+        if (last) {  // rows past nt get keys above every real one
 #pragma unroll
             for (int r = 0; r < 16; r++)
                 if (ctag[r] >= (float)(nt + (1 << 20))) ctag[r] = (float)KNN_NONE;
         }
-        const uint8_t *arow = tile[bf] + (32 * sub + col) * KNN4_ROWB + h * 16;
+        __builtin_amdgcn_sched_barrier(0);
+        knn_v4i a4[4];
+        a4[0] = a0;
 #pragma unroll
         for (int s = 0; s < 4; s++) {
-            const knn_v4i a4 = *(const knn_v4i *)(arow + s * 32);
-            const knn_v8i a = {a4[0], a4[1], a4[2], a4[3], 0, 0, 0, 0};
-            acc[0] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
-                a, bq[0][s], s ? acc[0] : ctag, 4, 4, 0, KNN4_SCALE_A, 0, KNN4_SCALE_B);
-            acc[1] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
-                a, bq[1][s], s ? acc[1] : ctag, 4, 4, 0, KNN4_SCALE_A, 0, KNN4_SCALE_B);
+            const knn_v8i a = {a4[s][0], a4[s][1], a4[s][2], a4[s][3], 0, 0, 0, 0};
+#pragma unroll
+            for (int u = 0; u < 2; u++) {
+                acc[u] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
+                    a, bq[u][s], s ? acc[u] : ctag, 4, 4, 0, KNN4_SCALE_A, 0, KNN4_SCALE_B);
+                if (u == 0) {
+                    if (s < 3)
+                        a4[s + 1] = afrag(bf, sub, s + 1);
+                    else if (next)
+                        a0 = afrag(bf, sub + 1, 0);
+                }
+                update4(old, 4 * s, u);
+                __builtin_amdgcn_sched_barrier(0);
+            }
         }
     };
-    bool pendB = false;
-    for (int s0 = 0, bf = 0; s0 < nt; s0 += 64, bf ^= 1) {
+    // a subtile past nt is skipped (in the last stage only), so the set that is still
+    // pending after the loop is the one the last subtile ran wrote
+    bool pendA = false;
+    for (int s0 = 0, bf = 0; s0 < nt; s0 += KNN4_STAGE, bf ^= 1) {
         __syncthreads();
-        if (s0 + 64 < nt) {
-            expand(xr0, xr1, bf ^ 1);
-            xr0 = fetch1(s0 + 128 + er);
-            xr1 = fetch1(s0 + 160 + er);
+        a0 = afrag(bf, 0, 0);
+        expand(xr, bf ^ 1);
+#pragma unroll
+        for (int k = 0; k < KNN4_NSUB; k++) xr[k] = fetch1(s0 + 2 * KNN4_STAGE + er + 32 * k);
+#pragma unroll
+        for (int k = 0; k < KNN4_NSUB; k += 2) {
+            if (k == 0 || s0 + 32 * k < nt) {
+                subtile(s0 + 32 * k, bf, k, s0 + 32 * k + 32 > nt, true, accA, accB);
+                pendA = true;
+            }
+            if (s0 + 32 * k + 32 < nt) {
+                subtile(s0 + 32 * k + 32, bf, k + 1, s0 + 32 * k + 64 > nt, k + 2 < KNN4_NSUB,
+                        accB, accA);
+                pendA = false;
+            }
         }
-        subtile(s0, bf, 0, accA);
-        if (pendB) epilogue(accB);
-        pendB = s0 + 32 < nt;
-        if (pendB) subtile(s0 + 32, bf, 1, accB);
-        epilogue(accA);
     }
-    if (pendB) epilogue(accB);
+    if (pendA)
+        epilogue(accA);
+    else
+        epilogue(accB);
     const uint32_t none = 0x4E000000u;  // bits of 2^29: real keys < 2^22, past-nt >= 2^30 - 2^20
 #pragma unroll
     for (int u = 0; u < 2; u++) {
@@ -282,7 +334,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
     if (bx * 256 >= nq) return;                                                                \
     BLOCK(desc + (size_t)b * fc * 32, nq, desc + (size_t)a * fc * 32, nt,                      \
           out + (size_t)p * fc * 3, bx * 256);
-// fp4: 128 VGPRs (4 waves per SIMD; two dwords spill outside the train loop)
+// fp4: 127 VGPRs (4 waves per SIMD), no scratch
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_knn2_pairs(
     const uint8_t *desc, const int32_t *counts, int fc, const int32_t *f1, const int32_t *f2,
     int32_t *out)
