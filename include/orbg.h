@@ -2012,6 +2012,182 @@ int orbg_optimize_essential_graph(orbg_ctx *ctx, const orbg_sim3d *Scw, const or
                                   int fixed_vertex, int fix_scale, int iterations,
                                   orbg_sim3d *Siw_out, float *Tiw_out, orbg_lm_report *report);
 
+/* ---------------- LoopClosing::CorrectLoop on the Map ----------------
+ * src/LoopClosing.cc:744-843 and 882-911 on an orbg_map: the state CorrectLoop reads beside
+ * the observation table, the Sim3 propagation with its map-point loop, LoopConnections, the
+ * walk that turns the map into OptimizeEssentialGraph's arrays (Optimizer.cc:1040-1258) and
+ * the application of the optimised poses (:1264-1323), the loop fusion and SearchAndFuse
+ * (:848-878), and orbg_map_correct_loop, which chains them.  Pointer order is slot order.
+ *
+ * State, all with defaults, so a map that never receives any of it behaves as before:
+ *  - per slot a pose Tcw (3x4 float, row-major), a "has a pose" flag (0 after create / clear)
+ *    and mnId (the slot itself after create / clear).  Setting a pose is KeyFrame::SetPose: it
+ *    also rewrites the camera centre the map stores, Ow = -Rcw^T tcw as the float cv::Mat
+ *    product (sums in double over k = 0, 1, 2 in order, one rounding to float).  d_Tcw or
+ *    d_mnid may be NULL (not both): that half is left as it is.  orbg_map_set_keyframe[s]
+ *    does not touch pose or mnId, and a later centre given there overwrites Ow.
+ *  - per slot mspLoopEdges, at most ORBG_MAP_MAX_LOOP_EDGES entries.  orbg_map_add_loop_edge
+ *    adds b to a's set and a to b's; an edge already there is not added again; ORBG_ERANGE,
+ *    nothing changed, when either side is full.  orbg_map_get_loop_edges: ascending slot.
+ *    erase_keyframe / set_bad_flag leave the edges alone; orbg_map_clear empties them.
+ *  - per point mnCorrectedByKF and mnCorrectedReference (mnId values, 0 after create / clear).
+ *
+ * orbg_map_propagate[_device] (:744-843 without the loop fusion): UpdateConnections(cur);
+ * mvpCurrentConnectedKFs = cur's ordered list followed by cur (d_set, its length in
+ * d_nset[0]; entries past it up to set_cap are -1); per member i NonCorrectedSim3 =
+ * Sim3(Riw, tiw, 1) and CorrectedSim3 = Sim3(Ric, tic, 1) * Scw, where Tic = Tiw * Twc is the
+ * float cv::Mat product (double sums over the four terms, one rounding), Sim3(R, t, 1) takes
+ * Eigen's Quaterniond(R) without normalisation and the product is g2o's in double;
+ * CorrectedSim3[cur] = Scw.  Both go to tables indexed by SLOT ([max_keyframes]; other entries
+ * are not written).  Then the map-point loop over CorrectedSim3 in slot order: a good point
+ * whose mnCorrectedByKF is not cur's mnId is moved by the LOWEST member slot that holds it,
+ * P = CorrectedSwi.map(Siw.map(P)) in double from the float position, rounded once; its
+ * mnCorrectedByKF becomes cur's mnId, its mnCorrectedReference that member's mnId, and its
+ * UpdateNormalAndDepth runs at that moment: for a point owned by member i an observing
+ * keyframe t contributes its corrected camera centre iff t is a member and t < i (its SetPose
+ * has run), else the centre it had; the reference keyframe's centre follows the same rule.
+ * Then SetPose([R(q) | t * (1 / s)]) and UpdateConnections per member.
+ * d_status [4]: [0] = ORBG_LOOP_* bits, [1] = the set's full length.  With a bit set only
+ * UpdateConnections(cur) has run, d_nset[0] = 0 and the tables are not written.  The host form
+ * returns ORBG_EINVAL for a cur that is not live or a member without a pose, ORBG_ERANGE for
+ * a set longer than set_cap, and then leaves its outputs untouched; ORBG_EINVAL for a slot out
+ * of range or a NULL pointer, ORBG_ENOTSUP for set_cap > ORBG_MAP_MAX_LOOP_SET.
+ *
+ * orbg_map_loop_connections[_device] (:882-911): for the members in VECTOR order, one after
+ * another: snapshot of the ordered list, UpdateConnections, then the non-zeros of the W row
+ * minus the snapshot minus the set.  The order matters: an earlier member's AddConnection can
+ * re-sort a later member's list over all its non-zero weights, the sub-threshold ones
+ * included, and those then drop out of that member's result.  d_pairs: (i, j) slot pairs,
+ * grouped by i in ascending slot, j ascending (the map-of-sets' iteration order); d_npairs[0]
+ * the full count, the first pair_cap pairs written.  A slot repeated in the set is processed
+ * each time and reported once, from its last entry.
+ *
+ * The device forms run on the context stream and never synchronise: the set's length stays on
+ * the device and the launches are sized by set_cap.  LoopConnections' workspace belongs to the
+ * map and is allocated by the first call. */
+#define ORBG_MAP_MAX_LOOP_EDGES 16
+#define ORBG_MAP_MAX_LOOP_SET 256
+#define ORBG_LOOP_NO_POSE 1
+#define ORBG_LOOP_SET_RANGE 2
+#define ORBG_LOOP_DEAD 4
+int orbg_map_set_keyframe_poses_device(orbg_ctx *ctx, orbg_map *map, const int32_t *d_slots, int n,
+                                       const float *d_Tcw, const int32_t *d_mnid);
+int orbg_map_set_keyframe_poses(orbg_ctx *ctx, orbg_map *map, const int32_t *slots, int n,
+                                const float *Tcw, const int32_t *mnid);
+/* slots first .. first + n - 1; any output may be NULL.  centres [n][3]: the stored Ow */
+int orbg_map_get_keyframe_poses(orbg_ctx *ctx, orbg_map *map, int first, int n, float *Tcw,
+                                int32_t *has_pose, int32_t *mnid, float *centres);
+int orbg_map_add_loop_edge(orbg_ctx *ctx, orbg_map *map, int a, int b);
+int orbg_map_get_loop_edges(orbg_ctx *ctx, orbg_map *map, int slot, int32_t *slots, int cap,
+                            int32_t *n);
+int orbg_map_get_point_corrected(orbg_ctx *ctx, orbg_map *map, int first, int n,
+                                 int32_t *corrected_by_kf, int32_t *corrected_reference);
+/* for a map uploaded from host state that carries earlier corrections */
+int orbg_map_set_point_corrected(orbg_ctx *ctx, orbg_map *map, int first, int n,
+                                 const int32_t *corrected_by_kf, const int32_t *corrected_reference);
+int orbg_map_propagate_device(orbg_ctx *ctx, orbg_map *map, int cur, const orbg_sim3d *d_Scw,
+                              int32_t *d_set, int set_cap, int32_t *d_nset,
+                              orbg_sim3d *d_corrected, orbg_sim3d *d_noncorrected,
+                              int32_t *d_status);
+int orbg_map_propagate(orbg_ctx *ctx, orbg_map *map, int cur, const orbg_sim3d *Scw, int32_t *set,
+                       int set_cap, int32_t *nset, orbg_sim3d *corrected,
+                       orbg_sim3d *noncorrected);
+int orbg_map_loop_connections_device(orbg_ctx *ctx, orbg_map *map, const int32_t *d_set,
+                                     int set_cap, const int32_t *d_nset, int32_t *d_pairs,
+                                     int pair_cap, int32_t *d_npairs);
+/* CorrectLoop's loop fusion (:848-863), keyframes attached: d_matched [n] is
+ * mvpCurrentMatchedPoints as ids (-1 = none), walked in feature order over the first min(n, N)
+ * features of cur.  A held point is Replace()d by the matched one (MapPoint::Replace's own
+ * returns apply: the same point, a matched point that is bad); a free feature takes the
+ * matched point unless cur already holds it (AddObservation returns then).  The descriptors
+ * of the matched points that were used are recomputed once when the call ends (the rule of
+ * orbg_map_replace_device).  d_counts [2]: replaced, added.
+ *
+ * SearchAndFuse (:944-992), keyframes attached: for the members of the set in SLOT order, one
+ * after another, Fuse(pKF, Scw, d_loop_points, th, vpReplacePoints) and then the Replace loop.
+ * The search is orbg_fuse_sim3_batch_device's kernel; its camera is d_cams[slot] with the
+ * member's corrected Sim3 as Tcw ([s R | t] rounded to float); its inputs are gathered from the
+ * map as orbg_map_fuse_device gathers them (a point in the row or a bad point is not valid).
+ * The update, in list order: a free feature takes the point; a good point on the feature is
+ * recorded; after the list the recorded points are Replace()d by their loop points, in order.
+ * A later member's search sees the rows and flags the earlier members left.  d_counts [2]: the
+ * sum of nFused, the replacements.  ORBG_EINVAL when nothing is attached.  set_cap sequences of
+ * launches are issued whatever the set's length: size set_cap tightly (LoopConnections too). */
+int orbg_map_loop_fusion_device(orbg_ctx *ctx, orbg_map *map, int cur, const int32_t *d_matched, int n,
+                                int32_t *d_counts);
+int orbg_map_loop_fusion(orbg_ctx *ctx, orbg_map *map, int cur, const int32_t *matched, int n,
+                         int32_t *counts);
+int orbg_map_search_and_fuse_device(orbg_ctx *ctx, orbg_map *map, const int32_t *d_set, int set_cap,
+                                    const int32_t *d_nset, const orbg_sim3d *d_corrected,
+                                    const int32_t *d_loop_points, int n, float th, int32_t *d_counts);
+int orbg_map_search_and_fuse(orbg_ctx *ctx, orbg_map *map, const int32_t *set, int nset,
+                             const orbg_sim3d *corrected, const int32_t *loop_points, int n, float th,
+                             int32_t *counts);
+/* host arrays; ORBG_ERANGE when there are more than pair_cap pairs */
+int orbg_map_loop_connections(orbg_ctx *ctx, orbg_map *map, const int32_t *set, int nset,
+                              int32_t *pairs, int pair_cap, int32_t *npairs);
+/* The walk of Optimizer::OptimizeEssentialGraph over the map (src/Optimizer.cc:1040-1258): the
+ * arrays orbg_eg_graph_create / orbg_eg_graph_optimize take.  Inputs: cur, loop, the two Sim3
+ * tables of Propagate with the set that says which of their entries exist, the LoopConnections
+ * pairs.  Vertices: the live, not-bad slots in ascending slot order (d_vert_slot [max_keyframes],
+ * d_nvert[0]); d_fixed[0] = loop's vertex.  d_Scw[v] = CorrectedSim3 of the slot where the set
+ * has it, else Sim3(Rcw, tcw, 1) of the stored pose; d_Snc[v] = NonCorrectedSim3 where the set
+ * has the slot, else d_Scw[v].  Edges {i, j, kind} with i the EdgeSim3's vertex 0, in the
+ * reference's order:
+ *  - kind 0: the pairs in their order; a pair is kept iff W[i][j] >= 100 or (mnId of i, mnId of
+ *    j) = (cur's, loop's); each kept pair enters sInsertedEdges as (min mnId, max mnId);
+ *  - kind 1, per vertex in slot order: the parent; the loop edges with a lower mnId, ascending
+ *    slot; then GetCovisiblesByWeight(100), which is the entries of the ordered list before the
+ *    first weight below 100 and, as in the reference (KeyFrame.cc:237-241), EMPTY when no
+ *    weight of the list is below 100: an entry gives an edge iff it is not the parent, not a
+ *    child (its parent is not this slot), not a loop edge, a vertex, has a lower mnId and the
+ *    pair is not in sInsertedEdges.
+ * The one departure: an edge whose other end is not a vertex (a parent or loop-edge keyframe
+ * that is dead or bad, a pair with such an end) is left out and counted in d_status[1]; the
+ * reference dereferences NULL there.  d_status[0]: ORBG_LOOP_DEAD when loop is no vertex,
+ * ORBG_LOOP_NO_POSE when a vertex outside the set has no pose (the host form: ORBG_EINVAL,
+ * outputs untouched).  d_nedge[0] is the full count, the first edge_cap edges are written (the
+ * host form: ORBG_ERANGE past edge_cap).  ORBG_EINVAL for cur / loop out of range, cur == loop,
+ * NULL pointers.  Counts are per vertex, scanned, then emitted: the order needs no atomics. */
+int orbg_map_essential_graph_device(orbg_ctx *ctx, orbg_map *map, int cur, int loop,
+                                    const orbg_sim3d *d_corrected, const orbg_sim3d *d_noncorrected,
+                                    const int32_t *d_set, int set_cap, const int32_t *d_nset,
+                                    const int32_t *d_pairs, int pair_cap, const int32_t *d_npairs,
+                                    int32_t *d_vert_slot, int32_t *d_nvert, int32_t *d_fixed,
+                                    orbg_sim3d *d_Scw, orbg_sim3d *d_Snc, orbg_eg_edge *d_edges,
+                                    int edge_cap, int32_t *d_nedge, int32_t *d_status);
+int orbg_map_essential_graph(orbg_ctx *ctx, orbg_map *map, int cur, int loop,
+                             const orbg_sim3d *corrected, const orbg_sim3d *noncorrected,
+                             const int32_t *set, int nset, const int32_t *pairs, int npairs,
+                             int32_t *vert_slot, int32_t *nvert, int32_t *fixed, orbg_sim3d *Scw,
+                             orbg_sim3d *Snc, orbg_eg_edge *edges, int edge_cap, int32_t *nedge,
+                             int32_t *nskipped);
+/* Optimizer.cc:1264-1323 with the optimiser's outputs (orbg_eg_graph_optimize's d_Siw_out /
+ * d_Tiw_out, vertex-indexed as d_vert_slot): SetPose(Tiw[v]) for every vertex; then every good
+ * point p moves to correctedSwr.map(Srw.map(P)) through orbg_eg_correct_points_device's
+ * kernel, Srw = d_Scw[r], correctedSwr = d_Siw[r]^-1, r the vertex of mnCorrectedReference's
+ * keyframe if mnCorrectedByKF is cur's mnId, else of the reference keyframe (a point whose r is
+ * no vertex stays); then UpdateNormalAndDepth of all points.  The workspace belongs to the map
+ * and is allocated by the first call. */
+int orbg_map_apply_correction_device(orbg_ctx *ctx, orbg_map *map, int cur,
+                                     const int32_t *d_vert_slot, const int32_t *d_nvert,
+                                     const orbg_sim3d *d_Scw, const orbg_sim3d *d_Siw,
+                                     const float *d_Tiw);
+int orbg_map_apply_correction(orbg_ctx *ctx, orbg_map *map, int cur, const int32_t *vert_slot,
+                              int nvert, const orbg_sim3d *Scw, const orbg_sim3d *Siw,
+                              const float *Tiw);
+/* LoopClosing::CorrectLoop from mg2oScw to the corrected poses and points in one host call,
+ * keyframes attached: Propagate, the loop fusion with `matched` (mvpCurrentMatchedPoints),
+ * SearchAndFuse with `loop_points` (mvpLoopMapPoints, th 4), LoopConnections, the essential
+ * graph, orbg_eg_graph_create / orbg_eg_graph_optimize (20 iterations), Apply and
+ * AddLoopEdge(loop, cur).  counts [8]: set members, fusion replaced / added, SearchAndFuse
+ * nFused / replaced, LoopConnections pairs, vertices, edges.  Errors as the stages'; a failure
+ * after Propagate leaves the map as that stage left it.  Synchronises; allocates and frees its
+ * own device workspace. */
+int orbg_map_correct_loop(orbg_ctx *ctx, orbg_map *map, int cur, int loop, const orbg_sim3d *Scw,
+                          const int32_t *matched, int nmatched, const int32_t *loop_points,
+                          int nloop, int fix_scale, orbg_lm_report *report, int32_t *counts);
+
 /* ---------------- GlobalBundleAdjustment (Optimizer::BundleAdjustment) ----------------
  * src/Optimizer.cc:105-320: every keyframe a VertexSE3Expmap (fixed iff mnId == 0), every map
  * point a marginalised VertexSBAPointXYZ, one EdgeSE3ProjectXYZ / EdgeStereoSE3ProjectXYZ per

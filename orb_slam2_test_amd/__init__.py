@@ -27,11 +27,12 @@ from .keyframedatabase import KeyFrameDatabase  # noqa: F401
 from .sim3solver import Sim3Solver  # noqa: F401
 from .pnpsolver import PnPsolver  # noqa: F401
 from .initializer import Initializer  # noqa: F401
-from .map import Map  # noqa: F401
+from .map import Map, MAX_LOOP_EDGES, MAX_LOOP_SET  # noqa: F401
 
 __all__ = ["ORBextractor", "ORBmatcher", "Frame", "MapPointProjections", "StereoFrame", "PoseOptimization", "linearize_local_ba", "OptimizeSim3", "OptimizeSim3Batch",
            "OptimizeEssentialGraph", "CorrectMapPoints", "EssentialGraph",
            "GlobalBundleAdjustment", "CorrectPointsGBA", "sparse_symbolic",
            "ORBVocabulary", "BowVector", "FeatureVector", "KeyFrameDatabase", "Sim3Solver", "PnPsolver", "Initializer", "Map",
+           "MAX_LOOP_EDGES", "MAX_LOOP_SET",
            "KP_DTYPE",
            "EDGE_DTYPE", "EDGE_OUT_DTYPE", "POSE_DTYPE"]

@@ -494,6 +494,29 @@ def lib():
         "orbg_map_search_in_neighbors_device": (i32, [vp, vp, i32, i32, i32, f32, vp, i32, vp, vp]),
         "orbg_map_search_in_neighbors": (i32, [vp, vp, i32, i32, i32, f32, vp, i32, P(C.c_int32),
                                                vp]),
+        "orbg_map_set_keyframe_poses_device": (i32, [vp, vp, vp, i32, vp, vp]),
+        "orbg_map_set_keyframe_poses": (i32, [vp, vp, vp, i32, vp, vp]),
+        "orbg_map_get_keyframe_poses": (i32, [vp, vp, i32, i32, vp, vp, vp, vp]),
+        "orbg_map_add_loop_edge": (i32, [vp, vp, i32, i32]),
+        "orbg_map_get_loop_edges": (i32, [vp, vp, i32, vp, i32, P(C.c_int32)]),
+        "orbg_map_get_point_corrected": (i32, [vp, vp, i32, i32, vp, vp]),
+        "orbg_map_propagate_device": (i32, [vp, vp, i32, vp, vp, i32, vp, vp, vp, vp]),
+        "orbg_map_propagate": (i32, [vp, vp, i32, vp, vp, i32, P(C.c_int32), vp, vp]),
+        "orbg_map_loop_connections_device": (i32, [vp, vp, vp, i32, vp, vp, i32, vp]),
+        "orbg_map_loop_connections": (i32, [vp, vp, vp, i32, vp, i32, P(C.c_int32)]),
+        "orbg_map_essential_graph_device": (i32, [vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp,
+                                                  vp, vp, vp, vp, vp, vp, i32, vp, vp]),
+        "orbg_map_essential_graph": (i32, [vp, vp, i32, i32, vp, vp, vp, i32, vp, i32, vp,
+                                           P(C.c_int32), P(C.c_int32), vp, vp, vp, i32,
+                                           P(C.c_int32), P(C.c_int32)]),
+        "orbg_map_apply_correction_device": (i32, [vp, vp, i32, vp, vp, vp, vp, vp]),
+        "orbg_map_apply_correction": (i32, [vp, vp, i32, vp, i32, vp, vp, vp]),
+        "orbg_map_set_point_corrected": (i32, [vp, vp, i32, i32, vp, vp]),
+        "orbg_map_loop_fusion_device": (i32, [vp, vp, i32, vp, i32, vp]),
+        "orbg_map_loop_fusion": (i32, [vp, vp, i32, vp, i32, vp]),
+        "orbg_map_search_and_fuse_device": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, f32, vp]),
+        "orbg_map_search_and_fuse": (i32, [vp, vp, vp, i32, vp, vp, i32, f32, vp]),
+        "orbg_map_correct_loop": (i32, [vp, vp, i32, i32, vp, vp, i32, vp, i32, i32, P(LmReport), vp]),
         "orbg_sim3_ransac_iterations": (i32, [C.c_double, i32, i32, i32]),
         "orbg_sim3_solve": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
         "orbg_sim3_solve_batch_device": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp,

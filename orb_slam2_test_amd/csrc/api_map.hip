@@ -1,6 +1,7 @@
 // api_map.hip -- orbg_map_*
 #include "orbg_ctx.h"
 #include "map_args.h"
+#include "essential_args.h"
 
 #pragma clang fp contract(off)
 
@@ -25,6 +26,8 @@ struct orbg_map {
     bool attached = false;
     MapEditWs W{};               // Fuse / SearchInNeighbors workspace, allocated at the first call
     void *d_ws = nullptr;
+    void *d_lc = nullptr;        // LoopConnections' rows [MAX_LOOP_SET][K] u16 and counts [MAX_LOOP_SET]
+    void *d_ap = nullptr;        // the correction's positions in and out [2][P][3] and vertices [P]
 };
 
 static int map_reset(orbg_map *m, hipStream_t st)
@@ -39,6 +42,7 @@ static int map_reset(orbg_map *m, hipStream_t st)
     HIPCHK(hipMemsetAsync(D.child_next, 0xFF, (size_t)D.K * 4, st));
     HIPCHK(hipMemsetAsync(D.mp_replaced, 0xFF, (size_t)D.P * 4, st));
     if (launch_map_point_defaults(st, D)) return set_err(ORBG_EIO, "k_map_point_defaults launch failed");
+    if (launch_map_loop_defaults(st, D)) return set_err(ORBG_EIO, "k_loop_defaults launch failed");
     m->dirty = m->tree_dirty = true;
     return ORBG_OK;
 }
@@ -76,6 +80,12 @@ extern "C" int orbg_map_create(orbg_ctx *c, int max_keyframes, int kf_cap, int m
     const size_t o_rp = L.take(P * 4), o_en = L.take(P * 4), o_et = L.take(P * 4);
     const size_t o_ec = L.take(P * 4), o_ei = L.take(P * 4), o_em = L.take(P * 4);
     const size_t o_ef = L.take(P * 4);
+    const size_t o_tc = L.take(K * 48), o_kp2 = L.take(K * 4), o_id = L.take(K * 4);
+    const size_t o_ln = L.take(K * 4), o_ls = L.take(K * ORBG_MAP_MAX_LOOP_EDGES * 4);
+    const size_t o_ck = L.take(P * 4), o_cr = L.take(P * 4);
+    const size_t o_lt = L.take(K * 48), o_lc = L.take(K * 12), o_lp = L.take(K * 4);
+    const size_t o_lh = L.take(64), o_sn = L.take(K * 2);
+    const size_t o_cs2 = L.take(P * 4), o_vm = L.take(K * 4), o_ec2 = L.take((K + 1) * 4);
     auto *m = new orbg_map();
     m->device = c->device;
     if (hipMalloc(&m->d_mem, L.total()) != hipSuccess) {
@@ -130,6 +140,21 @@ extern "C" int orbg_map_create(orbg_ctx *c, int max_keyframes, int kf_cap, int m
     D.ed_inkf = L.at<int32_t>(b, o_ei);
     D.ed_mark = L.at<int32_t>(b, o_em);
     D.ed_first = L.at<int32_t>(b, o_ef);
+    D.kf_Tcw = L.at<float>(b, o_tc);
+    D.kf_pose = L.at<int32_t>(b, o_kp2);
+    D.kf_mnid = L.at<int32_t>(b, o_id);
+    D.le_n = L.at<int32_t>(b, o_ln);
+    D.le_slot = L.at<int32_t>(b, o_ls);
+    D.mp_corr_kf = L.at<int32_t>(b, o_ck);
+    D.mp_corr_ref = L.at<int32_t>(b, o_cr);
+    D.lp_T = L.at<float>(b, o_lt);
+    D.lp_c = L.at<float>(b, o_lc);
+    D.lp_pos = L.at<int32_t>(b, o_lp);
+    D.lp_hdr = L.at<int32_t>(b, o_lh);
+    D.lp_snap = L.at<uint16_t>(b, o_sn);
+    D.mp_corr_slot = L.at<int32_t>(b, o_cs2);
+    D.lp_vmap = L.at<int32_t>(b, o_vm);
+    D.lp_ecnt = L.at<int32_t>(b, o_ec2);
     int rc = map_reset(m, c->stream);
     if (!rc && hipStreamSynchronize(c->stream) != hipSuccess)
         rc = set_err(ORBG_EIO, "Map: the initial clear failed");
@@ -149,6 +174,8 @@ extern "C" void orbg_map_destroy(orbg_map *m)
     hipSetDevice(m->device);
     if (m->d_cnt) hipFree(m->d_cnt);
     if (m->d_ws) hipFree(m->d_ws);
+    if (m->d_lc) hipFree(m->d_lc);
+    if (m->d_ap) hipFree(m->d_ap);
     if (m->d_mem) hipFree(m->d_mem);
     delete m;
 }
@@ -1258,5 +1285,606 @@ extern "C" int orbg_map_search_in_neighbors(orbg_ctx *c, orbg_map *m, int slot, 
     c->prof.collect();
     *ntargets = nt;
     if (nt > target_cap) return set_err(ORBG_ERANGE, "%d target entries (target_cap %d)", nt, target_cap);
+    return ORBG_OK;
+}
+
+// ---------------------------------------------------------------------------
+// LoopClosing::CorrectLoop on the Map (map_loop_kernels.hip)
+// ---------------------------------------------------------------------------
+extern "C" int orbg_map_set_keyframe_poses_device(orbg_ctx *c, orbg_map *m, const int32_t *d_slots,
+                                                  int n, const float *d_Tcw, const int32_t *d_mnid)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (n < 0) return set_err(ORBG_EINVAL, "negative size");
+    if (n == 0) return ORBG_OK;
+    if (!d_slots || (!d_Tcw && !d_mnid)) return set_err(ORBG_EINVAL, "NULL device array");
+    if (launch_map_set_poses(c->stream, m->D, d_slots, n, d_Tcw, d_mnid))
+        return set_err(ORBG_EIO, "k_loop_set_poses launch failed");
+    m->touched = true;
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_set_keyframe_poses(orbg_ctx *c, orbg_map *m, const int32_t *slots, int n,
+                                           const float *Tcw, const int32_t *mnid)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (n < 0) return set_err(ORBG_EINVAL, "negative size");
+    if (n == 0) return ORBG_OK;
+    if (!slots || (!Tcw && !mnid)) return set_err(ORBG_EINVAL, "NULL array");
+    for (int i = 0; i < n; i++)
+        if ((rc = map_slot_ok(m, slots[i]))) return rc;
+    Layout L;
+    const size_t o_s = L.take((size_t)n * 4), o_t = L.take((size_t)n * 48), o_i = L.take((size_t)n * 4);
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
+    HIPCHK(hipMemcpyAsync(b + o_s, slots, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    if (Tcw) HIPCHK(hipMemcpyAsync(b + o_t, Tcw, (size_t)n * 48, hipMemcpyHostToDevice, c->stream));
+    if (mnid) HIPCHK(hipMemcpyAsync(b + o_i, mnid, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    if ((rc = orbg_map_set_keyframe_poses_device(c, m, L.at<int32_t>(b, o_s), n,
+                                                 Tcw ? L.at<float>(b, o_t) : nullptr,
+                                                 mnid ? L.at<int32_t>(b, o_i) : nullptr)))
+        return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_get_keyframe_poses(orbg_ctx *c, orbg_map *m, int first, int n, float *Tcw,
+                                           int32_t *has_pose, int32_t *mnid, float *centres)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (n < 0 || first < 0 || (int64_t)first + n > m->D.K)
+        return set_err(ORBG_EINVAL, "slots %d .. %lld outside [0, %d)", first, (long long)first + n, m->D.K);
+    if (n == 0) return ORBG_OK;
+    const MapDev &D = m->D;
+    if (Tcw) HIPCHK(hipMemcpyAsync(Tcw, D.kf_Tcw + (size_t)first * 12, (size_t)n * 48, hipMemcpyDeviceToHost, c->stream));
+    if (has_pose) HIPCHK(hipMemcpyAsync(has_pose, D.kf_pose + first, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (mnid) HIPCHK(hipMemcpyAsync(mnid, D.kf_mnid + first, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (centres) HIPCHK(hipMemcpyAsync(centres, D.kf_centre + (size_t)first * 3, (size_t)n * 12, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_add_loop_edge(orbg_ctx *c, orbg_map *m, int a, int b)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_slot_ok(m, a)) || (rc = map_slot_ok(m, b))) return rc;
+    if (a == b) return set_err(ORBG_EINVAL, "a loop edge from slot %d to itself", a);
+    Layout L;
+    const size_t o_s = L.take(4);
+    uint8_t *d;
+    if ((rc = L.device(c, &d))) return rc;
+    if (launch_map_add_loop_edge(c->stream, m->D, a, b, L.at<int32_t>(d, o_s)))
+        return set_err(ORBG_EIO, "k_loop_add_edge launch failed");
+    m->touched = true;
+    int32_t st = 0;
+    HIPCHK(hipMemcpyAsync(&st, d + o_s, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (st) return set_err(ORBG_ERANGE, "more than %d loop edges at slot %d or %d", ORBG_MAP_MAX_LOOP_EDGES, a, b);
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_get_loop_edges(orbg_ctx *c, orbg_map *m, int slot, int32_t *slots, int cap,
+                                       int32_t *n)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_slot_ok(m, slot))) return rc;
+    if (cap < 0 || !n || (cap && !slots)) return set_err(ORBG_EINVAL, "bad cap / NULL array");
+    int32_t cnt = 0, e[ORBG_MAP_MAX_LOOP_EDGES];
+    HIPCHK(hipMemcpyAsync(&cnt, m->D.le_n + slot, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(e, m->D.le_slot + (size_t)slot * ORBG_MAP_MAX_LOOP_EDGES, sizeof(e),
+                          hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    std::sort(e, e + cnt);  // a std::set<KeyFrame*>: ascending slot
+    for (int i = 0; i < std::min(cnt, cap); i++) slots[i] = e[i];
+    *n = cnt;
+    if (cnt > cap) return set_err(ORBG_ERANGE, "%d loop edges (cap %d)", cnt, cap);
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_get_point_corrected(orbg_ctx *c, orbg_map *m, int first, int n,
+                                            int32_t *corrected_by_kf, int32_t *corrected_reference)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_range_ok(m, first, n))) return rc;
+    if (n == 0) return ORBG_OK;
+    if (!corrected_by_kf || !corrected_reference) return set_err(ORBG_EINVAL, "NULL array");
+    HIPCHK(hipMemcpyAsync(corrected_by_kf, m->D.mp_corr_kf + first, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(corrected_reference, m->D.mp_corr_ref + first, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_set_point_corrected(orbg_ctx *c, orbg_map *m, int first, int n,
+                                            const int32_t *corrected_by_kf,
+                                            const int32_t *corrected_reference)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_range_ok(m, first, n))) return rc;
+    if (n == 0) return ORBG_OK;
+    if (!corrected_by_kf || !corrected_reference) return set_err(ORBG_EINVAL, "NULL array");
+    Layout L;
+    const size_t o_a = L.take((size_t)n * 4), o_b = L.take((size_t)n * 4);
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
+    HIPCHK(hipMemcpyAsync(b + o_a, corrected_by_kf, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(b + o_b, corrected_reference, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    if (launch_map_set_corrected(c->stream, m->D, first, n, L.at<int32_t>(b, o_a), L.at<int32_t>(b, o_b)))
+        return set_err(ORBG_EIO, "k_loop_set_corrected launch failed");
+    m->touched = true;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return ORBG_OK;
+}
+
+static int map_set_cap_ok(const orbg_map *m, int set_cap)
+{
+    if (set_cap < 1) return set_err(ORBG_EINVAL, "set_cap < 1");
+    if (set_cap > ORBG_MAP_MAX_LOOP_SET)
+        return set_err(ORBG_ENOTSUP, "set_cap %d (> %d)", set_cap, ORBG_MAP_MAX_LOOP_SET);
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_propagate_device(orbg_ctx *c, orbg_map *m, int cur, const orbg_sim3d *d_Scw,
+                                         int32_t *d_set, int set_cap, int32_t *d_nset,
+                                         orbg_sim3d *d_corrected, orbg_sim3d *d_noncorrected,
+                                         int32_t *d_status)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_slot_ok(m, cur))) return rc;
+    if ((rc = map_set_cap_ok(m, set_cap))) return rc;
+    if (!d_Scw || !d_set || !d_nset || !d_corrected || !d_noncorrected || !d_status)
+        return set_err(ORBG_EINVAL, "NULL device array");
+    if ((rc = orbg_map_rebuild(c, m))) return rc;
+    MapScales S{};
+    S.nlevels = std::min(std::max(c->p.nlevels, 1), 16);
+    for (int i = 0; i < 16; i++) S.scale[i] = c->scale[i];
+    if ((rc = launch_map_propagate(c->stream, m->D, cur, d_Scw, d_set, set_cap, d_nset, d_corrected,
+                                   d_noncorrected, d_status, S, &m->epoch, &c->prof)))
+        return set_err(rc, "Propagate launch failed");
+    m->tree_dirty = m->touched = true;
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_propagate(orbg_ctx *c, orbg_map *m, int cur, const orbg_sim3d *Scw,
+                                  int32_t *set, int set_cap, int32_t *nset, orbg_sim3d *corrected,
+                                  orbg_sim3d *noncorrected)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_slot_ok(m, cur))) return rc;
+    if ((rc = map_set_cap_ok(m, set_cap))) return rc;
+    if (!Scw || !set || !nset || !corrected || !noncorrected) return set_err(ORBG_EINVAL, "NULL array");
+    const size_t K = (size_t)m->D.K;
+    Layout L;
+    const size_t o_s = L.take(sizeof(orbg_sim3d)), o_e = L.take((size_t)set_cap * 4), o_n = L.take(4);
+    const size_t o_c = L.take(K * sizeof(orbg_sim3d)), o_u = L.take(K * sizeof(orbg_sim3d));
+    const size_t o_st = L.take(16);
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
+    HIPCHK(hipMemcpyAsync(b + o_s, Scw, sizeof(orbg_sim3d), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(b + o_c, 0, K * sizeof(orbg_sim3d), c->stream));
+    HIPCHK(hipMemsetAsync(b + o_u, 0, K * sizeof(orbg_sim3d), c->stream));
+    if ((rc = orbg_map_propagate_device(c, m, cur, L.at<orbg_sim3d>(b, o_s), L.at<int32_t>(b, o_e),
+                                        set_cap, L.at<int32_t>(b, o_n), L.at<orbg_sim3d>(b, o_c),
+                                        L.at<orbg_sim3d>(b, o_u), L.at<int32_t>(b, o_st))))
+        return rc;
+    int32_t st[4] = {0, 0, 0, 0}, ns = 0;
+    HIPCHK(hipMemcpyAsync(st, b + o_st, 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&ns, b + o_n, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->prof.collect();
+    if (st[0] & ORBG_LOOP_DEAD) return set_err(ORBG_EINVAL, "Propagate: slot %d is not a live keyframe", cur);
+    if (st[0] & ORBG_LOOP_SET_RANGE)
+        return set_err(ORBG_ERANGE, "Propagate: %d connected keyframes (set_cap %d)", st[1], set_cap);
+    if (st[0] & ORBG_LOOP_NO_POSE)
+        return set_err(ORBG_EINVAL, "Propagate: a connected keyframe has no pose");
+    HIPCHK(hipMemcpy(set, b + o_e, (size_t)ns * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(corrected, b + o_c, K * sizeof(orbg_sim3d), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(noncorrected, b + o_u, K * sizeof(orbg_sim3d), hipMemcpyDeviceToHost));
+    *nset = ns;
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_loop_connections_device(orbg_ctx *c, orbg_map *m, const int32_t *d_set,
+                                                int set_cap, const int32_t *d_nset, int32_t *d_pairs,
+                                                int pair_cap, int32_t *d_npairs)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_set_cap_ok(m, set_cap))) return rc;
+    if (pair_cap < 0 || !d_set || !d_nset || !d_npairs || (pair_cap && !d_pairs))
+        return set_err(ORBG_EINVAL, "bad pair_cap / NULL device array");
+    const size_t K = (size_t)m->D.K, rows = ORBG_MAP_MAX_LOOP_SET * K * 2;
+    if (!m->d_lc) {
+        if (hipMalloc(&m->d_lc, rows + ORBG_MAP_MAX_LOOP_SET * 4) != hipSuccess) {
+            m->d_lc = nullptr;
+            return set_err(ORBG_ENOMEM, "LoopConnections: hipMalloc(%zu bytes)", rows + ORBG_MAP_MAX_LOOP_SET * 4);
+        }
+    }
+    if ((rc = orbg_map_rebuild(c, m))) return rc;
+    if ((rc = launch_map_loop_connections(c->stream, m->D, d_set, set_cap, d_nset, (uint16_t *)m->d_lc,
+                                          (int32_t *)((uint8_t *)m->d_lc + rows), d_pairs, pair_cap,
+                                          d_npairs, &m->epoch, &c->prof)))
+        return set_err(rc, "LoopConnections launch failed");
+    m->tree_dirty = m->touched = true;
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_loop_connections(orbg_ctx *c, orbg_map *m, const int32_t *set, int nset,
+                                         int32_t *pairs, int pair_cap, int32_t *npairs)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_set_cap_ok(m, nset))) return rc;
+    if (pair_cap < 0 || !set || !npairs || (pair_cap && !pairs))
+        return set_err(ORBG_EINVAL, "bad pair_cap / NULL array");
+    for (int i = 0; i < nset; i++)
+        if ((rc = map_slot_ok(m, set[i]))) return rc;
+    Layout L;
+    const size_t o_e = L.take((size_t)nset * 4), o_n = L.take(8), o_p = L.take((size_t)pair_cap * 8);
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
+    const int32_t hdr[2] = {nset, 0};
+    HIPCHK(hipMemcpyAsync(b + o_e, set, (size_t)nset * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(b + o_n, hdr, 8, hipMemcpyHostToDevice, c->stream));
+    int32_t *dn = L.at<int32_t>(b, o_n);
+    if ((rc = orbg_map_loop_connections_device(c, m, L.at<int32_t>(b, o_e), nset, dn,
+                                               L.at<int32_t>(b, o_p), pair_cap, dn + 1)))
+        return rc;
+    int32_t np = 0;
+    HIPCHK(hipMemcpyAsync(&np, dn + 1, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->prof.collect();
+    const int nw = std::min(np, pair_cap);
+    if (nw > 0) HIPCHK(hipMemcpy(pairs, b + o_p, (size_t)nw * 8, hipMemcpyDeviceToHost));
+    *npairs = np;
+    if (np > pair_cap) return set_err(ORBG_ERANGE, "%d LoopConnections pairs (pair_cap %d)", np, pair_cap);
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_essential_graph_device(orbg_ctx *c, orbg_map *m, int cur, int loop,
+                                               const orbg_sim3d *d_corrected,
+                                               const orbg_sim3d *d_noncorrected,
+                                               const int32_t *d_set, int set_cap,
+                                               const int32_t *d_nset, const int32_t *d_pairs,
+                                               int pair_cap, const int32_t *d_npairs,
+                                               int32_t *d_vert_slot, int32_t *d_nvert,
+                                               int32_t *d_fixed, orbg_sim3d *d_Scw, orbg_sim3d *d_Snc,
+                                               orbg_eg_edge *d_edges, int edge_cap, int32_t *d_nedge,
+                                               int32_t *d_status)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_slot_ok(m, cur)) || (rc = map_slot_ok(m, loop))) return rc;
+    if (cur == loop) return set_err(ORBG_EINVAL, "cur and loop are both slot %d", cur);
+    if ((rc = map_set_cap_ok(m, set_cap))) return rc;
+    if (pair_cap < 0 || edge_cap < 0) return set_err(ORBG_EINVAL, "negative size");
+    if (!d_corrected || !d_noncorrected || !d_set || !d_nset || !d_npairs || (pair_cap && !d_pairs) ||
+        !d_vert_slot || !d_nvert || !d_fixed || !d_Scw || !d_Snc || (edge_cap && !d_edges) ||
+        !d_nedge || !d_status)
+        return set_err(ORBG_EINVAL, "NULL device array");
+    if ((rc = launch_map_essential_graph(c->stream, m->D, cur, loop, d_corrected, d_noncorrected, d_set,
+                                         set_cap, d_nset, d_pairs, pair_cap, d_npairs, d_vert_slot,
+                                         d_nvert, d_fixed, d_Scw, d_Snc, d_edges, edge_cap, d_nedge,
+                                         d_status)))
+        return set_err(rc, "essential graph assembly launch failed");
+    m->touched = true;
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_essential_graph(orbg_ctx *c, orbg_map *m, int cur, int loop,
+                                        const orbg_sim3d *corrected, const orbg_sim3d *noncorrected,
+                                        const int32_t *set, int nset, const int32_t *pairs,
+                                        int npairs, int32_t *vert_slot, int32_t *nvert,
+                                        int32_t *fixed, orbg_sim3d *Scw, orbg_sim3d *Snc,
+                                        orbg_eg_edge *edges, int edge_cap, int32_t *nedge,
+                                        int32_t *nskipped)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_slot_ok(m, cur)) || (rc = map_slot_ok(m, loop))) return rc;
+    if (cur == loop) return set_err(ORBG_EINVAL, "cur and loop are both slot %d", cur);
+    if ((rc = map_set_cap_ok(m, nset))) return rc;
+    if (npairs < 0 || edge_cap < 0) return set_err(ORBG_EINVAL, "negative size");
+    if (!corrected || !noncorrected || !set || (npairs && !pairs) || !vert_slot || !nvert || !fixed ||
+        !Scw || !Snc || (edge_cap && !edges) || !nedge)
+        return set_err(ORBG_EINVAL, "NULL array");
+    for (int i = 0; i < nset; i++)
+        if ((rc = map_slot_ok(m, set[i]))) return rc;
+    const size_t K = (size_t)m->D.K, sb = K * sizeof(orbg_sim3d);
+    Layout L;
+    const size_t o_c = L.take(sb), o_u = L.take(sb), o_e = L.take((size_t)nset * 4);
+    const size_t o_p = L.take((size_t)npairs * 8), o_h = L.take(32);  // nset, npairs, nvert, fixed, nedge
+    const size_t o_v = L.take(K * 4), o_sc = L.take(sb), o_sn = L.take(sb);
+    const size_t o_ed = L.take((size_t)edge_cap * sizeof(orbg_eg_edge)), o_st = L.take(16);
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
+    const int32_t hdr[8] = {nset, npairs, 0, -1, 0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(b + o_c, corrected, sb, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(b + o_u, noncorrected, sb, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(b + o_e, set, (size_t)nset * 4, hipMemcpyHostToDevice, c->stream));
+    if (npairs) HIPCHK(hipMemcpyAsync(b + o_p, pairs, (size_t)npairs * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(b + o_h, hdr, 32, hipMemcpyHostToDevice, c->stream));
+    int32_t *h = L.at<int32_t>(b, o_h);
+    if ((rc = orbg_map_essential_graph_device(
+             c, m, cur, loop, L.at<orbg_sim3d>(b, o_c), L.at<orbg_sim3d>(b, o_u), L.at<int32_t>(b, o_e),
+             nset, h, L.at<int32_t>(b, o_p), npairs, h + 1, L.at<int32_t>(b, o_v), h + 2, h + 3,
+             L.at<orbg_sim3d>(b, o_sc), L.at<orbg_sim3d>(b, o_sn), L.at<orbg_eg_edge>(b, o_ed), edge_cap,
+             h + 4, L.at<int32_t>(b, o_st))))
+        return rc;
+    int32_t out[8], st[4];
+    HIPCHK(hipMemcpyAsync(out, h, 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(st, b + o_st, 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (st[0] & ORBG_LOOP_DEAD) return set_err(ORBG_EINVAL, "essential graph: slot %d (loop) is not a vertex", loop);
+    if (st[0] & ORBG_LOOP_NO_POSE) return set_err(ORBG_EINVAL, "essential graph: a keyframe has no pose");
+    const int nv = out[2], ne = std::min(out[4], edge_cap);
+    HIPCHK(hipMemcpy(vert_slot, b + o_v, (size_t)nv * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(Scw, b + o_sc, (size_t)nv * sizeof(orbg_sim3d), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(Snc, b + o_sn, (size_t)nv * sizeof(orbg_sim3d), hipMemcpyDeviceToHost));
+    if (ne > 0) HIPCHK(hipMemcpy(edges, b + o_ed, (size_t)ne * sizeof(orbg_eg_edge), hipMemcpyDeviceToHost));
+    *nvert = nv;
+    *fixed = out[3];
+    *nedge = out[4];
+    if (nskipped) *nskipped = st[1];
+    if (out[4] > edge_cap) return set_err(ORBG_ERANGE, "%d edges (edge_cap %d)", out[4], edge_cap);
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_apply_correction_device(orbg_ctx *c, orbg_map *m, int cur,
+                                                const int32_t *d_vert_slot, const int32_t *d_nvert,
+                                                const orbg_sim3d *d_Scw, const orbg_sim3d *d_Siw,
+                                                const float *d_Tiw)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_slot_ok(m, cur))) return rc;
+    if (!d_vert_slot || !d_nvert || !d_Scw || !d_Siw || !d_Tiw) return set_err(ORBG_EINVAL, "NULL device array");
+    const size_t P = (size_t)m->D.P;
+    if (!m->d_ap && hipMalloc(&m->d_ap, P * 28) != hipSuccess) {
+        m->d_ap = nullptr;
+        return set_err(ORBG_ENOMEM, "apply correction: hipMalloc(%zu bytes)", P * 28);
+    }
+    float *pts = (float *)m->d_ap, *moved = pts + P * 3;
+    int32_t *ref = (int32_t *)((uint8_t *)m->d_ap + P * 24);
+    if (launch_map_apply_poses(c->stream, m->D, cur, d_vert_slot, d_nvert, d_Tiw, pts, ref))
+        return set_err(ORBG_EIO, "k_apply_poses launch failed");
+    m->touched = true;
+    if (launch_eg_correct_points(c->stream, (const Sim3d *)d_Scw, (const Sim3d *)d_Siw, m->D.K, ref, pts,
+                                 m->D.P, moved))
+        return set_err(ORBG_EIO, "k_eg_correct_points launch failed");
+    if (launch_map_scatter_points(c->stream, m->D, moved, ref))
+        return set_err(ORBG_EIO, "k_apply_scatter launch failed");
+    return orbg_map_update_normal_and_depth_batch_device(c, m, nullptr, m->D.P);
+}
+
+extern "C" int orbg_map_apply_correction(orbg_ctx *c, orbg_map *m, int cur, const int32_t *vert_slot,
+                                         int nvert, const orbg_sim3d *Scw, const orbg_sim3d *Siw,
+                                         const float *Tiw)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_slot_ok(m, cur))) return rc;
+    if (nvert < 1 || nvert > m->D.K) return set_err(ORBG_EINVAL, "nvert %d outside [1, %d]", nvert, m->D.K);
+    if (!vert_slot || !Scw || !Siw || !Tiw) return set_err(ORBG_EINVAL, "NULL array");
+    for (int i = 0; i < nvert; i++)
+        if ((rc = map_slot_ok(m, vert_slot[i]))) return rc;
+    const size_t n = (size_t)nvert, sb = n * sizeof(orbg_sim3d);
+    Layout L;
+    const size_t o_v = L.take(n * 4), o_n = L.take(4), o_c = L.take(sb), o_s = L.take(sb);
+    const size_t o_t = L.take(n * 48);
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
+    const int32_t nv = nvert;
+    HIPCHK(hipMemcpyAsync(b + o_v, vert_slot, n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(b + o_n, &nv, 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(b + o_c, Scw, sb, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(b + o_s, Siw, sb, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(b + o_t, Tiw, n * 48, hipMemcpyHostToDevice, c->stream));
+    if ((rc = orbg_map_apply_correction_device(c, m, cur, L.at<int32_t>(b, o_v), L.at<int32_t>(b, o_n),
+                                               L.at<orbg_sim3d>(b, o_c), L.at<orbg_sim3d>(b, o_s),
+                                               L.at<float>(b, o_t))))
+        return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->prof.collect();
+    return ORBG_OK;
+}
+
+// ---- the loop fusion (:848-863) and SearchAndFuse (:944-992) ----
+extern "C" int orbg_map_loop_fusion_device(orbg_ctx *c, orbg_map *m, int cur, const int32_t *d_matched,
+                                           int n, int32_t *d_counts)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_slot_ok(m, cur))) return rc;
+    if (n < 0) return set_err(ORBG_EINVAL, "negative size");
+    if ((rc = map_attached(m))) return rc;
+    if (!d_counts || (n && !d_matched)) return set_err(ORBG_EINVAL, "NULL device array");
+    if ((rc = map_edit_ws(c, m, m->D.cap))) return rc;
+    if ((rc = orbg_map_rebuild(c, m))) return rc;
+    if (launch_map_loop_fusion(c->stream, m->D, cur, d_matched, n, ++m->epoch, m->W.surv, d_counts))
+        return set_err(ORBG_EIO, "k_loop_fusion launch failed");
+    m->dirty = m->touched = true;
+    return map_distinctive(c, m, m->W.surv, m->D.cap, nullptr);
+}
+
+extern "C" int orbg_map_loop_fusion(orbg_ctx *c, orbg_map *m, int cur, const int32_t *matched, int n,
+                                    int32_t *counts)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (n < 0 || !counts || (n && !matched)) return set_err(ORBG_EINVAL, "negative size / NULL array");
+    Layout L;
+    const size_t o_m = L.take((size_t)n * 4), o_c = L.take(8);
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
+    if (n) HIPCHK(hipMemcpyAsync(b + o_m, matched, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    if ((rc = orbg_map_loop_fusion_device(c, m, cur, L.at<int32_t>(b, o_m), n, L.at<int32_t>(b, o_c))))
+        return rc;
+    HIPCHK(hipMemcpyAsync(counts, b + o_c, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->prof.collect();
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_search_and_fuse_device(orbg_ctx *c, orbg_map *m, const int32_t *d_set,
+                                               int set_cap, const int32_t *d_nset,
+                                               const orbg_sim3d *d_corrected,
+                                               const int32_t *d_loop_points, int n, float th,
+                                               int32_t *d_counts)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_set_cap_ok(m, set_cap))) return rc;
+    if (n < 0) return set_err(ORBG_EINVAL, "negative size");
+    if ((rc = map_attached(m))) return rc;
+    if (!d_set || !d_nset || !d_corrected || !d_counts || (n && !d_loop_points))
+        return set_err(ORBG_EINVAL, "NULL device array");
+    HIPCHK(hipMemsetAsync(d_counts, 0, 8, c->stream));
+    m->touched = true;
+    if (n == 0) return ORBG_OK;
+    if ((rc = map_edit_ws(c, m, n))) return rc;
+    const MapEditWs &W = m->W;
+    hipStream_t st = c->stream;
+    for (int r = 0; r < set_cap; r++) {  // the members in slot order, one after another
+        if ((rc = orbg_map_rebuild(c, m))) return rc;
+        if (launch_map_sf_job(st, m->D, m->att, W, d_set, set_cap, d_nset, r, d_corrected, n) ||
+            launch_map_fuse_gather(st, m->D, W, d_loop_points, n))
+            return set_err(ORBG_EIO, "k_sf_job launch failed");
+        rc = launch_fuse(st, m->att.kfs, m->att.cap, W.hdr + MAP_HDR_SLOT, W.cam, W.mps, W.mdesc,
+                         W.hdr + MAP_HDR_N, W.ncap, 1, th, c->scale, c->inv_sigma2, c->p.nlevels, 1,
+                         W.bidx, W.bdist, W.hdr + MAP_HDR_SEARCH, c->d_err);
+        if (rc == -95) return set_err(ORBG_ENOTSUP, "Fuse: more than 8192 keypoints per KeyFrame");
+        if (rc) return set_err(ORBG_EIO, "k_fuse launch failed");
+        if (launch_map_sf_update(st, m->D, W, d_loop_points, n, ++m->epoch, d_counts))
+            return set_err(ORBG_EIO, "k_sf_update launch failed");
+        m->dirty = true;
+        if ((rc = map_distinctive(c, m, W.surv, n, W.hdr + MAP_HDR_N))) return rc;
+    }
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_search_and_fuse(orbg_ctx *c, orbg_map *m, const int32_t *set, int nset,
+                                        const orbg_sim3d *corrected, const int32_t *loop_points,
+                                        int n, float th, int32_t *counts)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_set_cap_ok(m, nset))) return rc;
+    if (n < 0 || !set || !corrected || !counts || (n && !loop_points))
+        return set_err(ORBG_EINVAL, "negative size / NULL array");
+    if ((rc = map_attached(m))) return rc;
+    for (int i = 0; i < nset; i++)
+        if ((rc = map_slot_ok(m, set[i]))) return rc;
+    const size_t sb = (size_t)m->D.K * sizeof(orbg_sim3d);
+    Layout L;
+    const size_t o_e = L.take((size_t)nset * 4), o_n = L.take(4), o_c = L.take(sb);
+    const size_t o_p = L.take((size_t)n * 4), o_o = L.take(8);
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
+    const int32_t ns = nset;
+    HIPCHK(hipMemcpyAsync(b + o_e, set, (size_t)nset * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(b + o_n, &ns, 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(b + o_c, corrected, sb, hipMemcpyHostToDevice, c->stream));
+    if (n) HIPCHK(hipMemcpyAsync(b + o_p, loop_points, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    if ((rc = orbg_map_search_and_fuse_device(c, m, L.at<int32_t>(b, o_e), nset, L.at<int32_t>(b, o_n),
+                                              L.at<orbg_sim3d>(b, o_c), L.at<int32_t>(b, o_p), n, th,
+                                              L.at<int32_t>(b, o_o))))
+        return rc;
+    HIPCHK(hipMemcpyAsync(counts, b + o_o, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->prof.collect();
+    return ORBG_OK;
+}
+
+// ---- CorrectLoop in one call ----
+extern "C" int orbg_map_correct_loop(orbg_ctx *c, orbg_map *m, int cur, int loop, const orbg_sim3d *Scw,
+                                     const int32_t *matched, int nmatched, const int32_t *loop_points,
+                                     int nloop, int fix_scale, orbg_lm_report *report, int32_t *counts)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_slot_ok(m, cur)) || (rc = map_slot_ok(m, loop))) return rc;
+    if (cur == loop) return set_err(ORBG_EINVAL, "cur and loop are both slot %d", cur);
+    if (nmatched < 0 || nloop < 0 || !Scw || !report || !counts || (nmatched && !matched) ||
+        (nloop && !loop_points))
+        return set_err(ORBG_EINVAL, "negative size / NULL array");
+    if ((rc = map_attached(m))) return rc;
+    const size_t K = (size_t)m->D.K, sb = K * sizeof(orbg_sim3d);
+    const int set_cap = (int)std::min<size_t>(K, ORBG_MAP_MAX_LOOP_SET);
+    const int pair_cap = (int)std::min<size_t>((size_t)set_cap * K, 1u << 20);
+    const int edge_cap = (int)std::min<size_t>(K * 64, 1u << 22);
+    Layout L;
+    const size_t o_s = L.take(sizeof(orbg_sim3d)), o_m = L.take((size_t)nmatched * 4);
+    const size_t o_l = L.take((size_t)nloop * 4), o_e = L.take((size_t)set_cap * 4), o_h = L.take(128);
+    const size_t o_c = L.take(sb), o_u = L.take(sb), o_p = L.take((size_t)pair_cap * 8);
+    const size_t o_v = L.take(K * 4), o_sc = L.take(sb), o_sn = L.take(sb), o_si = L.take(sb);
+    const size_t o_t = L.take(K * 48), o_ed = L.take((size_t)edge_cap * sizeof(orbg_eg_edge));
+    uint8_t *b = nullptr;
+    if (hipMalloc((void **)&b, L.total()) != hipSuccess)
+        return set_err(ORBG_ENOMEM, "CorrectLoop: hipMalloc(%zu bytes)", L.total());
+    // h: 0 nset, 1 npairs, 2 nvert, 3 fixed, 4 nedge, 8.. propagate status, 12.. graph status,
+    //    16.. fusion counts, 18.. SearchAndFuse counts
+    int32_t *h = L.at<int32_t>(b, o_h);
+    orbg_sim3d *dc = L.at<orbg_sim3d>(b, o_c), *du = L.at<orbg_sim3d>(b, o_u);
+    int32_t *dset = L.at<int32_t>(b, o_e), *dp = L.at<int32_t>(b, o_p), *dv = L.at<int32_t>(b, o_v);
+    orbg_eg_graph *g = nullptr;
+    std::vector<orbg_eg_edge> edges;
+    int32_t hh[32] = {0};
+    auto body = [&]() -> int {
+        int r;
+        HIPCHK(hipMemsetAsync(b, 0, o_p, c->stream));
+        HIPCHK(hipMemcpyAsync(b + o_s, Scw, sizeof(orbg_sim3d), hipMemcpyHostToDevice, c->stream));
+        if (nmatched) HIPCHK(hipMemcpyAsync(b + o_m, matched, (size_t)nmatched * 4, hipMemcpyHostToDevice, c->stream));
+        if (nloop) HIPCHK(hipMemcpyAsync(b + o_l, loop_points, (size_t)nloop * 4, hipMemcpyHostToDevice, c->stream));
+        if ((r = orbg_map_propagate_device(c, m, cur, L.at<orbg_sim3d>(b, o_s), dset, set_cap, h, dc, du, h + 8))) return r;
+        HIPCHK(hipMemcpyAsync(hh + 8, h + 8, 16, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (hh[8] & ORBG_LOOP_DEAD) return set_err(ORBG_EINVAL, "CorrectLoop: slot %d is not a live keyframe", cur);
+        if (hh[8] & ORBG_LOOP_SET_RANGE) return set_err(ORBG_ERANGE, "CorrectLoop: %d connected keyframes (at most %d)", hh[9], set_cap);
+        if (hh[8] & ORBG_LOOP_NO_POSE) return set_err(ORBG_EINVAL, "CorrectLoop: a connected keyframe has no pose");
+        if ((r = orbg_map_loop_fusion_device(c, m, cur, L.at<int32_t>(b, o_m), nmatched, h + 16))) return r;
+        if ((r = orbg_map_search_and_fuse_device(c, m, dset, set_cap, h, dc, L.at<int32_t>(b, o_l), nloop, 4.0f, h + 18))) return r;
+        if ((r = orbg_map_loop_connections_device(c, m, dset, set_cap, h, dp, pair_cap, h + 1))) return r;
+        HIPCHK(hipMemcpyAsync(hh, h, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (hh[1] > pair_cap) return set_err(ORBG_ERANGE, "CorrectLoop: %d LoopConnections pairs (at most %d)", hh[1], pair_cap);
+        if ((r = orbg_map_essential_graph_device(c, m, cur, loop, dc, du, dset, set_cap, h, dp, pair_cap, h + 1, dv, h + 2,
+                                                 h + 3, L.at<orbg_sim3d>(b, o_sc), L.at<orbg_sim3d>(b, o_sn),
+                                                 L.at<orbg_eg_edge>(b, o_ed), edge_cap, h + 4, h + 12)))
+            return r;
+        HIPCHK(hipMemcpyAsync(hh, h, 128, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (hh[12] & ORBG_LOOP_DEAD) return set_err(ORBG_EINVAL, "CorrectLoop: slot %d (loop) is not a vertex", loop);
+        if (hh[12] & ORBG_LOOP_NO_POSE) return set_err(ORBG_EINVAL, "CorrectLoop: a keyframe has no pose");
+        if (hh[4] > edge_cap) return set_err(ORBG_ERANGE, "CorrectLoop: %d edges (at most %d)", hh[4], edge_cap);
+        edges.resize((size_t)std::max(hh[4], 1));
+        if (hh[4]) HIPCHK(hipMemcpy(edges.data(), b + o_ed, (size_t)hh[4] * sizeof(orbg_eg_edge), hipMemcpyDeviceToHost));
+        if ((r = orbg_eg_graph_create(c, edges.data(), hh[4], hh[2], hh[3], &g))) return r;
+        if ((r = orbg_eg_graph_optimize(c, g, L.at<orbg_sim3d>(b, o_sc), L.at<orbg_sim3d>(b, o_sn), fix_scale, 20,
+                                        L.at<orbg_sim3d>(b, o_si), L.at<float>(b, o_t), report)))
+            return r;
+        if ((r = orbg_map_apply_correction_device(c, m, cur, dv, h + 2, L.at<orbg_sim3d>(b, o_sc),
+                                                  L.at<orbg_sim3d>(b, o_si), L.at<float>(b, o_t))))
+            return r;
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return ORBG_OK;
+    };
+    rc = body();
+    if (g) orbg_eg_graph_destroy(g);
+    hipStreamSynchronize(c->stream);
+    hipFree(b);
+    if (rc) return rc;
+    if ((rc = orbg_map_add_loop_edge(c, m, loop, cur))) return rc;
+    const int32_t out[8] = {hh[0], hh[16], hh[17], hh[18], hh[19], hh[1], hh[2], hh[4]};
+    for (int i = 0; i < 8; i++) counts[i] = out[i];
+    c->prof.collect();
     return ORBG_OK;
 }

@@ -1,6 +1,7 @@
 // map_args.h -- device layout and launch arguments of the covisibility Map (map_kernels.hip:
 // KeyFrame::UpdateConnections, Tracking::UpdateLocalKeyFrames / UpdateLocalPoints,
-// MapPoint::UpdateNormalAndDepth; map_cull_kernels.hip; map_edit_kernels.hip), shared with the
+// MapPoint::UpdateNormalAndDepth; map_cull_kernels.hip; map_edit_kernels.hip;
+// map_loop_kernels.hip), shared with the
 // host entry points (api_map.hip).
 #pragma once
 
@@ -72,7 +73,29 @@ struct MapDev {
     int32_t *ed_inkf;           // [P] stamp: the point entered the Fuse keyframe's row in this call
     int32_t *ed_mark;           // [P] stamp: the point is already listed for its descriptor
     int32_t *ed_first;          // [P] SearchInNeighbors: first position of a fuse candidate
+    // map_loop_kernels.hip: what LoopClosing::CorrectLoop reads beside the table
+    float *kf_Tcw;              // [K][12] GetPose(), 3x4 row-major
+    int32_t *kf_pose;           // [K] 1 = the slot has a pose
+    int32_t *kf_mnid;           // [K] mnId, the slot by default
+    int32_t *le_n;              // [K] mspLoopEdges
+    int32_t *le_slot;           // [K][ORBG_MAP_MAX_LOOP_EDGES] in arrival order
+    int32_t *mp_corr_kf;        // [P] mnCorrectedByKF
+    int32_t *mp_corr_ref;       // [P] mnCorrectedReference
+    float *lp_T, *lp_c;         // [K][12], [K][3] the corrected poses / centres of a running Propagate
+    int32_t *lp_pos;            // [K] position in mvpCurrentConnectedKFs, -1 = not a member
+    int32_t *lp_hdr;            // [16] LOOP_HDR_*
+    uint16_t *lp_snap;          // [K] LoopConnections: vpPreviousNeighbors
+    int32_t *mp_corr_slot;      // [P] the slot Propagate wrote mnCorrectedReference for (a hint: checked against kf_mnid)
+    int32_t *lp_vmap;           // [K] essential graph: slot -> vertex, -1 = none
+    int32_t *lp_ecnt;           // [K + 1] its kind-1 edges per vertex, then their offsets
 };
+#define LOOP_HDR_SLOT 0               // the slot of the running UpdateConnections, -1 = none
+#define LOOP_HDR_NSET 1               // members the running call acts on
+#define LOOP_HDR_NSNAP 3
+#define LOOP_HDR_NVERT 4
+#define LOOP_HDR_N0 5                 // kept kind-0 edges
+#define LOOP_HDR_SKIP 6               // edges left out: an end is not a vertex
+#define LOOP_HDR_BITS 7               // ORBG_LOOP_* of the running assembly
 
 struct MapScales {
     float scale[16];
@@ -176,10 +199,50 @@ int launch_map_fuse_gather(hipStream_t st, const MapDev &M, const MapEditWs &W, 
 int launch_map_fuse_update(hipStream_t st, const MapDev &M, const MapEditWs &W, const int32_t *ids,
                            int nmax, int epoch, int32_t *best_idx, int32_t *best_dist,
                            int32_t *status, int32_t *nfused, int nfused_at_ntargets);
+// CorrectLoop's loop fusion and SearchAndFuse (map_edit_kernels.hip); surv [M.cap], counts [2]
+int launch_map_loop_fusion(hipStream_t st, const MapDev &M, int cur, const int32_t *matched, int nm,
+                           int epoch, int32_t *surv, int32_t *counts);
+int launch_map_sf_job(hipStream_t st, const MapDev &M, const MapAttach &A, const MapEditWs &W,
+                      const int32_t *set, int set_cap, const int32_t *nset, int rank,
+                      const orbg_sim3d *corrected, int n);
+int launch_map_sf_update(hipStream_t st, const MapDev &M, const MapEditWs &W, const int32_t *ids,
+                         int nmax, int epoch, int32_t *counts);
 int launch_map_sin_targets(hipStream_t st, const MapDev &M, const MapEditWs &W, int slot,
                            int current_kf_id, int monocular, int32_t *targets, int target_cap,
                            int32_t *ntargets, int32_t *nfused);
 int launch_map_sin_candidates(hipStream_t st, const MapDev &M, const MapEditWs &W);
 int launch_map_sin_row(hipStream_t st, const MapDev &M, const MapEditWs &W, int slot);
+
+
+// map_loop_kernels.hip
+int launch_map_loop_defaults(hipStream_t st, const MapDev &M);
+int launch_map_set_poses(hipStream_t st, const MapDev &M, const int32_t *slots, int n,
+                         const float *Tcw, const int32_t *mnid);
+int launch_map_add_loop_edge(hipStream_t st, const MapDev &M, int a, int b, int32_t *status);
+// UpdateConnections(cur), the set and the two Sim3 tables; then the map-point loop, SetPose and
+// UpdateConnections per member.  status [4]: bits, the set's full length
+int launch_map_propagate(hipStream_t st, const MapDev &M, int cur, const orbg_sim3d *Scw,
+                         int32_t *set, int set_cap, int32_t *nset, orbg_sim3d *corrected,
+                         orbg_sim3d *noncorrected, int32_t *status, const MapScales &S,
+                         int *epoch, Prof *prof);
+// rows [set_cap][K] / cnt [set_cap]: each member's new connections, the caller's workspace
+int launch_map_loop_connections(hipStream_t st, const MapDev &M, const int32_t *set, int set_cap,
+                                const int32_t *nset, uint16_t *rows, int32_t *cnt, int32_t *pairs,
+                                int pair_cap, int32_t *npairs, int *epoch, Prof *prof);
+// Optimizer.cc:1040-1258 on the map: vertices, Scw / Snc per vertex, the edge list in the
+// reference's order.  status [4]: ORBG_LOOP_* bits, the edges left out because an end is no vertex
+int launch_map_essential_graph(hipStream_t st, const MapDev &M, int cur, int loop,
+                               const orbg_sim3d *corrected, const orbg_sim3d *noncorrected,
+                               const int32_t *set, int set_cap, const int32_t *nset,
+                               const int32_t *pairs, int pair_cap, const int32_t *npairs,
+                               int32_t *vert_slot, int32_t *nvert, int32_t *fixed, orbg_sim3d *Scw,
+                               orbg_sim3d *Snc, orbg_eg_edge *edges, int edge_cap, int32_t *nedge,
+                               int32_t *status);
+// :1264-1323: SetPose per vertex, ref[p] and the gathered positions (pts [P][3], ref [P])
+int launch_map_apply_poses(hipStream_t st, const MapDev &M, int cur, const int32_t *vert_slot,
+                           const int32_t *nvert, const float *Tiw, float *pts, int32_t *ref);
+int launch_map_set_corrected(hipStream_t st, const MapDev &M, int first, int n, const int32_t *by,
+                             const int32_t *ref);
+int launch_map_scatter_points(hipStream_t st, const MapDev &M, const float *pts, const int32_t *ref);
 
 }  // namespace orbg

@@ -3,7 +3,8 @@
 // MapPoint::Replace (:253-303), MapPoint::ComputeDistinctiveDescriptors over the map's own
 // observations (:342-425), the map update of ORBmatcher::Fuse (src/ORBmatcher.cc:1100-1125)
 // around the existing search kernel (k_fuse, mapping_kernels.hip) and the lists of
-// LocalMapping::SearchInNeighbors (src/LocalMapping.cc:583-683).
+// LocalMapping::SearchInNeighbors (src/LocalMapping.cc:583-683), and LoopClosing::CorrectLoop's
+// loop fusion and SearchAndFuse (src/LoopClosing.cc:848-863, 944-992).
 //
 // Inside one call a surviving point gains observations, so the point -> observations index
 // built before the call is no superset of a survivor's observers.  The rows are the truth; the
@@ -86,16 +87,17 @@ __device__ __forceinline__ void edit_chain_init(const MapDev &M, int x, int epoc
 
 // o->Replace(w) by the whole workgroup; o != w, both in range, w good.  Barriers inside; the
 // caller's reads of o's and w's state precede the call.
-__device__ void edit_replace(const MapDev &M, int o, int w, int ex_u, int ex_j, int epoch,
-                             int guard, uint32_t *bm, bool was_bad)
+// (exw_u, exw_j) / (exo_u, exo_j): the observation of w / of o that no index segment may hold
+__device__ void edit_replace2(const MapDev &M, int o, int w, int exw_u, int exw_j, int exo_u,
+                              int exo_j, int epoch, int guard, uint32_t *bm, bool was_bad)
 {
     if (!was_bad) {
         for (int k = threadIdx.x; k < (M.K + 31) / 32; k += MAP_T) bm[k] = 0;
         __syncthreads();
-        edit_walk(M, w, epoch, guard, ex_u, ex_j,
+        edit_walk(M, w, epoch, guard, exw_u, exw_j,
                   [&](int u, int) { atomicOr(&bm[u >> 5], 1u << (u & 31)); });
         __syncthreads();
-        edit_walk(M, o, epoch, guard, ex_u, ex_j, [&](int u, int j) {
+        edit_walk(M, o, epoch, guard, exo_u, exo_j, [&](int u, int j) {
             // pMP->IsInKeyFrame(pKF): EraseMapPointMatch, else ReplaceMapPointMatch + AddObservation
             M.kf_points[(size_t)u * M.cap + j] = (bm[u >> 5] >> (u & 31) & 1u) ? -1 : w;
         });
@@ -114,6 +116,38 @@ __device__ void edit_replace(const MapDev &M, int o, int w, int ex_u, int ex_j, 
         M.mp_visible[w] += M.mp_visible[o];
     }
     __syncthreads();
+}
+
+__device__ __forceinline__ void edit_replace(const MapDev &M, int o, int w, int ex_u, int ex_j,
+                                             int epoch, int guard, uint32_t *bm, bool was_bad)
+{
+    edit_replace2(M, o, w, ex_u, ex_j, ex_u, ex_j, epoch, guard, bm, was_bad);
+}
+
+// the feature of slot s that holds x, or -1, by the whole workgroup (barriers inside); sh: LDS
+__device__ __forceinline__ int edit_find(const MapDev &M, int s, int x, int nrow, int *sh)
+{
+    __syncthreads();
+    if (threadIdx.x == 0) *sh = -1;
+    __syncthreads();
+    for (int k = threadIdx.x; k < nrow; k += MAP_T)
+        if (M.kf_points[(size_t)s * M.cap + k] == x) *sh = k;  // at most one
+    __syncthreads();
+    return *sh;
+}
+
+// old->Replace(w) with MapPoint::Replace's early returns, both possibly seen by slot s through
+// an observation written in this call; true when the survivor's descriptor is to be recomputed
+__device__ bool edit_replace_in(const MapDev &M, int o, int w, int s, int nrow, int epoch, int guard,
+                                uint32_t *bm, int *sh)
+{
+    if (o == w || o < 0 || o >= M.P || w < 0 || w >= M.P) return false;
+    if (!(M.mp[w].flags & ORBG_MP_VALID)) return false;
+    const bool was_bad = !(M.mp[o].flags & ORBG_MP_VALID);
+    const int pw = edit_find(M, s, w, nrow, sh);
+    const int po = edit_find(M, s, o, nrow, sh);
+    edit_replace2(M, o, w, pw >= 0 ? s : -1, pw, po >= 0 ? s : -1, po, epoch, guard, bm, was_bad);
+    return true;
 }
 
 // ---------------------------------------------------------------------------
@@ -418,6 +452,150 @@ __global__ __launch_bounds__(MAP_T) void k_fuse_update(MapDev M, MapEditWs W, co
 }
 
 // ---------------------------------------------------------------------------
+// LoopClosing::CorrectLoop's loop fusion (src/LoopClosing.cc:848-863) and SearchAndFuse's
+// update (:944-992 with ORBmatcher.cc:1230-1250)
+// ---------------------------------------------------------------------------
+// matched[i] (mvpCurrentMatchedPoints as ids, -1 = none) in feature order: a held point is
+// replaced by the matched one, else the matched one is added.  surv [cap]: the points whose
+// descriptor is recomputed once after the call; counts: replaced, added
+__global__ __launch_bounds__(MAP_T) void k_loop_fusion(MapDev M, int cur, const int32_t *matched,
+                                                       int nm, int epoch, int32_t *surv,
+                                                       int32_t *counts)
+{
+    __shared__ uint32_t bm[ED_BM];
+    __shared__ int sh;
+    const int nrow = edit_kf_live(M, cur) ? min(M.kf_n[cur], M.cap) : 0;
+    const int n = min(nrow, nm);
+    for (int k = threadIdx.x; k < M.cap; k += MAP_T) surv[k] = -1;
+    __syncthreads();
+    int nrep = 0, nadd = 0;
+    for (int i = 0; i < n; i++) {
+        const int w = matched[i];
+        if (w < 0 || w >= M.P) continue;
+        const int o = M.kf_points[(size_t)cur * M.cap + i];
+        int sv = -1;
+        if (o >= 0) {
+            if (edit_replace_in(M, o, w, cur, nrow, epoch, n, bm, &sh)) {
+                sv = w;
+                nrep++;
+            }
+        } else if (M.mp[w].flags & ORBG_MP_VALID) {
+            if (edit_find(M, cur, w, nrow, &sh) < 0) {  // AddObservation returns when cur has it
+                if (threadIdx.x == 0) M.kf_points[(size_t)cur * M.cap + i] = w;
+                sv = w;
+                nadd++;
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) surv[i] = sv;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        counts[0] = nrep;
+        counts[1] = nadd;
+    }
+}
+
+// the job of SearchAndFuse's member of rank `rank` in slot order: its slot, the loop points'
+// count, the attached camera with the corrected Sim3's rows as Tcw ([s R | t], float)
+__global__ void k_sf_job(MapDev M, MapAttach A, MapEditWs W, const int32_t *set, int set_cap,
+                         const int32_t *nset, int rank, const orbg_sim3d *corrected, int n)
+{
+    if (blockIdx.x || threadIdx.x) return;
+    const int ns = min(max(*nset, 0), set_cap);
+    int s = -1;
+    for (int i = 0; i < ns && s < 0; i++) {
+        int r = 0;
+        for (int k = 0; k < ns; k++) r += set[k] < set[i];
+        if (r == rank) s = set[i];
+    }
+    const int act = rank < ns && edit_kf_live(M, s);
+    const int sc = min(max(s, 0), M.K - 1);
+    W.hdr[MAP_HDR_SLOT] = sc;
+    W.hdr[MAP_HDR_N] = act ? min(max(n, 0), W.ncap) : 0;
+    W.hdr[MAP_HDR_ACTIVE] = act;
+    orbg_frustum_camera cam = A.cams[sc];
+    if (act) {
+        const orbg_sim3d S = corrected[sc];
+        const double x = S.q[0], y = S.q[1], z = S.q[2], w = S.q[3];  // Quaterniond::toRotationMatrix
+        const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
+        const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x;
+        const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
+        const double R[9] = {1 - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1 - (txx + tzz),
+                             tyz - twx, txz - twy, tyz + twx, 1 - (txx + tyy)};
+        for (int r = 0; r < 3; r++) {
+            for (int k = 0; k < 3; k++) cam.Tcw[r * 4 + k] = (float)(S.s * R[r * 3 + k]);
+            cam.Tcw[r * 4 + 3] = (float)S.t[r];
+        }
+    }
+    W.cam[0] = cam;
+}
+
+// Fuse(pKF, Scw, vpPoints, th, vpReplacePoint)'s update and SearchAndFuse's Replace loop by one
+// workgroup: first every point with a target in order (a free feature takes it, a good point on
+// the feature is recorded), then the recorded points are replaced in order.  counts: nFused,
+// replaced
+__global__ __launch_bounds__(MAP_T) void k_sf_update(MapDev M, MapEditWs W, const int32_t *ids,
+                                                     int nmax, int epoch, int32_t *counts)
+{
+    __shared__ uint32_t bm[ED_BM];
+    __shared__ int scr[4];
+    __shared__ int sh;
+    const int s = W.hdr[MAP_HDR_SLOT], n = min(W.hdr[MAP_HDR_N], nmax);
+    const int nrow = W.hdr[MAP_HDR_ACTIVE] ? min(M.kf_n[s], M.cap) : 0;
+    int32_t *hits = W.hits, *rep = W.dd_best;
+    int nh = 0;
+    for (int base = 0; base < nmax; base += MAP_T) {  // uniform trip count
+        const int i = base + threadIdx.x;
+        bool hit = false;
+        if (i < n) {
+            const int b = W.bidx[i], p = ids[i];
+            hit = p >= 0 && p < M.P && b >= 0 && b < nrow && W.bdist[i] <= ORBG_MAP_TH_LOW;
+        }
+        if (i < nmax) W.surv[i] = -1;
+        int total;
+        const int ex = block_scan(hit, scr, &total);
+        if (hit) hits[nh + ex] = i;
+        nh += total;
+    }
+    __syncthreads();
+    int fused = 0, nrep = 0;
+    for (int h = 0; h < nh; h++) {
+        const int p = ids[hits[h]], b = W.bidx[hits[h]];
+        const int q = M.kf_points[(size_t)s * M.cap + b];
+        int r = -1;
+        bool add = false;
+        if (q < 0)
+            add = (M.mp[p].flags & ORBG_MP_VALID) && edit_find(M, s, p, nrow, &sh) < 0;
+        else if (q < M.P && (M.mp[q].flags & ORBG_MP_VALID))
+            r = q;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            if (add) M.kf_points[(size_t)s * M.cap + b] = p;
+            rep[h] = r;
+        }
+        fused++;
+        __syncthreads();
+    }
+    for (int h = 0; h < nh; h++) {
+        const int r = rep[h];
+        if (r < 0) continue;
+        const int p = ids[hits[h]];
+        const bool done = edit_replace_in(M, r, p, s, nrow, epoch, nh, bm, &sh);
+        __syncthreads();
+        if (done) {
+            if (threadIdx.x == 0) W.surv[hits[h]] = p;
+            nrep++;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        counts[0] += fused;
+        counts[1] += nrep;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // LocalMapping::SearchInNeighbors: the lists
 // ---------------------------------------------------------------------------
 // vpTargetKFs of `slot` into W.targets (all of it) and targets (the first target_cap), the
@@ -566,6 +744,30 @@ int launch_map_fuse_update(hipStream_t st, const MapDev &M, const MapEditWs &W, 
 {
     hipLaunchKernelGGL(k_fuse_update, dim3(1), dim3(MAP_T), 0, st, M, W, ids, nmax, epoch, best_idx,
                        best_dist, status, nfused, nfused_at_ntargets);
+    return last_rc();
+}
+
+int launch_map_loop_fusion(hipStream_t st, const MapDev &M, int cur, const int32_t *matched, int nm,
+                           int epoch, int32_t *surv, int32_t *counts)
+{
+    hipLaunchKernelGGL(k_loop_fusion, dim3(1), dim3(MAP_T), 0, st, M, cur, matched, nm, epoch, surv,
+                       counts);
+    return last_rc();
+}
+
+int launch_map_sf_job(hipStream_t st, const MapDev &M, const MapAttach &A, const MapEditWs &W,
+                      const int32_t *set, int set_cap, const int32_t *nset, int rank,
+                      const orbg_sim3d *corrected, int n)
+{
+    hipLaunchKernelGGL(k_sf_job, dim3(1), dim3(64), 0, st, M, A, W, set, set_cap, nset, rank,
+                       corrected, n);
+    return last_rc();
+}
+
+int launch_map_sf_update(hipStream_t st, const MapDev &M, const MapEditWs &W, const int32_t *ids,
+                         int nmax, int epoch, int32_t *counts)
+{
+    hipLaunchKernelGGL(k_sf_update, dim3(1), dim3(MAP_T), 0, st, M, W, ids, nmax, epoch, counts);
     return last_rc();
 }
 

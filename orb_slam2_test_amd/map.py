@@ -3,7 +3,10 @@ keyframe slot observes which map point" (liborbg's orbg_map_* entry points):
 KeyFrame::UpdateConnections (src/KeyFrame.cc:375-515), Tracking::UpdateLocalKeyFrames /
 UpdateLocalPoints (src/Tracking.cc:1731-1925), MapPoint::UpdateNormalAndDepth
 (src/MapPoint.cc:457-518), KeyFrame::SetBadFlag (src/KeyFrame.cc:622-720) and
-LocalMapping::KeyFrameCulling / MapPointCulling (src/LocalMapping.cc:227-270, 804-877).
+LocalMapping::KeyFrameCulling / MapPointCulling (src/LocalMapping.cc:227-270, 804-877), and of
+LoopClosing::CorrectLoop (src/LoopClosing.cc:744-843, 882-911, src/Optimizer.cc:1040-1323) the
+Sim3 propagation, LoopConnections, the essential-graph walk and the application of the optimised
+poses, over keyframe poses, mnId, loop edges and the mnCorrected fields the Map holds.
 
 A KeyFrame is a slot in [0, max_keyframes), as in KeyFrameDatabase; a MapPoint is an id in
 [0, max_points).  Wherever the reference orders by KeyFrame pointer, the order here is the
@@ -19,6 +22,14 @@ ascending slot (include/orbg.h).
     recent, status = m.MapPointCulling(recent, current_kf_id, monocular)
     for r in m.KeyFrameCulling(slot, monocular):              # CULL_RECORD_DTYPE records
         if r["status"] == 1: db.erase(r["slot"])
+    m.SetPoses(slots, Tcw, mnId)                              # KeyFrame::SetPose, once per pose
+    members, corrected, noncorrected = m.Propagate(cur, Scw)  # CorrectLoop, LoopClosing.cc:744-843
+    m.LoopFusion(cur, matched); m.SearchAndFuse(members, corrected, loop_points)
+    pairs = m.LoopConnections(members)
+    vs, fixed, Scw_v, Snc_v, edges, _ = m.EssentialGraph(cur, loop, corrected, noncorrected, members, pairs)
+    Siw, Tiw, _ = OptimizeEssentialGraph(Scw_v, Snc_v, edges, fixed, bFixScale)
+    m.ApplyCorrection(cur, vs, Scw_v, Siw, Tiw); m.AddLoopEdge(loop, cur)
+    report, counts = m.CorrectLoop(cur, loop, Scw, matched, loop_points, bFixScale)  # all of it
 """
 import ctypes as C
 
@@ -30,6 +41,9 @@ from .orbmatcher import _ctx
 NEIGHBOURS = 10
 SIN_MAX_TARGETS = 120     # SearchInNeighbors: 20 first-level + 20 * 5 second-level entries
 KF_ROOT, KF_BAD = 1, 2
+MAX_LOOP_EDGES = 16        # mspLoopEdges entries per slot (ORBG_ERANGE past it)
+MAX_LOOP_SET = 256         # members of mvpCurrentConnectedKFs a Propagate / LoopConnections call takes
+LOOP_NO_POSE, LOOP_SET_RANGE, LOOP_DEAD = 1, 2, 4   # propagate_device's status bits
 FEAT_STEREO, FEAT_CLOSE = L.MAP_FEAT_STEREO, L.MAP_FEAT_CLOSE
 
 
@@ -509,3 +523,196 @@ class Map:
         L.check(L.lib().orbg_map_get_point_refs(self._c(), self._h, int(first), n, L.ptr(out)),
                 "orbg_map_get_point_refs")
         return out
+
+    # ---- LoopClosing::CorrectLoop: poses, loop edges, Propagate, LoopConnections ----
+    def SetPoses(self, slots, Tcw=None, mnid=None):
+        """KeyFrame::SetPose of the listed slots (Tcw [n, 3, 4] float32; the stored camera
+        centre becomes -Rcw^T tcw) and / or their mnId; None leaves that half as it is."""
+        s = _i32(slots)
+        T = None if Tcw is None else np.ascontiguousarray(Tcw, np.float32).reshape(-1, 12)
+        i = None if mnid is None else _i32(mnid)
+        if (T is not None and len(T) != len(s)) or (i is not None and len(i) != len(s)):
+            raise ValueError("slots, poses and ids differ in length")
+        L.check(L.lib().orbg_map_set_keyframe_poses(self._c(), self._h, L.ptr(s), len(s), L.ptr(T),
+                                                    L.ptr(i)), "orbg_map_set_keyframe_poses")
+
+    def set_poses_device(self, d_slots, n, d_Tcw, d_mnid, ctx=None):
+        L.check(L.lib().orbg_map_set_keyframe_poses_device(self._c(ctx), self._h, d_slots, int(n),
+                                                           d_Tcw, d_mnid),
+                "orbg_map_set_keyframe_poses_device")
+
+    def poses(self, first=0, n=None):
+        """(Tcw float32 [n, 3, 4], has_pose bool [n], mnId int32 [n], camera centres [n, 3])"""
+        n = self.max_keyframes - first if n is None else int(n)
+        T, h = np.zeros((n, 3, 4), np.float32), np.zeros(n, np.int32)
+        i, c = np.zeros(n, np.int32), np.zeros((n, 3), np.float32)
+        L.check(L.lib().orbg_map_get_keyframe_poses(self._c(), self._h, int(first), n, L.ptr(T),
+                                                    L.ptr(h), L.ptr(i), L.ptr(c)),
+                "orbg_map_get_keyframe_poses")
+        return T, h != 0, i, c
+
+    def AddLoopEdge(self, a, b):
+        """KeyFrame::AddLoopEdge on both sides, as CorrectLoop calls it"""
+        L.check(L.lib().orbg_map_add_loop_edge(self._c(), self._h, int(a), int(b)),
+                "orbg_map_add_loop_edge")
+
+    def GetLoopEdges(self, slot):
+        """mspLoopEdges of a slot, ascending"""
+        out, n = np.zeros(MAX_LOOP_EDGES, np.int32), C.c_int32()
+        L.check(L.lib().orbg_map_get_loop_edges(self._c(), self._h, int(slot), L.ptr(out), len(out),
+                                                C.byref(n)), "orbg_map_get_loop_edges")
+        return out[:n.value].tolist()
+
+    def corrected(self, first=0, n=None):
+        """(mnCorrectedByKF, mnCorrectedReference) of the points"""
+        n = self.max_points - first if n is None else int(n)
+        a, b = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        L.check(L.lib().orbg_map_get_point_corrected(self._c(), self._h, int(first), n, L.ptr(a),
+                                                     L.ptr(b)), "orbg_map_get_point_corrected")
+        return a, b
+
+    def Propagate(self, cur, Scw, set_cap=MAX_LOOP_SET):
+        """CorrectLoop's Sim3 propagation (LoopClosing.cc:744-843 without the loop fusion) with
+        mpCurrentKF = cur and mg2oScw = Scw (a SIM3D_DTYPE record or (q, t, s), q = x, y, z, w):
+        (mvpCurrentConnectedKFs as slots, CorrectedSim3, NonCorrectedSim3), the tables
+        SIM3D_DTYPE [max_keyframes] indexed by slot."""
+        from .optimizer import sim3d_records
+        S = sim3d_records(Scw if isinstance(Scw, np.ndarray) else [Scw])
+        st = np.zeros(int(set_cap), np.int32)
+        n = C.c_int32()
+        co, nc = (np.zeros(self.max_keyframes, L.SIM3D_DTYPE) for _ in range(2))
+        L.check(L.lib().orbg_map_propagate(self._c(), self._h, int(cur), L.ptr(S), L.ptr(st),
+                                           len(st), C.byref(n), L.ptr(co), L.ptr(nc)),
+                "orbg_map_propagate")
+        return st[:n.value].tolist(), co, nc
+
+    def propagate_device(self, cur, d_Scw, d_set, set_cap, d_nset, d_corrected, d_noncorrected,
+                         d_status, ctx=None):
+        L.check(L.lib().orbg_map_propagate_device(self._c(ctx), self._h, int(cur), d_Scw, d_set,
+                                                  int(set_cap), d_nset, d_corrected,
+                                                  d_noncorrected, d_status),
+                "orbg_map_propagate_device")
+
+    def LoopConnections(self, members):
+        """CorrectLoop's LoopConnections (LoopClosing.cc:882-911) over the members in the given
+        (vector) order: int32 [n, 2] slot pairs (i, j), by i then j ascending"""
+        s = _i32(members)
+        cap = max(len(s) * self.max_keyframes, 1)
+        out, n = np.zeros((cap, 2), np.int32), C.c_int32()
+        L.check(L.lib().orbg_map_loop_connections(self._c(), self._h, L.ptr(s), len(s), L.ptr(out),
+                                                  cap, C.byref(n)), "orbg_map_loop_connections")
+        return out[:n.value]
+
+    def loop_connections_device(self, d_set, set_cap, d_nset, d_pairs, pair_cap, d_npairs,
+                                ctx=None):
+        L.check(L.lib().orbg_map_loop_connections_device(self._c(ctx), self._h, d_set, int(set_cap),
+                                                         d_nset, d_pairs, int(pair_cap), d_npairs),
+                "orbg_map_loop_connections_device")
+
+    def EssentialGraph(self, cur, loop, corrected, noncorrected, members, pairs, edge_cap=None):
+        """The walk of Optimizer::OptimizeEssentialGraph over the map (Optimizer.cc:1040-1258):
+        (vert_slot int32 [nvert], fixed vertex, Scw, Snc SIM3D_DTYPE [nvert], edges EG_EDGE_DTYPE
+        in the reference's order, edges left out because an end is no vertex) -- the inputs of
+        OptimizeEssentialGraph / EssentialGraph.  corrected / noncorrected: Propagate's tables."""
+        co = np.ascontiguousarray(corrected, L.SIM3D_DTYPE).reshape(-1)
+        nc = np.ascontiguousarray(noncorrected, L.SIM3D_DTYPE).reshape(-1)
+        if len(co) != self.max_keyframes or len(nc) != self.max_keyframes:
+            raise ValueError("the Sim3 tables have max_keyframes entries")
+        s = _i32(members)
+        p = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        K = self.max_keyframes
+        cap = int(edge_cap) if edge_cap is not None else len(p) + K * (1 + MAX_LOOP_EDGES) + K * 32
+        vs = np.zeros(K, np.int32)
+        Scw, Snc = np.zeros(K, L.SIM3D_DTYPE), np.zeros(K, L.SIM3D_DTYPE)
+        ed = np.zeros(cap, L.EG_EDGE_DTYPE)
+        nv, fx, ne, sk = (C.c_int32() for _ in range(4))
+        L.check(L.lib().orbg_map_essential_graph(self._c(), self._h, int(cur), int(loop), L.ptr(co),
+                                                 L.ptr(nc), L.ptr(s), len(s), L.ptr(p), len(p),
+                                                 L.ptr(vs), C.byref(nv), C.byref(fx), L.ptr(Scw),
+                                                 L.ptr(Snc), L.ptr(ed), cap, C.byref(ne),
+                                                 C.byref(sk)), "orbg_map_essential_graph")
+        n = nv.value
+        return vs[:n], fx.value, Scw[:n], Snc[:n], ed[:ne.value], sk.value
+
+    def essential_graph_device(self, cur, loop, d_corrected, d_noncorrected, d_set, set_cap, d_nset,
+                               d_pairs, pair_cap, d_npairs, d_vert_slot, d_nvert, d_fixed, d_Scw,
+                               d_Snc, d_edges, edge_cap, d_nedge, d_status, ctx=None):
+        L.check(L.lib().orbg_map_essential_graph_device(
+            self._c(ctx), self._h, int(cur), int(loop), d_corrected, d_noncorrected, d_set,
+            int(set_cap), d_nset, d_pairs, int(pair_cap), d_npairs, d_vert_slot, d_nvert, d_fixed,
+            d_Scw, d_Snc, d_edges, int(edge_cap), d_nedge, d_status),
+            "orbg_map_essential_graph_device")
+
+    def ApplyCorrection(self, cur, vert_slot, Scw, Siw, Tiw):
+        """Optimizer.cc:1264-1323: SetPose(Tiw[v]) per vertex, the map points' correction with
+        Srw = Scw[r] and the optimised Siw[r], UpdateNormalAndDepth of all points."""
+        v = _i32(vert_slot)
+        a = np.ascontiguousarray(Scw, L.SIM3D_DTYPE).reshape(-1)
+        b = np.ascontiguousarray(Siw, L.SIM3D_DTYPE).reshape(-1)
+        T = np.ascontiguousarray(Tiw, np.float32).reshape(-1, 12)
+        if not (len(v) == len(a) == len(b) == len(T)):
+            raise ValueError("vert_slot, Scw, Siw and Tiw differ in length")
+        L.check(L.lib().orbg_map_apply_correction(self._c(), self._h, int(cur), L.ptr(v), len(v),
+                                                  L.ptr(a), L.ptr(b), L.ptr(T)),
+                "orbg_map_apply_correction")
+
+    def apply_correction_device(self, cur, d_vert_slot, d_nvert, d_Scw, d_Siw, d_Tiw, ctx=None):
+        L.check(L.lib().orbg_map_apply_correction_device(self._c(ctx), self._h, int(cur),
+                                                         d_vert_slot, d_nvert, d_Scw, d_Siw, d_Tiw),
+                "orbg_map_apply_correction_device")
+
+    def SetCorrected(self, first, corrected_by_kf, corrected_reference):
+        """mnCorrectedByKF / mnCorrectedReference of the points first .. (a map uploaded from host
+        state)"""
+        a, b = _i32(corrected_by_kf), _i32(corrected_reference)
+        if len(a) != len(b):
+            raise ValueError("the two arrays differ in length")
+        L.check(L.lib().orbg_map_set_point_corrected(self._c(), self._h, int(first), len(a), L.ptr(a),
+                                                     L.ptr(b)), "orbg_map_set_point_corrected")
+
+    def LoopFusion(self, cur, matched):
+        """CorrectLoop's loop fusion (LoopClosing.cc:848-863) with mvpCurrentMatchedPoints as ids
+        (-1 = none) in feature order: (replaced, added)"""
+        p = _i32(matched)
+        out = np.zeros(2, np.int32)
+        L.check(L.lib().orbg_map_loop_fusion(self._c(), self._h, int(cur), L.ptr(p), len(p),
+                                             L.ptr(out)), "orbg_map_loop_fusion")
+        return int(out[0]), int(out[1])
+
+    def loop_fusion_device(self, cur, d_matched, n, d_counts, ctx=None):
+        L.check(L.lib().orbg_map_loop_fusion_device(self._c(ctx), self._h, int(cur), d_matched,
+                                                    int(n), d_counts), "orbg_map_loop_fusion_device")
+
+    def SearchAndFuse(self, members, corrected, loop_points, th=4.0):
+        """LoopClosing::SearchAndFuse over the members in slot order with Propagate's
+        CorrectedSim3 table and mvpLoopMapPoints as ids: (sum of nFused, replacements)"""
+        s, p = _i32(members), _i32(loop_points)
+        co = np.ascontiguousarray(corrected, L.SIM3D_DTYPE).reshape(-1)
+        if len(co) != self.max_keyframes:
+            raise ValueError("the Sim3 table has max_keyframes entries")
+        out = np.zeros(2, np.int32)
+        L.check(L.lib().orbg_map_search_and_fuse(self._c(), self._h, L.ptr(s), len(s), L.ptr(co),
+                                                 L.ptr(p), len(p), float(th), L.ptr(out)),
+                "orbg_map_search_and_fuse")
+        return int(out[0]), int(out[1])
+
+    def search_and_fuse_device(self, d_set, set_cap, d_nset, d_corrected, d_loop_points, n, th,
+                               d_counts, ctx=None):
+        L.check(L.lib().orbg_map_search_and_fuse_device(self._c(ctx), self._h, d_set, int(set_cap),
+                                                        d_nset, d_corrected, d_loop_points, int(n),
+                                                        float(th), d_counts),
+                "orbg_map_search_and_fuse_device")
+
+    def CorrectLoop(self, cur, loop, Scw, matched, loop_points, bFixScale):
+        """LoopClosing::CorrectLoop in one call: (LM report dict, counts dict)"""
+        from .optimizer import sim3d_records, _lm_report
+        S = sim3d_records(Scw if isinstance(Scw, np.ndarray) else [Scw])
+        a, b = _i32(matched), _i32(loop_points)
+        rep, cnt = L.LmReport(), np.zeros(8, np.int32)
+        L.check(L.lib().orbg_map_correct_loop(self._c(), self._h, int(cur), int(loop), L.ptr(S),
+                                              L.ptr(a), len(a), L.ptr(b), len(b),
+                                              1 if bFixScale else 0, C.byref(rep), L.ptr(cnt)),
+                "orbg_map_correct_loop")
+        keys = ("members", "fusion_replaced", "fusion_added", "fused", "replaced", "pairs",
+                "vertices", "edges")
+        return _lm_report(rep), dict(zip(keys, cnt.tolist()))
