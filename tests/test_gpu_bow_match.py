@@ -10,6 +10,8 @@ k = 10, L = 6 vocabulary (ORBvoc.txt's shape; the real file is a missing blob) a
 features, the kernel's > 128-candidate path) and at levelsup 1 (> 1024 nodes per frame:
 several node-join passes); invalid MapPoints; empty inputs; and the
 batched device entry over a batch of frames, frame t's reference KeyFrame = frame t - 1.
+The same kernels against an independent reference on designed boundary scenes:
+tests/test_gpu_kf_matching_ref.py.
 """
 import numpy as np
 import pytest

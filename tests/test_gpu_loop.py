@@ -11,6 +11,8 @@ tests/test_oracle_loop.py), bit for bit: the written keypoint array and nmatches
 Cases: several points competing for one keypoint (the in-order skip of written keypoints),
 keypoints written before the call, rotations outside the dominant bins, fractional
 (undistorted-camera) bounds, Sim3 scales, empty inputs, and the batched device form.
+SearchBySim3 against an independent reference on designed boundary scenes:
+tests/test_gpu_kf_matching_ref.py.
 """
 import ctypes as C
 

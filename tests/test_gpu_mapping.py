@@ -8,6 +8,8 @@ bOnlyStereo / checkOri both ways; KF2 features on the epipole of a forward motio
 monocular epipole test); few large nodes (> 128 candidates: the kernel's re-read path); more
 than 1024 nodes (several join passes); empty KeyFrames; and the batched device entry over a
 set of KeyFrames, each paired with several neighbours (CreateNewMapPoints' loop).
+The same kernels against an independent reference on designed boundary scenes:
+tests/test_gpu_kf_matching_ref.py.
 """
 import numpy as np
 import pytest
