@@ -2188,6 +2188,90 @@ int orbg_map_correct_loop(orbg_ctx *ctx, orbg_map *map, int cur, int loop, const
                           const int32_t *matched, int nmatched, const int32_t *loop_points,
                           int nloop, int fix_scale, orbg_lm_report *report, int32_t *counts);
 
+/* ---- Optimizer::LocalBundleAdjustment(pKF, pbStopFlag, pMap) on the Map ----
+ * src/Optimizer.cc:633-979 in three stages and one chaining call.  The keyframe data must be
+ * attached (orbg_map_attach_keyframes: mvKeysUn, mvuRight, the cameras) and every window
+ * keyframe needs a pose (orbg_map_set_keyframe_poses).  The `_device` forms run on the context
+ * stream without synchronising and allocate nothing after the first call of a size; the host
+ * forms take host arrays and synchronise.  Pointer order is slot order.
+ *
+ * The window (:635-851), exactly what the compat layer's build_lba_window produces from the
+ * reference's three lists:
+ *   kf_slots [npose]   nlocal local keyframes (slot, then its ordered covisibility list without
+ *                      the ORBG_MAP_KF_BAD entries), then the fixed cameras in order of first
+ *                      appearance over the local points (list order) and each point's observers
+ *                      (ascending slot); a bad observer is listed nowhere.
+ *   point_ids [npoint] the good points of the local rows, rows in list order, features in order,
+ *                      each at its first occurrence.
+ *   poses [npose]      Converter::toSE3Quat(kf_Tcw) in double from the float entries (Eigen's
+ *                      branch, w >= 0, one normalisation); fixed = 1 for the fixed part and mnId 0.
+ *   points [npoint][3] the stored float positions as doubles.
+ *   edges [nedge], edge_feat [nedge]
+ *                      per local point, per observer that is not bad (ascending slot): stereo =
+ *                      mvuRight[idx] >= 0 (no mvuRight attached: mono), obs from mvKeysUn[idx] and
+ *                      mvuRight[idx], inv_sigma2 = mvInvLevelSigma2[octave] (a float, widened),
+ *                      the intrinsics of the attached camera, huber_delta = (float)sqrt(5.991) /
+ *                      (float)sqrt(7.815), robust = active = 1; edge_feat = idx.
+ *   counts [4]         nlocal, npose, npoint, nedge: always the full counts.
+ *   status [4]         [0] = ORBG_LBA_* bits.
+ * Nothing in the Map changes.  point_cap <= 524286.  The host form returns ORBG_ERANGE when a cap
+ * is exceeded (counts hold what is needed) and ORBG_EINVAL for a dead slot, nothing attached, a
+ * window keyframe without a pose or an observation whose feature index is past the attached
+ * count. */
+#define ORBG_LBA_NO_POSE 1
+#define ORBG_LBA_RANGE 2
+#define ORBG_LBA_DEAD 4
+#define ORBG_LBA_FEATURE 8
+int orbg_map_lba_window_device(orbg_ctx *ctx, orbg_map *map, int slot, int32_t *d_kf_slots,
+                               orbg_pose *d_poses, int pose_cap, int32_t *d_point_ids,
+                               double *d_points, int point_cap, orbg_edge *d_edges,
+                               int32_t *d_edge_feat, int edge_cap, int32_t *d_counts,
+                               int32_t *d_status);
+int orbg_map_lba_window(orbg_ctx *ctx, orbg_map *map, int slot, int32_t *kf_slots, orbg_pose *poses,
+                        int pose_cap, int32_t *point_ids, double *points, int point_cap,
+                        orbg_edge *edges, int32_t *edge_feat, int edge_cap, int32_t *counts);
+/* The write-back (:943-978) of a window (its arrays as above, d_counts as the window left them;
+ * the edges of one point are adjacent, as the window emits them), the optimised d_poses /
+ * d_points and the vToErase flags d_erase [nedge]:
+ *   erasures  per flagged edge, mono edges first and then stereo edges, each in edge order:
+ *             EraseMapPointMatch (the row entry becomes -1) and MapPoint::EraseObservation as
+ *             KeyFrameCulling states it (Observations() less 2 for an ORBG_MAP_FEAT_STEREO
+ *             feature, else 1; mpRefKF moves to the lowest remaining observing slot; at
+ *             Observations() <= 2 the point goes bad and leaves every row).  A flag on an edge
+ *             whose point has gone bad earlier in the call does nothing;
+ *   poses     SetPose(Converter::toCvMat(pose)) of the first nlocal keyframes, mnId 0 included,
+ *             the centres as orbg_map_set_keyframe_poses writes them;
+ *   points    every window point's position = (float) of its estimate, bad or not; then
+ *             UpdateNormalAndDepth of the window's points over the rebuilt observation index;
+ *   cameras   d_cams_out (may be NULL): the Tcw of the local keyframes' entries is rewritten,
+ *             nothing else.
+ * W and the ordered lists do not change.  d_out [2]: erased observations, points gone bad. */
+int orbg_map_lba_apply_device(orbg_ctx *ctx, orbg_map *map, const int32_t *d_kf_slots, int pose_cap,
+                              const int32_t *d_point_ids, int point_cap, const orbg_edge *d_edges,
+                              const int32_t *d_edge_feat, int edge_cap, const int32_t *d_counts,
+                              const orbg_pose *d_poses, const double *d_points,
+                              const uint8_t *d_erase, orbg_frustum_camera *d_cams_out,
+                              int32_t *d_out);
+int orbg_map_lba_apply(orbg_ctx *ctx, orbg_map *map, const int32_t *kf_slots, int nlocal, int npose,
+                       const int32_t *point_ids, int npoint, const orbg_edge *edges,
+                       const int32_t *edge_feat, int nedge, const orbg_pose *poses,
+                       const double *points, const uint8_t *erase,
+                       orbg_frustum_camera *d_cams_out, int32_t *out);
+/* All of it: the window, the stop check (control->force_stop raised: stopped = 1 and nothing
+ * written, :853-855), orbg_local_ba_optimize's optimisation on the window's device arrays (the
+ * estimates never reach the host; the edge records are read once for orbg_ba_graph_create; the
+ * outlier and vToErase decisions stay host reads of chi2 / depth), the write-back.  The workspace
+ * belongs to the map and grows on demand.  An empty edge set optimises nothing and still
+ * applies.  ORBG_ENOTSUP of orbg_ba_graph_create is returned with the Map untouched. */
+typedef struct {
+    orbg_lba_report lba;
+    int32_t nlocal, nfixed, npoints, nedges;
+    int32_t nerased, npoints_bad;  /* observations erased, points gone bad by erasure */
+    int32_t stopped, pad;
+} orbg_map_lba_report;
+int orbg_map_local_ba(orbg_ctx *ctx, orbg_map *map, int slot, const orbg_lm_control *control,
+                      orbg_frustum_camera *d_cams_out, orbg_map_lba_report *report);
+
 /* ---------------- GlobalBundleAdjustment (Optimizer::BundleAdjustment) ----------------
  * src/Optimizer.cc:105-320: every keyframe a VertexSE3Expmap (fixed iff mnId == 0), every map
  * point a marginalised VertexSBAPointXYZ, one EdgeSE3ProjectXYZ / EdgeStereoSE3ProjectXYZ per

@@ -172,6 +172,22 @@ class LmControl(C.Structure):
                 ("d_last_chi2", C.c_void_p)]
 
 
+class LbaReport(C.Structure):
+    """orbg_lba_report (include/orbg.h)."""
+    _fields_ = [("lm", LmReport * 2), ("do_more", C.c_int32), ("n_outliers", C.c_int32),
+                ("n_erase", C.c_int32), ("pad", C.c_int32)]
+
+
+class MapLbaReport(C.Structure):
+    """orbg_map_lba_report (include/orbg.h)."""
+    _fields_ = [("lba", LbaReport), ("nlocal", C.c_int32), ("nfixed", C.c_int32),
+                ("npoints", C.c_int32), ("nedges", C.c_int32), ("nerased", C.c_int32),
+                ("npoints_bad", C.c_int32), ("stopped", C.c_int32), ("pad", C.c_int32)]
+
+
+LBA_NO_POSE, LBA_RANGE, LBA_DEAD, LBA_FEATURE = 1, 2, 4, 8   # ORBG_LBA_*
+
+
 class KeyFrames(C.Structure):
     """orbg_keyframes (include/orbg.h): a set of KeyFrames in device memory."""
     _fields_ = [("desc", C.c_void_p), ("kps", C.c_void_p), ("uright", C.c_void_p),
@@ -517,6 +533,14 @@ def lib():
         "orbg_map_search_and_fuse_device": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, f32, vp]),
         "orbg_map_search_and_fuse": (i32, [vp, vp, vp, i32, vp, vp, i32, f32, vp]),
         "orbg_map_correct_loop": (i32, [vp, vp, i32, i32, vp, vp, i32, vp, i32, i32, P(LmReport), vp]),
+        "orbg_local_ba_optimize": (i32, [vp, vp, i32, vp, i32, vp, i32, P(LmControl), vp, vp, vp,
+                                         P(LbaReport)]),
+        "orbg_map_lba_window_device": (i32, [vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp]),
+        "orbg_map_lba_window": (i32, [vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp]),
+        "orbg_map_lba_apply_device": (i32, [vp, vp, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp,
+                                            vp]),
+        "orbg_map_lba_apply": (i32, [vp, vp, vp, i32, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
+        "orbg_map_local_ba": (i32, [vp, vp, i32, P(LmControl), vp, P(MapLbaReport)]),
         "orbg_sim3_ransac_iterations": (i32, [C.c_double, i32, i32, i32]),
         "orbg_sim3_solve": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
         "orbg_sim3_solve_batch_device": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp,

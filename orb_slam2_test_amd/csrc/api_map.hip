@@ -28,6 +28,14 @@ struct orbg_map {
     void *d_ws = nullptr;
     void *d_lc = nullptr;        // LoopConnections' rows [MAX_LOOP_SET][K] u16 and counts [MAX_LOOP_SET]
     void *d_ap = nullptr;        // the correction's positions in and out [2][P][3] and vertices [P]
+    MapLbaWs LW{};               // LocalBundleAdjustment's marks, allocated at the first call
+    void *d_lw = nullptr;
+    MapLbaWindow LB{};           // orbg_map_local_ba's window, grown on demand
+    void *d_lb = nullptr;
+    uint8_t *d_lb_erase = nullptr;  // [edge_cap] the vToErase flags of that window
+    std::vector<orbg_edge> lb_edges;           // its edge records, fixed flags and vToErase on the host
+    std::vector<int32_t> lb_fixed;
+    std::vector<uint8_t> lb_fixed8, lb_erase;
 };
 
 static int map_reset(orbg_map *m, hipStream_t st)
@@ -176,6 +184,8 @@ extern "C" void orbg_map_destroy(orbg_map *m)
     if (m->d_ws) hipFree(m->d_ws);
     if (m->d_lc) hipFree(m->d_lc);
     if (m->d_ap) hipFree(m->d_ap);
+    if (m->d_lw) hipFree(m->d_lw);
+    if (m->d_lb) hipFree(m->d_lb);
     if (m->d_mem) hipFree(m->d_mem);
     delete m;
 }
@@ -1886,5 +1896,359 @@ extern "C" int orbg_map_correct_loop(orbg_ctx *c, orbg_map *m, int cur, int loop
     const int32_t out[8] = {hh[0], hh[16], hh[17], hh[18], hh[19], hh[1], hh[2], hh[4]};
     for (int i = 0; i < 8; i++) counts[i] = out[i];
     c->prof.collect();
+    return ORBG_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Optimizer::LocalBundleAdjustment on the Map (map_lba_kernels.hip)
+// ---------------------------------------------------------------------------
+// the marks of one window over up to pcap points
+static int map_lba_ws(orbg_ctx *c, orbg_map *m, int pcap)
+{
+    if (m->d_lw && pcap <= m->LW.pcap) return ORBG_OK;
+    if (m->d_lw) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipFree(m->d_lw));
+        m->d_lw = nullptr;
+        m->LW = MapLbaWs{};
+    }
+    const size_t K = (size_t)m->D.K, n = (size_t)std::max(pcap, 1);
+    Layout L;
+    const size_t o_h = L.take(16 * 4), o_r = L.take(K * 4), o_f = L.take(K * 4), o_p = L.take(K * 4);
+    const size_t o_s = L.take(K * 4), o_x = L.take(K * 4), o_c = L.take((K + 1) * 4);
+    const size_t o_e = L.take((n + 1) * 4), o_i = L.take(n * 4);
+    if (hipMalloc(&m->d_lw, L.total()) != hipSuccess) {
+        m->d_lw = nullptr;
+        return set_err(ORBG_ENOMEM, "Map: hipMalloc(%zu bytes) for the local BA marks", L.total());
+    }
+    HIPCHK(hipMemsetAsync(m->d_lw, 0, L.total(), c->stream));
+    uint8_t *b = (uint8_t *)m->d_lw;
+    MapLbaWs &W = m->LW;
+    W.pcap = (int32_t)n;
+    W.hdr = L.at<int32_t>(b, o_h);
+    W.lrank = L.at<int32_t>(b, o_r);
+    W.ffirst = L.at<int32_t>(b, o_f);
+    W.pidx = L.at<int32_t>(b, o_p);
+    W.lslot = L.at<int32_t>(b, o_s);
+    W.fixed = L.at<int32_t>(b, o_x);
+    W.cnt = L.at<int32_t>(b, o_c);
+    W.eoff = L.at<int32_t>(b, o_e);
+    W.ids = L.at<int32_t>(b, o_i);
+    return ORBG_OK;
+}
+
+static int map_lba_caps_ok(int pose_cap, int point_cap, int edge_cap)
+{
+    if (pose_cap < 0 || point_cap < 0 || edge_cap < 0) return set_err(ORBG_EINVAL, "negative cap");
+    if (point_cap > ORBG_LBA_MAX_POINTS)
+        return set_err(ORBG_ENOTSUP, "point_cap %d (> %d: a window position is 19 bits of a sort key)",
+                       point_cap, ORBG_LBA_MAX_POINTS);
+    return ORBG_OK;
+}
+
+static int map_lba_status(int bits, int slot, const int32_t *cnt, int pose_cap, int point_cap, int edge_cap)
+{
+    if (bits & ORBG_LBA_DEAD) return set_err(ORBG_EINVAL, "LocalBundleAdjustment: slot %d is not a live keyframe", slot);
+    if (bits & ORBG_LBA_NO_POSE) return set_err(ORBG_EINVAL, "LocalBundleAdjustment: a window keyframe has no pose");
+    if (bits & ORBG_LBA_RANGE)
+        return set_err(ORBG_ERANGE, "LocalBundleAdjustment: %d poses, %d points, %d edges (caps %d, %d, %d)",
+                       cnt[1], cnt[2], cnt[3], pose_cap, point_cap, edge_cap);
+    if (bits & ORBG_LBA_FEATURE)
+        return set_err(ORBG_EINVAL, "LocalBundleAdjustment: an observation's feature index is past the attached count");
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_lba_window_device(orbg_ctx *c, orbg_map *m, int slot, int32_t *d_kf_slots,
+                                          orbg_pose *d_poses, int pose_cap, int32_t *d_point_ids,
+                                          double *d_points, int point_cap, orbg_edge *d_edges,
+                                          int32_t *d_edge_feat, int edge_cap, int32_t *d_counts,
+                                          int32_t *d_status)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_slot_ok(m, slot)) || (rc = map_lba_caps_ok(pose_cap, point_cap, edge_cap))) return rc;
+    if ((pose_cap && (!d_kf_slots || !d_poses)) || (point_cap && (!d_point_ids || !d_points)) ||
+        (edge_cap && (!d_edges || !d_edge_feat)) || !d_counts || !d_status)
+        return set_err(ORBG_EINVAL, "NULL device array");
+    if ((rc = map_attached(m))) return rc;
+    if ((rc = map_lba_ws(c, m, point_cap))) return rc;
+    if ((rc = orbg_map_rebuild(c, m))) return rc;
+    MapLbaWindow O{};
+    O.kf_slots = d_kf_slots;
+    O.poses = d_poses;
+    O.point_ids = d_point_ids;
+    O.points = d_points;
+    O.edges = d_edges;
+    O.edge_feat = d_edge_feat;
+    O.pose_cap = pose_cap;
+    O.point_cap = point_cap;
+    O.edge_cap = edge_cap;
+    O.counts = d_counts;
+    MapLbaConst C{};
+    for (int i = 0; i < 16; i++) C.inv_sigma2[i] = c->inv_sigma2[i];
+    const float hm = std::sqrt(5.991), hs = std::sqrt(7.815);  // float in the reference (Optimizer.cc:758-759)
+    C.huber_mono = hm;
+    C.huber_stereo = hs;
+    if ((rc = launch_map_lba_window(c->stream, m->D, m->att, m->LW, slot, O, C, d_status, &c->prof)))
+        return set_err(rc, "k_lba window launch failed");
+    m->touched = true;
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_lba_window(orbg_ctx *c, orbg_map *m, int slot, int32_t *kf_slots,
+                                   orbg_pose *poses, int pose_cap, int32_t *point_ids, double *points,
+                                   int point_cap, orbg_edge *edges, int32_t *edge_feat, int edge_cap,
+                                   int32_t *counts)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_slot_ok(m, slot)) || (rc = map_lba_caps_ok(pose_cap, point_cap, edge_cap))) return rc;
+    if ((pose_cap && (!kf_slots || !poses)) || (point_cap && (!point_ids || !points)) ||
+        (edge_cap && (!edges || !edge_feat)) || !counts)
+        return set_err(ORBG_EINVAL, "NULL array");
+    const size_t np = (size_t)pose_cap, nq = (size_t)point_cap, ne = (size_t)edge_cap;
+    Layout L;
+    const size_t o_k = L.take(np * 4), o_p = L.take(np * sizeof(orbg_pose)), o_i = L.take(nq * 4);
+    const size_t o_x = L.take(nq * 24), o_e = L.take(ne * sizeof(orbg_edge)), o_f = L.take(ne * 4);
+    const size_t o_h = L.take(32);  // counts [4], status [4]
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
+    int32_t *h = L.at<int32_t>(b, o_h);
+    HIPCHK(hipMemsetAsync(h, 0, 32, c->stream));
+    if ((rc = orbg_map_lba_window_device(c, m, slot, L.at<int32_t>(b, o_k), L.at<orbg_pose>(b, o_p),
+                                         pose_cap, L.at<int32_t>(b, o_i), L.at<double>(b, o_x),
+                                         point_cap, L.at<orbg_edge>(b, o_e), L.at<int32_t>(b, o_f),
+                                         edge_cap, h, h + 4)))
+        return rc;
+    int32_t out[8];
+    HIPCHK(hipMemcpyAsync(out, h, 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->prof.collect();
+    for (int i = 0; i < 4; i++) counts[i] = out[i];
+    if ((rc = map_lba_status(out[4], slot, out, pose_cap, point_cap, edge_cap))) return rc;
+    if (out[1]) {
+        HIPCHK(hipMemcpy(kf_slots, b + o_k, (size_t)out[1] * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(poses, b + o_p, (size_t)out[1] * sizeof(orbg_pose), hipMemcpyDeviceToHost));
+    }
+    if (out[2]) {
+        HIPCHK(hipMemcpy(point_ids, b + o_i, (size_t)out[2] * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(points, b + o_x, (size_t)out[2] * 24, hipMemcpyDeviceToHost));
+    }
+    if (out[3]) {
+        HIPCHK(hipMemcpy(edges, b + o_e, (size_t)out[3] * sizeof(orbg_edge), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(edge_feat, b + o_f, (size_t)out[3] * 4, hipMemcpyDeviceToHost));
+    }
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_lba_apply_device(orbg_ctx *c, orbg_map *m, const int32_t *d_kf_slots,
+                                         int pose_cap, const int32_t *d_point_ids, int point_cap,
+                                         const orbg_edge *d_edges, const int32_t *d_edge_feat,
+                                         int edge_cap, const int32_t *d_counts,
+                                         const orbg_pose *d_poses, const double *d_points,
+                                         const uint8_t *d_erase, orbg_frustum_camera *d_cams_out,
+                                         int32_t *d_out)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_lba_caps_ok(pose_cap, point_cap, edge_cap))) return rc;
+    if ((pose_cap && (!d_kf_slots || !d_poses)) || (point_cap && (!d_point_ids || !d_points)) ||
+        (edge_cap && (!d_edges || !d_edge_feat || !d_erase)) || !d_counts || !d_out)
+        return set_err(ORBG_EINVAL, "NULL device array");
+    if ((rc = map_lba_ws(c, m, point_cap))) return rc;
+    if ((rc = orbg_map_rebuild(c, m))) return rc;  // the erasures read Observations() from the index
+    MapLbaWindow O{};
+    O.kf_slots = const_cast<int32_t *>(d_kf_slots);
+    O.poses = const_cast<orbg_pose *>(d_poses);
+    O.point_ids = const_cast<int32_t *>(d_point_ids);
+    O.points = const_cast<double *>(d_points);
+    O.edges = const_cast<orbg_edge *>(d_edges);
+    O.edge_feat = const_cast<int32_t *>(d_edge_feat);
+    O.pose_cap = pose_cap;
+    O.point_cap = point_cap;
+    O.edge_cap = edge_cap;
+    O.counts = const_cast<int32_t *>(d_counts);
+    if ((rc = launch_map_lba_apply(c->stream, m->D, m->LW, O, d_erase, d_cams_out, d_out, &c->prof)))
+        return set_err(rc, "k_lba apply launch failed");
+    m->dirty = m->touched = true;  // an erased observation is still in the index
+    if (point_cap == 0) return ORBG_OK;
+    return orbg_map_update_normal_and_depth_batch_device(c, m, m->LW.ids, point_cap);
+}
+
+extern "C" int orbg_map_lba_apply(orbg_ctx *c, orbg_map *m, const int32_t *kf_slots, int nlocal,
+                                  int npose, const int32_t *point_ids, int npoint,
+                                  const orbg_edge *edges, const int32_t *edge_feat, int nedge,
+                                  const orbg_pose *poses, const double *points, const uint8_t *erase,
+                                  orbg_frustum_camera *d_cams_out, int32_t *out)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (nlocal < 0 || npose < nlocal || npose > m->D.K)
+        return set_err(ORBG_EINVAL, "nlocal %d / npose %d outside 0 <= nlocal <= npose <= %d", nlocal, npose, m->D.K);
+    if ((rc = map_lba_caps_ok(npose, npoint, nedge))) return rc;
+    if ((npose && (!kf_slots || !poses)) || (npoint && (!point_ids || !points)) ||
+        (nedge && (!edges || !edge_feat || !erase)))
+        return set_err(ORBG_EINVAL, "NULL array");
+    for (int i = 0; i < npose; i++)
+        if ((rc = map_slot_ok(m, kf_slots[i]))) return rc;
+    for (int i = 0; i < npoint; i++)
+        if (point_ids[i] < 0 || point_ids[i] >= m->D.P)
+            return set_err(ORBG_EINVAL, "point id %d outside [0, %d)", point_ids[i], m->D.P);
+    for (int e = 0; e < nedge; e++)
+        if (edges[e].point < 0 || edges[e].point >= npoint || edges[e].pose < 0 ||
+            edges[e].pose >= npose || edge_feat[e] < 0 || edge_feat[e] >= m->D.cap)
+            return set_err(ORBG_EINVAL, "edge %d: point %d, pose %d or feature %d out of range", e,
+                           edges[e].point, edges[e].pose, edge_feat[e]);
+    const size_t np = (size_t)npose, nq = (size_t)npoint, ne = (size_t)nedge;
+    Layout L;
+    const size_t o_k = L.take(np * 4), o_p = L.take(np * sizeof(orbg_pose)), o_i = L.take(nq * 4);
+    const size_t o_x = L.take(nq * 24), o_e = L.take(ne * sizeof(orbg_edge)), o_f = L.take(ne * 4);
+    const size_t o_r = L.take(ne), o_h = L.take(32);  // counts [4], out [2]
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
+    const int32_t hdr[8] = {nlocal, npose, npoint, nedge, 0, 0, 0, 0};
+    hipStream_t st = c->stream;
+    if (np) {
+        HIPCHK(hipMemcpyAsync(b + o_k, kf_slots, np * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(b + o_p, poses, np * sizeof(orbg_pose), hipMemcpyHostToDevice, st));
+    }
+    if (nq) {
+        HIPCHK(hipMemcpyAsync(b + o_i, point_ids, nq * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(b + o_x, points, nq * 24, hipMemcpyHostToDevice, st));
+    }
+    if (ne) {
+        HIPCHK(hipMemcpyAsync(b + o_e, edges, ne * sizeof(orbg_edge), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(b + o_f, edge_feat, ne * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(b + o_r, erase, ne, hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(hipMemcpyAsync(b + o_h, hdr, 32, hipMemcpyHostToDevice, st));
+    int32_t *h = L.at<int32_t>(b, o_h);
+    if ((rc = orbg_map_lba_apply_device(c, m, L.at<int32_t>(b, o_k), npose, L.at<int32_t>(b, o_i), npoint,
+                                        L.at<orbg_edge>(b, o_e), L.at<int32_t>(b, o_f), nedge, h,
+                                        L.at<orbg_pose>(b, o_p), L.at<double>(b, o_x), b + o_r,
+                                        d_cams_out, h + 4)))
+        return rc;
+    int32_t o2[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(o2, h + 4, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    c->prof.collect();
+    if (out) {
+        out[0] = o2[0];
+        out[1] = o2[1];
+    }
+    return ORBG_OK;
+}
+
+// orbg_map_local_ba's window arrays, grown to the caps asked for
+static int map_lba_chain_ws(orbg_ctx *c, orbg_map *m, int pose_cap, int point_cap, int edge_cap)
+{
+    MapLbaWindow &B = m->LB;
+    if (m->d_lb && pose_cap <= B.pose_cap && point_cap <= B.point_cap && edge_cap <= B.edge_cap)
+        return ORBG_OK;
+    pose_cap = std::max(pose_cap, B.pose_cap);
+    point_cap = std::max(point_cap, B.point_cap);
+    edge_cap = std::max(edge_cap, B.edge_cap);
+    if (m->d_lb) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipFree(m->d_lb));
+        m->d_lb = nullptr;
+        B = MapLbaWindow{};
+    }
+    const size_t np = (size_t)pose_cap, nq = (size_t)point_cap, ne = (size_t)edge_cap;
+    Layout L;
+    const size_t o_k = L.take(np * 4), o_p = L.take(np * sizeof(orbg_pose)), o_i = L.take(nq * 4);
+    const size_t o_x = L.take(nq * 24), o_e = L.take(ne * sizeof(orbg_edge)), o_f = L.take(ne * 4);
+    const size_t o_r = L.take(ne), o_h = L.take(64);  // counts [4], status [4], out [2]
+    if (hipMalloc(&m->d_lb, L.total()) != hipSuccess) {
+        m->d_lb = nullptr;
+        return set_err(ORBG_ENOMEM, "Map: hipMalloc(%zu bytes) for the local BA window", L.total());
+    }
+    uint8_t *b = (uint8_t *)m->d_lb;
+    B.kf_slots = L.at<int32_t>(b, o_k);
+    B.poses = L.at<orbg_pose>(b, o_p);
+    B.point_ids = L.at<int32_t>(b, o_i);
+    B.points = L.at<double>(b, o_x);
+    B.edges = L.at<orbg_edge>(b, o_e);
+    B.edge_feat = L.at<int32_t>(b, o_f);
+    B.counts = L.at<int32_t>(b, o_h);
+    B.pose_cap = pose_cap;
+    B.point_cap = point_cap;
+    B.edge_cap = edge_cap;
+    m->d_lb_erase = b + o_r;
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_local_ba(orbg_ctx *c, orbg_map *m, int slot, const orbg_lm_control *control,
+                                 orbg_frustum_camera *d_cams_out, orbg_map_lba_report *report)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_slot_ok(m, slot))) return rc;
+    if (!report) return set_err(ORBG_EINVAL, "report is NULL");
+    if ((rc = map_attached(m))) return rc;
+    *report = orbg_map_lba_report{};
+    const MapDev &D = m->D;
+    const int64_t rows = (int64_t)D.K * D.cap;
+    if (!m->d_lb &&
+        (rc = map_lba_chain_ws(c, m, std::min(D.K, 128), (int)std::min<int64_t>({(int64_t)D.P, rows, 1 << 16}),
+                               (int)std::min<int64_t>(rows, 1 << 18))))
+        return rc;
+    hipStream_t st = c->stream;
+    int32_t h[8] = {0};
+    for (int pass = 0;; pass++) {
+        const MapLbaWindow &B = m->LB;
+        if ((rc = orbg_map_lba_window_device(c, m, slot, B.kf_slots, B.poses, B.pose_cap, B.point_ids,
+                                             B.points, B.point_cap, B.edges, B.edge_feat, B.edge_cap,
+                                             B.counts, B.counts + 4)))
+            return rc;
+        HIPCHK(hipMemcpyAsync(h, B.counts, 32, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (!(h[4] & ORBG_LBA_RANGE) || (h[4] & (ORBG_LBA_DEAD | ORBG_LBA_NO_POSE)) || pass) break;
+        if (h[2] > ORBG_LBA_MAX_POINTS) break;
+        if ((rc = map_lba_chain_ws(c, m, h[1] + h[1] / 4, std::min(h[2] + h[2] / 4, ORBG_LBA_MAX_POINTS),
+                                   h[3] + h[3] / 4)))
+            return rc;
+    }
+    const MapLbaWindow &B = m->LB;
+    if ((rc = map_lba_status(h[4], slot, h, B.pose_cap, B.point_cap, B.edge_cap))) return rc;
+    report->nlocal = h[0];
+    report->nfixed = h[1] - h[0];
+    report->npoints = h[2];
+    report->nedges = h[3];
+    if (control && control->force_stop && *control->force_stop != 0) {  // Optimizer.cc:853-855
+        report->stopped = 1;
+        c->prof.collect();
+        return ORBG_OK;
+    }
+    const int npose = h[1], npoint = h[2], nedge = h[3];
+    m->lb_erase.assign((size_t)std::max(nedge, 1), 0);
+    if (nedge) {
+        m->lb_edges.resize((size_t)nedge);
+        m->lb_fixed.resize((size_t)npose);
+        m->lb_fixed8.resize((size_t)npose);
+        HIPCHK(hipMemcpyAsync(m->lb_edges.data(), B.edges, (size_t)nedge * sizeof(orbg_edge), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(m->lb_fixed.data(), m->LW.fixed, (size_t)npose * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (int i = 0; i < npose; i++) m->lb_fixed8[i] = m->lb_fixed[i] ? 1 : 0;
+        orbg_lm_control K{};
+        if (control) K = *control;
+        K.d_last_chi2 = nullptr;
+        if ((rc = lba_optimize_device(c, B.poses, npose, B.points, npoint, m->lb_edges.data(), nedge,
+                                      m->lb_fixed8.data(), &K, nullptr, nullptr, m->lb_erase.data(),
+                                      &report->lba)))
+            return rc;
+    }
+    uint8_t *d_erase = m->d_lb_erase;  // the two counts go behind the window's status
+    if (nedge) HIPCHK(hipMemcpyAsync(d_erase, m->lb_erase.data(), (size_t)nedge, hipMemcpyHostToDevice, st));
+    if ((rc = orbg_map_lba_apply_device(c, m, B.kf_slots, B.pose_cap, B.point_ids, B.point_cap, B.edges,
+                                        B.edge_feat, B.edge_cap, B.counts, B.poses, B.points, d_erase,
+                                        d_cams_out, B.counts + 8)))
+        return rc;
+    int32_t o2[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(o2, B.counts + 8, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    c->prof.collect();
+    report->nerased = o2[0];
+    report->npoints_bad = o2[1];
     return ORBG_OK;
 }

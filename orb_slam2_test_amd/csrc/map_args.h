@@ -1,7 +1,7 @@
 // map_args.h -- device layout and launch arguments of the covisibility Map (map_kernels.hip:
 // KeyFrame::UpdateConnections, Tracking::UpdateLocalKeyFrames / UpdateLocalPoints,
 // MapPoint::UpdateNormalAndDepth; map_cull_kernels.hip; map_edit_kernels.hip;
-// map_loop_kernels.hip), shared with the
+// map_loop_kernels.hip, map_lba_kernels.hip), shared with the
 // host entry points (api_map.hip).
 #pragma once
 
@@ -244,5 +244,50 @@ int launch_map_apply_poses(hipStream_t st, const MapDev &M, int cur, const int32
 int launch_map_set_corrected(hipStream_t st, const MapDev &M, int first, int n, const int32_t *by,
                              const int32_t *ref);
 int launch_map_scatter_points(hipStream_t st, const MapDev &M, const float *pts, const int32_t *ref);
+
+// map_lba_kernels.hip: Optimizer::LocalBundleAdjustment's window and write-back
+// (src/Optimizer.cc:635-851, 943-978).  The map-owned marks of one call:
+#define ORBG_LBA_MAX_POINTS 0x7FFFE   // a window position is 19 bits of the fixed cameras' sort key
+struct MapLbaWs {
+    int32_t pcap;                     // entries of eoff / ids
+    int32_t *hdr;                     // [16] LBA_HDR_*
+    int32_t *lrank;                   // [K] rank among the local keyframes, -1 none, -2 local but bad
+    int32_t *ffirst;                  // [K] least window position of a local point the slot observes
+    int32_t *pidx;                    // [K] slot -> pose index, -1 = no vertex
+    int32_t *lslot;                   // [K] pose index -> slot
+    int32_t *fixed;                   // [K] pose index -> the vertex is fixed
+    int32_t *cnt;                     // [K + 1] points first listed per local keyframe, then offsets
+    int32_t *eoff;                    // [pcap + 1] edges per window point, then their offsets
+    int32_t *ids;                     // [pcap] Apply: the window's points, -1 behind them
+};
+#define LBA_HDR_NLOCAL 0
+#define LBA_HDR_NPOSE 1
+#define LBA_HDR_NPOINT 2
+#define LBA_HDR_NEDGE 3
+#define LBA_HDR_BITS 4                // ORBG_LBA_*
+#define LBA_HDR_NERASED 8             // Apply
+#define LBA_HDR_NBAD 9
+struct MapLbaWindow {
+    int32_t *kf_slots;                // [pose_cap]
+    orbg_pose *poses;                 // [pose_cap]
+    int32_t *point_ids;               // [point_cap]
+    double *points;                   // [point_cap][3]
+    orbg_edge *edges;                 // [edge_cap]
+    int32_t *edge_feat;               // [edge_cap]
+    int32_t pose_cap, point_cap, edge_cap;
+    int32_t *counts;                  // [4] nlocal, npose, npoint, nedge
+};
+struct MapLbaConst {
+    float inv_sigma2[16];             // mvInvLevelSigma2
+    double huber_mono, huber_stereo;  // (float)sqrt(5.991), (float)sqrt(7.815)
+};
+// status [4]: [0] = ORBG_LBA_* bits
+int launch_map_lba_window(hipStream_t st, const MapDev &M, const MapAttach &A, const MapLbaWs &W,
+                          int slot, const MapLbaWindow &O, const MapLbaConst &C, int32_t *status,
+                          Prof *prof);
+// out [2]: erased observations, points gone bad; cams_out may be NULL
+int launch_map_lba_apply(hipStream_t st, const MapDev &M, const MapLbaWs &W, const MapLbaWindow &O,
+                         const uint8_t *erase, orbg_frustum_camera *cams_out, int32_t *out,
+                         Prof *prof);
 
 }  // namespace orbg

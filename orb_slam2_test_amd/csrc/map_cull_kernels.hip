@@ -68,28 +68,6 @@ __device__ __forceinline__ CullLds cull_lds_of(int K, int bn)
     return L;
 }
 
-// MapPoint::SetBadFlag: bad, and out of every row that holds it
-__device__ __forceinline__ void cull_point_bad(const MapDev &M, int p)
-{
-    M.mp[p].flags &= ~ORBG_MP_VALID;
-    const int e1 = M.obs_off[p + 1];
-    for (int e = M.obs_off[p]; e < e1; e++) {
-        int u, j;
-        if (cull_obs(M, M.obs[e], p, &u, &j)) M.kf_points[(size_t)u * M.cap + j] = -1;
-    }
-}
-
-__device__ __forceinline__ int cull_nobs(const MapDev &M, int p)
-{
-    int nobs = 0;
-    const int e1 = M.obs_off[p + 1];
-    for (int e = M.obs_off[p]; e < e1; e++) {
-        int u, j;
-        if (cull_obs(M, M.obs[e], p, &u, &j)) nobs += cull_weight(M, u, j);
-    }
-    return nobs;
-}
-
 // nMPs and nRedundantObservations of slot t into out[0], out[1] (zeroed by the caller, behind a
 // barrier); the workgroup calls it, a barrier follows
 __device__ void cull_score(const MapDev &M, int t, int monocular, int *out)

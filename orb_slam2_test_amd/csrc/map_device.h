@@ -1,5 +1,5 @@
 // map_device.h -- what the Map's kernel files share (map_kernels.hip, map_cull_kernels.hip,
-// map_edit_kernels.hip): the workgroup size, the sort-key layout, the workgroup scan, the LDS
+// map_edit_kernels.hip, map_loop_kernels.hip, map_lba_kernels.hip): the workgroup size, the sort-key layout, the workgroup scan, the LDS
 // bitonic sort, the store of an ordered list and the test of an entry of a stale observation
 // index.  Every kernel file that includes it has its own map_smem.
 #pragma once
@@ -122,6 +122,39 @@ __device__ __forceinline__ bool cull_obs(const MapDev &M, uint32_t ob, int p, in
 __device__ __forceinline__ int cull_weight(const MapDev &M, int u, int j)
 {
     return (M.kf_feat[(size_t)u * M.cap + j] & ORBG_MAP_FEAT_STEREO) ? 2 : 1;
+}
+
+// MapPoint::SetBadFlag: bad, and out of every row that holds it
+__device__ __forceinline__ void cull_point_bad(const MapDev &M, int p)
+{
+    M.mp[p].flags &= ~ORBG_MP_VALID;
+    const int e1 = M.obs_off[p + 1];
+    for (int e = M.obs_off[p]; e < e1; e++) {
+        int u, j;
+        if (cull_obs(M, M.obs[e], p, &u, &j)) M.kf_points[(size_t)u * M.cap + j] = -1;
+    }
+}
+
+__device__ __forceinline__ int cull_nobs(const MapDev &M, int p)
+{
+    int nobs = 0;
+    const int e1 = M.obs_off[p + 1];
+    for (int e = M.obs_off[p]; e < e1; e++) {
+        int u, j;
+        if (cull_obs(M, M.obs[e], p, &u, &j)) nobs += cull_weight(M, u, j);
+    }
+    return nobs;
+}
+
+// Ow = -Rwc * tcw of a 3x4 float pose: the product in double, one rounding
+__device__ __forceinline__ void loop_centre(const float *T, float *O)
+{
+    for (int i = 0; i < 3; i++) {
+        double a = (double)T[i] * (double)T[3];
+        a += (double)T[4 + i] * (double)T[7];
+        a += (double)T[8 + i] * (double)T[11];
+        O[i] = (float)(-a);
+    }
 }
 
 static inline int last_rc() { return hipGetLastError() == hipSuccess ? ORBG_OK : ORBG_EIO; }

@@ -39,17 +39,6 @@
 
 namespace orbg {
 
-// Ow = -Rwc * tcw of a 3x4 float pose: the product in double, one rounding
-__device__ __forceinline__ void loop_centre(const float *T, float *O)
-{
-    for (int i = 0; i < 3; i++) {
-        double a = (double)T[i] * (double)T[3];
-        a += (double)T[4 + i] * (double)T[7];
-        a += (double)T[8 + i] * (double)T[11];
-        O[i] = (float)(-a);
-    }
-}
-
 __device__ __forceinline__ void loop_sim3_of_pose(const float *T, Sim3d *S)
 {
     double R[3][3];

@@ -3574,22 +3574,17 @@ extern "C" int orbg_ba_graph_optimize_ctl(orbg_ctx *c, orbg_ba_graph *g, orbg_po
 // Optimizer::LocalBundleAdjustment's optimisation (Optimizer.cc:853-935) on one window: see
 // include/orbg.h.  The host takes the decisions the reference takes on the host (the flag, the
 // outlier thresholds, isBad), every pass over the edges runs on the device.
-extern "C" int orbg_local_ba_optimize(orbg_ctx *c, orbg_pose *poses, int npose, double *points,
-                                      int npoint, const orbg_edge *edges, int nedge,
-                                      const orbg_lm_control *control,
-                                      int (*point_is_bad)(void *user, int point), void *user,
-                                      uint8_t *erase, orbg_lba_report *rep)
+namespace orbg {
+// orbg_local_ba_optimize's body on device-resident estimates: the graph from the host edge
+// records, optimize(5), the outlier pass, optimize(10) and the vToErase test.  fixed [npose]
+// (host) is the poses' flag; the estimates stay where they are.
+int lba_optimize_device(orbg_ctx *c, orbg_pose *d_poses, int npose, double *d_points, int npoint,
+                        const orbg_edge *edges, int nedge, const uint8_t *fixed,
+                        const orbg_lm_control *control,
+                        int (*point_is_bad)(void *user, int point), void *user, uint8_t *erase,
+                        orbg_lba_report *rep)
 {
-    if (!c) return set_err(ORBG_EINVAL, "ctx is NULL");
-    if (npose < 0 || npoint < 0 || nedge < 0) return set_err(ORBG_EINVAL, "negative size");
-    if ((npose && !poses) || (npoint && !points) || (nedge && (!edges || !erase)))
-        return set_err(ORBG_EINVAL, "NULL array");
     orbg_lba_report R{};
-    if (nedge == 0) {  // initializeOptimization of an empty graph fails: nothing optimised
-        if (rep) *rep = R;
-        return ORBG_OK;
-    }
-    HIPCHK(hipSetDevice(c->device));
     orbg_ba_graph *g = nullptr;
     int rc = orbg_ba_graph_create(c, edges, nedge, npose, npoint, &g);
     if (rc) return rc;
@@ -3603,27 +3598,20 @@ extern "C" int orbg_local_ba_optimize(orbg_ctx *c, orbg_pose *poses, int npose, 
             if (g) orbg_ba_graph_destroy(g);
         }
     } guard{g, &dmem};
-    const size_t ne = (size_t)nedge, np = (size_t)std::max(npose, 1), nq = (size_t)std::max(npoint, 1);
-    const size_t o_p = 0, o_q = al256(np * sizeof(orbg_pose)), o_c5 = o_q + al256(nq * 24),
-                 o_c10 = o_c5 + al256(ne * 8), o_ce = o_c10 + al256(ne * 8),
+    const size_t ne = (size_t)nedge;
+    const size_t o_c5 = 0, o_c10 = o_c5 + al256(ne * 8), o_ce = o_c10 + al256(ne * 8),
                  o_dk = o_ce + al256(ne * 8), o_end = o_dk + al256(ne);
     HIPCHK(hipMalloc((void **)&dmem, o_end));
-    orbg_pose *d_poses = (orbg_pose *)(dmem + o_p);
-    double *d_points = (double *)(dmem + o_q), *d_c5 = (double *)(dmem + o_c5),
-           *d_c10 = (double *)(dmem + o_c10), *d_ce = (double *)(dmem + o_ce);
+    double *d_c5 = (double *)(dmem + o_c5), *d_c10 = (double *)(dmem + o_c10),
+           *d_ce = (double *)(dmem + o_ce);
     uint8_t *d_dk = dmem + o_dk;
     hipStream_t st = c->stream;
-    if (npose)
-        HIPCHK(hipMemcpyAsync(d_poses, poses, (size_t)npose * sizeof(orbg_pose), hipMemcpyHostToDevice, st));
-    if (npoint)
-        HIPCHK(hipMemcpyAsync(d_points, points, (size_t)npoint * 24, hipMemcpyHostToDevice, st));
-    std::vector<uint8_t> fixed((size_t)std::max(npose, 1), 0), active(ne), robust(ne);
-    for (int i = 0; i < npose; i++) fixed[i] = poses[i].fixed ? 1 : 0;
+    std::vector<uint8_t> active(ne), robust(ne);
     for (size_t e = 0; e < ne; e++) {
         active[e] = edges[e].active ? 1 : 0;
         robust[e] = edges[e].robust ? 1 : 0;
     }
-    if ((rc = orbg_ba_graph_schur_plan(c, g, fixed.data()))) return rc;
+    if ((rc = orbg_ba_graph_schur_plan(c, g, fixed))) return rc;
     // the chi2 g2o's edges would hold if optimize(5) ran no iteration: the initial estimates'
     if ((rc = orbg_ba_graph_errors(c, g, d_poses, d_points, nullptr, d_c5, nullptr, nullptr))) return rc;
     orbg_lm_control K{};
@@ -3679,12 +3667,54 @@ extern "C" int orbg_local_ba_optimize(orbg_ctx *c, orbg_pose *poses, int npose, 
             R.n_erase++;
         }
     }
+    if (rep) *rep = R;
+    return ORBG_OK;
+}
+}  // namespace orbg
+
+extern "C" int orbg_local_ba_optimize(orbg_ctx *c, orbg_pose *poses, int npose, double *points,
+                                      int npoint, const orbg_edge *edges, int nedge,
+                                      const orbg_lm_control *control,
+                                      int (*point_is_bad)(void *user, int point), void *user,
+                                      uint8_t *erase, orbg_lba_report *rep)
+{
+    if (!c) return set_err(ORBG_EINVAL, "ctx is NULL");
+    if (npose < 0 || npoint < 0 || nedge < 0) return set_err(ORBG_EINVAL, "negative size");
+    if ((npose && !poses) || (npoint && !points) || (nedge && (!edges || !erase)))
+        return set_err(ORBG_EINVAL, "NULL array");
+    if (nedge == 0) {  // initializeOptimization of an empty graph fails: nothing optimised
+        if (rep) *rep = orbg_lba_report{};
+        return ORBG_OK;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    uint8_t *dmem = nullptr;
+    struct Guard {
+        uint8_t **m;
+        ~Guard()
+        {
+            if (*m) hipFree(*m);
+        }
+    } guard{&dmem};
+    const size_t np = (size_t)std::max(npose, 1), nq = (size_t)std::max(npoint, 1);
+    const size_t o_q = al256(np * sizeof(orbg_pose)), o_end = o_q + al256(nq * 24);
+    HIPCHK(hipMalloc((void **)&dmem, o_end));
+    orbg_pose *d_poses = (orbg_pose *)dmem;
+    double *d_points = (double *)(dmem + o_q);
+    hipStream_t st = c->stream;
+    if (npose)
+        HIPCHK(hipMemcpyAsync(d_poses, poses, (size_t)npose * sizeof(orbg_pose), hipMemcpyHostToDevice, st));
+    if (npoint)
+        HIPCHK(hipMemcpyAsync(d_points, points, (size_t)npoint * 24, hipMemcpyHostToDevice, st));
+    std::vector<uint8_t> fixed((size_t)std::max(npose, 1), 0);
+    for (int i = 0; i < npose; i++) fixed[i] = poses[i].fixed ? 1 : 0;
+    int rc = lba_optimize_device(c, d_poses, npose, d_points, npoint, edges, nedge, fixed.data(),
+                                 control, point_is_bad, user, erase, rep);
+    if (rc) return rc;
     if (npose)
         HIPCHK(hipMemcpyAsync(poses, d_poses, (size_t)npose * sizeof(orbg_pose), hipMemcpyDeviceToHost, st));
     if (npoint)
         HIPCHK(hipMemcpyAsync(points, d_points, (size_t)npoint * 24, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    if (rep) *rep = R;
     return ORBG_OK;
 }
 

@@ -388,6 +388,14 @@ int scratch(orbg_ctx *c, size_t bytes, void **p);
 // (ev_caller), ahead of a write to a caller's buffer on `mstream`
 hipError_t order_after_caller(orbg_ctx *c);
 
+// orbg_api.hip: orbg_local_ba_optimize's body on device-resident estimates (fixed [npose] and
+// the edge records on the host, erase [nedge] out); api_map.hip runs it on the Map's window
+int lba_optimize_device(orbg_ctx *c, orbg_pose *d_poses, int npose, double *d_points, int npoint,
+                        const orbg_edge *edges, int nedge, const uint8_t *fixed,
+                        const orbg_lm_control *control,
+                        int (*point_is_bad)(void *user, int point), void *user, uint8_t *erase,
+                        orbg_lba_report *rep);
+
 // Byte layout of the buffers of an entry point on host arrays: take() hands out the offsets
 // of 256-byte-aligned sub-buffers (an empty array still gets 256 bytes of its own, so it
 // never aliases its neighbour), then one block of total() bytes is acquired.

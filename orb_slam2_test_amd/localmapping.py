@@ -85,18 +85,23 @@ class LocalMapping:
         return n.value, x[:a.n].copy(), st[:a.n].copy()
 
     def RunOnMap(self, m, slot, current_kf_id, monocular, recent, create_new_map_points=None,
-                 local_bundle_adjustment=None, th=3.0):
+                 local_bundle_adjustment=None, th=3.0, stop_flag=None, d_cams_out=None):
         """One keyframe's pass of LocalMapping::Run (src/LocalMapping.cc:55-120) over a device
         Map `m` whose row `slot` ProcessNewKeyFrame has uploaded: MapPointCulling of `recent`,
         create_new_map_points(recent) -> recent (the caller's: the triangulation above, then
         Map.SetPoints and Map.AddObservations for the new ids), SearchInNeighbors,
-        local_bundle_adjustment() (the caller's), KeyFrameCulling.  Every step edits the one
-        table in HBM.  Returns (mlpRecentAddedMapPoints, vpTargetKFs, the nFused of each
+        local bundle adjustment, KeyFrameCulling.  local_bundle_adjustment: True runs
+        m.LocalBundleAdjustment(slot, stop_flag, d_cams_out) (Optimizer::LocalBundleAdjustment on
+        the table: d_cams_out keeps the attached cameras' Tcw current for the next keyframe's
+        SearchInNeighbors), a callable is called (the caller's own), None skips the step.  Every
+        step edits the one table in HBM.  Returns (mlpRecentAddedMapPoints, vpTargetKFs, the nFused of each
         target's Fuse, the second pass's, the CULL_RECORD_DTYPE records)."""
         recent, _ = m.MapPointCulling(recent, current_kf_id, monocular)
         if create_new_map_points is not None:
             recent = create_new_map_points(recent)
         targets, nfused, second = m.SearchInNeighbors(slot, current_kf_id, monocular, th)
-        if local_bundle_adjustment is not None:
+        if local_bundle_adjustment is True:
+            self.lba_report = m.LocalBundleAdjustment(slot, stop_flag, d_cams_out)
+        elif local_bundle_adjustment is not None:
             local_bundle_adjustment()
         return recent, targets, nfused, second, m.KeyFrameCulling(slot, monocular)

@@ -30,6 +30,8 @@ ascending slot (include/orbg.h).
     Siw, Tiw, _ = OptimizeEssentialGraph(Scw_v, Snc_v, edges, fixed, bFixScale)
     m.ApplyCorrection(cur, vs, Scw_v, Siw, Tiw); m.AddLoopEdge(loop, cur)
     report, counts = m.CorrectLoop(cur, loop, Scw, matched, loop_points, bFixScale)  # all of it
+    report = m.LocalBundleAdjustment(slot, stop_flag)         # Optimizer.cc:633-979 on the table
+    w = m.LbaWindow(slot); m.LbaApply(w, poses, points, erase)  # its two ends, one at a time
 """
 import ctypes as C
 
@@ -716,3 +718,82 @@ class Map:
         keys = ("members", "fusion_replaced", "fusion_added", "fused", "replaced", "pairs",
                 "vertices", "edges")
         return _lm_report(rep), dict(zip(keys, cnt.tolist()))
+
+    # ---- Optimizer::LocalBundleAdjustment: the window, the write-back, all of it ----
+    def LbaWindow(self, slot, pose_cap=None, point_cap=None, edge_cap=None):
+        """The window of Optimizer::LocalBundleAdjustment(slot) (Optimizer.cc:635-851) as a dict:
+        kf_slots (nlocal local keyframes, then the fixed cameras), nlocal, poses POSE_DTYPE,
+        point_ids, points float64 [n, 3], edges EDGE_DTYPE, edge_feat (the keypoint index of each
+        edge).  The keyframe data must be attached (AttachKeyFrames) and the poses set."""
+        K = self.max_keyframes
+        pc = K if pose_cap is None else int(pose_cap)
+        qc = min(self.max_points, K * self.kf_cap, 524286) if point_cap is None else int(point_cap)
+        ec = K * self.kf_cap if edge_cap is None else int(edge_cap)
+        ks, po = np.zeros(pc, np.int32), np.zeros(pc, L.POSE_DTYPE)
+        ids, pts = np.zeros(qc, np.int32), np.zeros((qc, 3), np.float64)
+        ed, ef = np.zeros(ec, L.EDGE_DTYPE), np.zeros(ec, np.int32)
+        cnt = np.zeros(4, np.int32)
+        rc = L.lib().orbg_map_lba_window(self._c(), self._h, int(slot), L.ptr(ks), L.ptr(po), pc,
+                                         L.ptr(ids), L.ptr(pts), qc, L.ptr(ed), L.ptr(ef), ec,
+                                         L.ptr(cnt))
+        self.lba_counts = cnt.tolist()      # the full counts, also after ORBG_ERANGE
+        L.check(rc, "orbg_map_lba_window")
+        nl, npo, nq, ne = cnt.tolist()
+        return dict(kf_slots=ks[:npo], nlocal=nl, poses=po[:npo], point_ids=ids[:nq],
+                    points=pts[:nq], edges=ed[:ne], edge_feat=ef[:ne])
+
+    def lba_window_device(self, slot, d_kf_slots, d_poses, pose_cap, d_point_ids, d_points,
+                          point_cap, d_edges, d_edge_feat, edge_cap, d_counts, d_status, ctx=None):
+        L.check(L.lib().orbg_map_lba_window_device(
+            self._c(ctx), self._h, int(slot), d_kf_slots, d_poses, int(pose_cap), d_point_ids,
+            d_points, int(point_cap), d_edges, d_edge_feat, int(edge_cap), d_counts, d_status),
+            "orbg_map_lba_window_device")
+
+    def LbaApply(self, window, poses, points, erase, d_cams_out=None):
+        """Optimizer.cc:943-978 on the table for a window of LbaWindow: the flagged observations
+        erased (mono edges first, then stereo), SetPose of the local keyframes, the window
+        points' positions and UpdateNormalAndDepth; d_cams_out (a device pointer, FRUSTUM_DTYPE
+        per slot) gets the local keyframes' new Tcw.  Returns (observations erased, points gone
+        bad)."""
+        ks, ids = _i32(window["kf_slots"]), _i32(window["point_ids"])
+        ed = np.ascontiguousarray(window["edges"], L.EDGE_DTYPE).reshape(-1)
+        ef = _i32(window["edge_feat"])
+        po = np.ascontiguousarray(poses, L.POSE_DTYPE).reshape(-1)
+        pts = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+        er = np.ascontiguousarray(np.asarray(erase) != 0, np.uint8).reshape(-1)
+        if len(po) != len(ks) or len(pts) != len(ids) or not (len(ed) == len(ef) == len(er)):
+            raise ValueError("the window and the estimates differ in length")
+        out = np.zeros(2, np.int32)
+        L.check(L.lib().orbg_map_lba_apply(self._c(), self._h, L.ptr(ks), int(window["nlocal"]),
+                                           len(ks), L.ptr(ids), len(ids), L.ptr(ed), L.ptr(ef),
+                                           len(ed), L.ptr(po), L.ptr(pts), L.ptr(er), d_cams_out,
+                                           L.ptr(out)), "orbg_map_lba_apply")
+        return int(out[0]), int(out[1])
+
+    def lba_apply_device(self, d_kf_slots, pose_cap, d_point_ids, point_cap, d_edges, d_edge_feat,
+                         edge_cap, d_counts, d_poses, d_points, d_erase, d_cams_out, d_out,
+                         ctx=None):
+        L.check(L.lib().orbg_map_lba_apply_device(
+            self._c(ctx), self._h, d_kf_slots, int(pose_cap), d_point_ids, int(point_cap), d_edges,
+            d_edge_feat, int(edge_cap), d_counts, d_poses, d_points, d_erase, d_cams_out, d_out),
+            "orbg_map_lba_apply_device")
+
+    def LocalBundleAdjustment(self, slot, stop_flag=None, d_cams_out=None, post_iteration=None):
+        """Optimizer::LocalBundleAdjustment(slot, stop_flag, map) in one call: the window, the
+        stop check, optimize(5) / the outlier pass / optimize(10) on the device estimates, the
+        write-back.  stop_flag: a one-byte host buffer (numpy uint8 [1] or ctypes c_bool), polled
+        as g2o polls it; post_iteration(it): a callback after every LM iteration (it may raise
+        the flag).  Returns the report as a dict (stopped = 1: the flag was up, nothing written)."""
+        from .optimizer import _lm_report, _stop_flag_address
+        rep, ctl = L.MapLbaReport(), L.LmControl()
+        ctl.force_stop = _stop_flag_address(stop_flag)
+        pi = L.LM_POST_ITERATION((lambda u, it: post_iteration(it)) if post_iteration else 0)
+        ctl.post_iteration = pi
+        L.check(L.lib().orbg_map_local_ba(self._c(), self._h, int(slot), C.byref(ctl), d_cams_out,
+                                          C.byref(rep)), "orbg_map_local_ba")
+        out = {k: int(getattr(rep, k)) for k in ("nlocal", "nfixed", "npoints", "nedges", "nerased",
+                                                 "npoints_bad", "stopped")}
+        out.update(lm=[_lm_report(rep.lba.lm[0]), _lm_report(rep.lba.lm[1])],
+                   do_more=int(rep.lba.do_more), n_outliers=int(rep.lba.n_outliers),
+                   n_erase=int(rep.lba.n_erase))
+        return out
