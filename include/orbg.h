@@ -1537,8 +1537,8 @@ int orbg_map_get_point_replaced(orbg_ctx *ctx, orbg_map *map, int first, int n, 
 int orbg_map_get_point_descriptors(orbg_ctx *ctx, orbg_map *map, int first, int n, uint8_t *desc);
 /* Attaches the keyframes' data: *kfs is copied, its device arrays (rows of `cap`) and d_cams
  * are indexed by slot and must stay valid while attached; desc, kps, uright (may be NULL) and
- * counts are read, has_mp and fv_* are not.  d_cams[slot] = the keyframe's pose, intrinsics
- * and bounds as orbg_fuse reads them.  kfs == NULL detaches.  The calls below return
+ * counts are read, has_mp is not, fv_* only by orbg_map_create_new_points*.  d_cams[slot] =
+ * the keyframe's pose, intrinsics and bounds as orbg_fuse reads them.  kfs == NULL detaches.  The calls below return
  * ORBG_EINVAL while nothing is attached (orbg_map_add_observations* needs nothing attached). */
 int orbg_map_attach_keyframes(orbg_ctx *ctx, orbg_map *map, const orbg_keyframes *kfs, int cap,
                               const orbg_frustum_camera *d_cams);
@@ -1611,6 +1611,96 @@ int orbg_map_search_in_neighbors_device(orbg_ctx *ctx, orbg_map *map, int slot, 
 int orbg_map_search_in_neighbors(orbg_ctx *ctx, orbg_map *map, int slot, int current_kf_id,
                                  int monocular, float th, int32_t *targets, int target_cap,
                                  int32_t *ntargets, int32_t *nfused);
+
+/* ---- LocalMapping::CreateNewMapPoints and ProcessNewKeyFrame on the Map ----
+ * Beside orbg_map_attach_keyframes (whose fv_nodes / fv_off / fv_feats / nfv are read here, in
+ * orbg_search_for_triangulation_batch_device's layout: ORBG_EINVAL if one is NULL) the rest of
+ * what the triangulation reads, indexed by slot with the attached `cap`, not owned: mvKeys
+ * d_kps_raw (NULL: mvKeysUn), mvDepth d_depth (required when uright is attached) and
+ * d_kf_cams[slot], of which only fx, fy, cx, cy, invfx, invfy, mb, mbf are read.  The pose is the
+ * Map's stored Tcw (orbg_map_set_keyframe_poses) and the camera centre its stored Ow, which
+ * orbg_map_lba_apply_device keeps current: there is no further copy of a pose.  d_kf_cams ==
+ * NULL detaches. */
+int orbg_map_attach_keyframe_geometry(orbg_ctx *ctx, orbg_map *map, const orbg_keypoint *d_kps_raw,
+                                      const float *d_depth, const orbg_kf_camera *d_kf_cams);
+#define ORBG_CNP_POINT_RANGE 1    /* an id reached max_points */
+#define ORBG_CNP_RECENT_RANGE 2   /* a d_recent position reached recent_cap */
+#define ORBG_CNP_DEAD 4           /* the slot is not live: nothing done */
+#define ORBG_CNP_NO_POSE 8        /* the slot has no stored pose: nothing done */
+/* LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:293-576) with mpCurrentKeyFrame = slot,
+ * mnId = current_kf_id.  Neighbours: the first nn = monocular ? 20 : 10 entries of the slot's
+ * stored ordered list (no bad check, as the reference); d_neigh[i] (-1 past the count).  From
+ * neighbour i > 0 on CheckNewKeyFrames() is d_abort (may be NULL; any device-readable address,
+ * mapped pinned host memory included), read once per neighbour by one lane and latched: once
+ * non-zero that neighbour and all later ones get status 2.  d_neigh_status[i]: 0 processed;
+ * 1 skipped by the baseline test (baseline = cv::norm of the stored centres' difference; stereo:
+ * baseline < mb of the neighbour; monocular: baseline / ComputeSceneMedianDepth(2) < 0.01, the
+ * depths z = Tcw row 2 . X + tz of every row entry of the neighbour, accumulated in double in
+ * order, sorted, element (n - 1) / 2); 2 aborted; 3 a dead neighbour, one without a stored pose
+ * or, monocular, with an empty row (a departure: the reference indexes an empty vector there).
+ * Per processed neighbour in list order: ComputeF12, SearchForTriangulation(cur, nb, F12, .,
+ * false) of ORBmatcher(0.6, false) with has_mp = (row[idx] >= 0) of both rows as they stand at
+ * that moment, the triangulation (the three kernels of orbg_triangulation_geometry /
+ * orbg_search_for_triangulation / orbg_triangulate_batch_device, unchanged), then the insertion
+ * in idx1 order: point k of the whole call gets id first_id + k, the record (x3d,
+ * ORBG_MP_VALID), mpRefKF = slot, mnFirstKFid = current_kf_id, mnVisible = mnFound = 1,
+ * mpReplaced = -1, mnCorrected* = 0, the id in row[slot][idx1] and row[nb][idx2], and the id
+ * appended to d_recent at d_nrecent[0] (in / out).  The reference never sets vbMatched2, so two
+ * idx1 may match one idx2: both points are created and, as pKF2->AddMapPoint overwrites, the
+ * later one keeps the neighbour's feature (a departure: the earlier point then has no
+ * observation in the neighbour, where the reference leaves a one-sided one).
+ * ComputeDistinctiveDescriptors and UpdateNormalAndDepth of the new points run once, after the
+ * last neighbour (nothing in between reads them).  W, the ordered lists and the parents do not
+ * change.  d_nmatches[i] = the search's return value, d_nnew[i] = points created, d_tri_status
+ * (may be NULL) [20][kf_cap of the Map] = the ORBG_TRI_* per idx1.  An id >= max_points or a
+ * d_recent position >= recent_cap: that point and all later ones of the call are not created
+ * and no row is touched for them (the feature of the slot is still taken as matched by the
+ * later neighbours' searches, so that d_out[2] is exact).  d_out: [0] neighbours, [1] points
+ * created, [2] points a large enough cap would have created, [3] ORBG_CNP_* bits.  Precondition, not checked: the ids
+ * from first_id on are unused.  The device form never synchronises and allocates nothing after
+ * its first call on a map (the workspace belongs to the map): the launches are sized by the
+ * bounds (20 neighbours, kf_cap features) and every length stays on the device: 4 launches and
+ * one 4-byte memset per neighbour slot, nn of them whatever the list holds, plus three of its
+ * own and those of the closing index rebuild, descriptors and normals.
+ * ORBG_EINVAL: slot out of range, first_id < 0, nothing / no geometry attached, fv_* NULL. */
+int orbg_map_create_new_points_device(orbg_ctx *ctx, orbg_map *map, int slot, int current_kf_id,
+                                      int monocular, int first_id, const int32_t *d_abort,
+                                      int32_t *d_recent, int recent_cap, int32_t *d_nrecent,
+                                      int32_t *d_neigh, int32_t *d_neigh_status,
+                                      int32_t *d_nmatches, int32_t *d_nnew, int8_t *d_tri_status,
+                                      int32_t *d_out);
+/* host arrays (abort: one int32 or NULL, read when the call starts; *nrecent in / out;
+ * tri_status may be NULL); synchronises.  ORBG_ERANGE for the two range bits (everything is
+ * written), ORBG_EINVAL for a dead slot or one without a pose. */
+int orbg_map_create_new_points(orbg_ctx *ctx, orbg_map *map, int slot, int current_kf_id,
+                               int monocular, int first_id, const int32_t *abort, int32_t *recent,
+                               int recent_cap, int32_t *nrecent, int32_t *neigh,
+                               int32_t *neigh_status, int32_t *nmatches, int32_t *nnew,
+                               int8_t *tri_status, int32_t *out);
+/* The table side of LocalMapping::ProcessNewKeyFrame (src/LocalMapping.cc:164-220) for one
+ * keyframe: the row (d_point_ids / d_octaves / d_feat_flags [n]; d_feat_flags may be NULL), the
+ * pose d_Tcw [12], mnId and the ORBG_MAP_KF_* flags are stored as orbg_map_set_keyframes_device,
+ * _features_device and _poses_device store them (the centre is -Rcw^T tcw).  An id that is bad
+ * or out of range is stored as -1 (a departure: the reference leaves the bad pointer in
+ * mvpMapPoints and every reader skips it).  For each good entry in feature order:
+ * d_in_keyframe[i] != 0 (pMP->IsInKeyFrame(pKF) as Tracking left it; NULL: all 0; the table
+ * cannot know, the row is the observation set) appends the id to d_recent at d_nrecent[0];
+ * otherwise the point's UpdateNormalAndDepth and ComputeDistinctiveDescriptors run once the row
+ * is in.  Then UpdateConnections(slot).  d_out: [0] ids appended, [1] points updated, [2] ids
+ * a large enough recent_cap would have appended, [3] ORBG_CNP_RECENT_RANGE or 0.  Needs the
+ * keyframe data attached (the slot's descriptors included).  Never synchronises. */
+int orbg_map_process_new_keyframe_device(orbg_ctx *ctx, orbg_map *map, int slot,
+                                         const int32_t *d_point_ids, const uint8_t *d_octaves,
+                                         const uint8_t *d_feat_flags, int n, const float *d_Tcw,
+                                         int mnid, int kf_flags, const uint8_t *d_in_keyframe,
+                                         int32_t *d_recent, int recent_cap, int32_t *d_nrecent,
+                                         int32_t *d_out);
+/* host arrays; synchronises.  ORBG_ERANGE for the range bit. */
+int orbg_map_process_new_keyframe(orbg_ctx *ctx, orbg_map *map, int slot, const int32_t *point_ids,
+                                  const uint8_t *octaves, const uint8_t *feat_flags, int n,
+                                  const float *Tcw, int mnid, int kf_flags,
+                                  const uint8_t *in_keyframe, int32_t *recent, int recent_cap,
+                                  int32_t *nrecent, int32_t *out);
 
 /* ---------------- ORBmatcher::SearchByBoW(KeyFrame*, Frame&) ---------------- */
 /* One side of SearchByBoW pairs, device memory, in orbg_bow_transform_batch_device's layout

@@ -21,6 +21,7 @@ ORBG_ENOMEM = -12
 ORBG_EINVAL = -22
 ORBG_ERANGE = -34
 ORBG_ENOTSUP = -95
+CNP_POINT_RANGE, CNP_RECENT_RANGE, CNP_DEAD, CNP_NO_POSE = 1, 2, 4, 8   # orbg_map_create_new_points
 
 RESIZE_SCALAR, RESIZE_SSE2_16_4, RESIZE_SIMD_16_8 = 0, 4, 8
 SINCOS_GLIBC, SINCOS_PINNED = 0, 1
@@ -541,6 +542,15 @@ def lib():
                                             vp]),
         "orbg_map_lba_apply": (i32, [vp, vp, vp, i32, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
         "orbg_map_local_ba": (i32, [vp, vp, i32, P(LmControl), vp, P(MapLbaReport)]),
+        "orbg_map_attach_keyframe_geometry": (i32, [vp, vp, vp, vp, vp]),
+        "orbg_map_create_new_points_device": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp,
+                                                    vp, vp, vp, vp, vp]),
+        "orbg_map_create_new_points": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp,
+                                             vp, vp, vp]),
+        "orbg_map_process_new_keyframe_device": (i32, [vp, vp, i32, vp, vp, vp, i32, vp, i32, i32, vp,
+                                                       vp, i32, vp, vp]),
+        "orbg_map_process_new_keyframe": (i32, [vp, vp, i32, vp, vp, vp, i32, vp, i32, i32, vp, vp,
+                                                i32, vp, vp]),
         "orbg_sim3_ransac_iterations": (i32, [C.c_double, i32, i32, i32]),
         "orbg_sim3_solve": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
         "orbg_sim3_solve_batch_device": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp,

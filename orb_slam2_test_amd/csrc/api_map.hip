@@ -33,6 +33,9 @@ struct orbg_map {
     MapLbaWindow LB{};           // orbg_map_local_ba's window, grown on demand
     void *d_lb = nullptr;
     uint8_t *d_lb_erase = nullptr;  // [edge_cap] the vToErase flags of that window
+    MapGeom geom{};              // orbg_map_attach_keyframe_geometry: not owned
+    MapCreateWs CW{};            // CreateNewMapPoints / ProcessNewKeyFrame workspace, allocated at the first call
+    void *d_cw = nullptr;
     std::vector<orbg_edge> lb_edges;           // its edge records, fixed flags and vToErase on the host
     std::vector<int32_t> lb_fixed;
     std::vector<uint8_t> lb_fixed8, lb_erase;
@@ -186,6 +189,7 @@ extern "C" void orbg_map_destroy(orbg_map *m)
     if (m->d_ap) hipFree(m->d_ap);
     if (m->d_lw) hipFree(m->d_lw);
     if (m->d_lb) hipFree(m->d_lb);
+    if (m->d_cw) hipFree(m->d_cw);
     if (m->d_mem) hipFree(m->d_mem);
     delete m;
 }
@@ -1295,6 +1299,294 @@ extern "C" int orbg_map_search_in_neighbors(orbg_ctx *c, orbg_map *m, int slot, 
     c->prof.collect();
     *ntargets = nt;
     if (nt > target_cap) return set_err(ORBG_ERANGE, "%d target entries (target_cap %d)", nt, target_cap);
+    return ORBG_OK;
+}
+
+// ---------------------------------------------------------------------------
+// LocalMapping::CreateNewMapPoints / ProcessNewKeyFrame on the Map (map_create_kernels.hip)
+// ---------------------------------------------------------------------------
+extern "C" int orbg_map_attach_keyframe_geometry(orbg_ctx *c, orbg_map *m,
+                                                 const orbg_keypoint *d_kps_raw,
+                                                 const float *d_depth,
+                                                 const orbg_kf_camera *d_kf_cams)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (!d_kf_cams && (d_kps_raw || d_depth))
+        return set_err(ORBG_EINVAL, "NULL d_kf_cams beside other arrays");
+    m->geom.kps_raw = d_kps_raw;
+    m->geom.depth = d_depth;
+    m->geom.cams = d_kf_cams;
+    return ORBG_OK;
+}
+
+// the workspace of CreateNewMapPoints / ProcessNewKeyFrame for the attached row length
+static int map_create_ws(orbg_ctx *c, orbg_map *m)
+{
+    const int acap = m->att.cap;
+    if (m->d_cw && m->CW.acap == acap) return ORBG_OK;
+    if (m->d_cw) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipFree(m->d_cw));
+        m->d_cw = nullptr;
+        m->CW = MapCreateWs{};
+    }
+    const size_t K = (size_t)m->D.K, a = (size_t)acap, cap = (size_t)m->D.cap;
+    Layout L;
+    const size_t o_h = L.take(16 * 4), o_1 = L.take(ORBG_CNP_MAX_NEIGH * 4);
+    const size_t o_2 = L.take(ORBG_CNP_MAX_NEIGH * 4), o_s = L.take(ORBG_CNP_MAX_NEIGH * 4);
+    const size_t o_c = L.take(K * 4), o_f = L.take(K * 4), o_k = L.take(K * sizeof(orbg_kf_camera));
+    const size_t o_m = L.take(K * a), o_g = L.take(ORBG_CNP_MAX_NEIGH * sizeof(orbg_triangulation_pair));
+    const size_t o_ma = L.take(a * 4), o_nm = L.take(4), o_x = L.take(a * 12), o_t = L.take(a);
+    const size_t o_nn = L.take(4), o_i = L.take((cap + 1) * 4), o_r = L.take(cap * 4), o_ce = L.take(12);
+    const size_t o_v = L.take(a);
+    if (hipMalloc(&m->d_cw, L.total()) != hipSuccess) {
+        m->d_cw = nullptr;
+        return set_err(ORBG_ENOMEM, "Map: hipMalloc(%zu bytes) for the CreateNewMapPoints workspace", L.total());
+    }
+    HIPCHK(hipMemsetAsync(m->d_cw, 0, L.total(), c->stream));
+    uint8_t *b = (uint8_t *)m->d_cw;
+    MapCreateWs &W = m->CW;
+    W.acap = acap;
+    W.hdr = L.at<int32_t>(b, o_h);
+    W.kf1 = L.at<int32_t>(b, o_1);
+    W.kf2 = L.at<int32_t>(b, o_2);
+    W.nstat = L.at<int32_t>(b, o_s);
+    W.counts = L.at<int32_t>(b, o_c);
+    W.nfv = L.at<int32_t>(b, o_f);
+    W.cams = L.at<orbg_kf_camera>(b, o_k);
+    W.has_mp = b + o_m;
+    W.geo = L.at<orbg_triangulation_pair>(b, o_g);
+    W.match = L.at<int32_t>(b, o_ma);
+    W.nm = L.at<int32_t>(b, o_nm);
+    W.x3d = L.at<float>(b, o_x);
+    W.tst = L.at<int8_t>(b, o_t);
+    W.nnew = L.at<int32_t>(b, o_nn);
+    W.ids = L.at<int32_t>(b, o_i);
+    W.row = L.at<int32_t>(b, o_r);
+    W.centre = L.at<float>(b, o_ce);
+    W.virt = b + o_v;
+    return ORBG_OK;
+}
+
+// ComputeDistinctiveDescriptors and UpdateNormalAndDepth of W.ids (their count behind them)
+static int map_create_update(orbg_ctx *c, orbg_map *m)
+{
+    const MapCreateWs &W = m->CW;
+    int rc = map_distinctive(c, m, W.ids, m->D.cap, W.ids + m->D.cap);
+    if (rc) return rc;
+    return orbg_map_update_normal_and_depth_batch_device(c, m, W.ids, m->D.cap);
+}
+
+extern "C" int orbg_map_create_new_points_device(orbg_ctx *c, orbg_map *m, int slot,
+                                                 int current_kf_id, int monocular, int first_id,
+                                                 const int32_t *d_abort, int32_t *d_recent,
+                                                 int recent_cap, int32_t *d_nrecent,
+                                                 int32_t *d_neigh, int32_t *d_neigh_status,
+                                                 int32_t *d_nmatches, int32_t *d_nnew,
+                                                 int8_t *d_tri_status, int32_t *d_out)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_slot_ok(m, slot))) return rc;
+    if ((rc = map_attached(m))) return rc;
+    if (!m->geom.cams)
+        return set_err(ORBG_EINVAL, "no keyframe geometry attached (orbg_map_attach_keyframe_geometry)");
+    const orbg_keyframes &ak = m->att.kfs;
+    if (!ak.fv_nodes || !ak.fv_off || !ak.fv_feats || !ak.nfv)
+        return set_err(ORBG_EINVAL, "the attached keyframes carry no FeatureVector (fv_* NULL)");
+    if (ak.uright && !m->geom.depth) return set_err(ORBG_EINVAL, "mvuRight attached without mvDepth");
+    if (first_id < 0 || recent_cap < 0) return set_err(ORBG_EINVAL, "negative first_id / recent_cap");
+    if (!d_nrecent || !d_neigh || !d_neigh_status || !d_nmatches || !d_nnew || !d_out ||
+        (recent_cap && !d_recent))
+        return set_err(ORBG_EINVAL, "NULL device array");
+    if ((rc = map_edit_ws(c, m, m->D.cap))) return rc;
+    if ((rc = map_create_ws(c, m))) return rc;
+    const MapCreateWs &W = m->CW;
+    const int acap = W.acap, nn = monocular ? ORBG_CNP_MAX_NEIGH : ORBG_CNP_MAX_NEIGH / 2;
+    hipStream_t st = c->stream;
+    HIPCHK(hipMemsetAsync(d_nmatches, 0, ORBG_CNP_MAX_NEIGH * 4, st));
+    HIPCHK(hipMemsetAsync(d_nnew, 0, ORBG_CNP_MAX_NEIGH * 4, st));
+    PROF_LAUNCH(c, "map_cnp_neighbours",
+                rc = launch_map_cnp_neighbours(st, m->D, m->att, m->geom, W, slot, monocular != 0,
+                                               d_nrecent, d_neigh));
+    if (rc) return set_err(rc, "k_cnp_neigh launch failed");
+    m->touched = true;
+    if (launch_tri_geometry(st, W.cams, W.kf1, W.kf2, ORBG_CNP_MAX_NEIGH, W.geo))
+        return set_err(ORBG_EIO, "k_tri_geometry launch failed");
+    orbg_keyframes K = ak;  // the attached arrays with the rows' has_mp and the clamped counts
+    K.has_mp = W.has_mp;
+    K.counts = W.counts;
+    K.nfv = W.nfv;
+    for (int i = 0; i < nn; i++) {
+        if (launch_map_cnp_pair(st, m->D, m->att, W, slot, i, d_abort))
+            return set_err(ORBG_EIO, "k_cnp_pair launch failed");
+        PROF_LAUNCH(c, "map_cnp_match",
+                    rc = launch_tri_match(st, K, acap, W.kf1 + i, W.kf2 + i, W.geo + i, 1, c->scale,
+                                          c->sigma2, c->p.nlevels, 0, 0, W.match, W.nm));
+        if (rc == -95) return set_err(ORBG_ENOTSUP, "SearchForTriangulation: more than 65535 features");
+        if (rc) return set_err(ORBG_EIO, "k_tri_match launch failed");
+        PROF_LAUNCH(c, "map_cnp_triangulate",
+                    rc = launch_triangulate(st, K, m->geom.kps_raw, m->geom.depth, acap, W.cams,
+                                            W.kf1 + i, W.kf2 + i, W.match, 1, c->scale, c->sigma2,
+                                            c->p.nlevels, c->p.scale_factor, W.x3d, W.tst, W.nnew));
+        if (rc) return set_err(ORBG_EIO, "k_triangulate launch failed");
+        PROF_LAUNCH(c, "map_cnp_insert",
+                    rc = launch_map_cnp_insert(st, m->D, W, slot, i, current_kf_id, first_id, d_recent,
+                                               recent_cap, d_nrecent, d_nmatches, d_nnew,
+                                               d_tri_status));
+        if (rc) return set_err(rc, "k_cnp_insert launch failed");
+    }
+    if (d_tri_status && nn < ORBG_CNP_MAX_NEIGH)
+        HIPCHK(hipMemsetAsync(d_tri_status + (size_t)nn * m->D.cap, 0,
+                              (size_t)(ORBG_CNP_MAX_NEIGH - nn) * m->D.cap, st));
+    if (launch_map_cnp_finish(st, m->D, W, first_id, d_neigh_status, d_out))
+        return set_err(ORBG_EIO, "k_cnp_finish launch failed");
+    m->dirty = true;
+    return map_create_update(c, m);
+}
+
+extern "C" int orbg_map_create_new_points(orbg_ctx *c, orbg_map *m, int slot, int current_kf_id,
+                                          int monocular, int first_id, const int32_t *abort,
+                                          int32_t *recent, int recent_cap, int32_t *nrecent,
+                                          int32_t *neigh, int32_t *neigh_status, int32_t *nmatches,
+                                          int32_t *nnew, int8_t *tri_status, int32_t *out)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (recent_cap < 0 || !nrecent || !neigh || !neigh_status || !nmatches || !nnew || !out ||
+        (recent_cap && !recent))
+        return set_err(ORBG_EINVAL, "bad recent_cap / NULL array");
+    const int n0 = *nrecent;
+    if (n0 < 0 || n0 > recent_cap) return set_err(ORBG_EINVAL, "*nrecent %d outside [0, %d]", n0, recent_cap);
+    const size_t nb = ORBG_CNP_MAX_NEIGH * 4, ts = (size_t)ORBG_CNP_MAX_NEIGH * m->D.cap;
+    Layout L;
+    const size_t o_r = L.take((size_t)recent_cap * 4), o_n = L.take(4), o_a = L.take(4);
+    const size_t o_g = L.take(nb), o_s = L.take(nb), o_m = L.take(nb), o_w = L.take(nb);
+    const size_t o_o = L.take(16), o_t = L.take(ts);
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
+    const int32_t ab = abort ? *abort : 0;
+    if (n0) HIPCHK(hipMemcpyAsync(b + o_r, recent, (size_t)n0 * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(b + o_n, &n0, 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(b + o_a, &ab, 4, hipMemcpyHostToDevice, c->stream));
+    rc = orbg_map_create_new_points_device(
+        c, m, slot, current_kf_id, monocular, first_id, abort ? L.at<int32_t>(b, o_a) : nullptr,
+        L.at<int32_t>(b, o_r), recent_cap, L.at<int32_t>(b, o_n), L.at<int32_t>(b, o_g),
+        L.at<int32_t>(b, o_s), L.at<int32_t>(b, o_m), L.at<int32_t>(b, o_w),
+        tri_status ? L.at<int8_t>(b, o_t) : nullptr, L.at<int32_t>(b, o_o));
+    if (rc) {
+        hipStreamSynchronize(c->stream);  // the copies above read the caller's stack
+        return rc;
+    }
+    int32_t n1 = 0;
+    HIPCHK(hipMemcpyAsync(&n1, b + o_n, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(neigh, b + o_g, nb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(neigh_status, b + o_s, nb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(nmatches, b + o_m, nb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(nnew, b + o_w, nb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(out, b + o_o, 16, hipMemcpyDeviceToHost, c->stream));
+    if (tri_status) HIPCHK(hipMemcpyAsync(tri_status, b + o_t, ts, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (n1 > n0) HIPCHK(hipMemcpy(recent + n0, b + o_r + (size_t)n0 * 4, (size_t)(n1 - n0) * 4, hipMemcpyDeviceToHost));
+    c->prof.collect();
+    *nrecent = n1;
+    if (out[3] & ORBG_CNP_DEAD) return set_err(ORBG_EINVAL, "slot %d is not live", slot);
+    if (out[3] & ORBG_CNP_NO_POSE) return set_err(ORBG_EINVAL, "slot %d has no stored pose", slot);
+    if (out[3] & (ORBG_CNP_POINT_RANGE | ORBG_CNP_RECENT_RANGE))
+        return set_err(ORBG_ERANGE, "%d new points, %d created (max_points %d, recent_cap %d)", out[2],
+                       out[1], m->D.P, recent_cap);
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_process_new_keyframe_device(orbg_ctx *c, orbg_map *m, int slot,
+                                                    const int32_t *d_point_ids,
+                                                    const uint8_t *d_octaves,
+                                                    const uint8_t *d_feat_flags, int n,
+                                                    const float *d_Tcw, int mnid, int kf_flags,
+                                                    const uint8_t *d_in_keyframe, int32_t *d_recent,
+                                                    int recent_cap, int32_t *d_nrecent,
+                                                    int32_t *d_out)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if ((rc = map_slot_ok(m, slot))) return rc;
+    if ((rc = map_attached(m))) return rc;
+    if (n < 0 || n > m->D.cap) return set_err(ORBG_EINVAL, "%d features (kf_cap %d)", n, m->D.cap);
+    if (recent_cap < 0) return set_err(ORBG_EINVAL, "negative recent_cap");
+    if (!d_Tcw || !d_nrecent || !d_out || (recent_cap && !d_recent) || (n && (!d_point_ids || !d_octaves)))
+        return set_err(ORBG_EINVAL, "NULL device array");
+    if ((rc = map_edit_ws(c, m, m->D.cap))) return rc;
+    if ((rc = map_create_ws(c, m))) return rc;
+    const MapCreateWs &W = m->CW;
+    const MapDev &D = m->D;
+    hipStream_t st = c->stream;
+    if (launch_map_pnk_prepare(st, D, W, slot, d_point_ids, n, d_Tcw, mnid, kf_flags, d_in_keyframe,
+                               d_recent, recent_cap, d_nrecent, d_out))
+        return set_err(ORBG_EIO, "k_pnk_prepare launch failed");
+    m->touched = true;
+    const int32_t *h = W.hdr;
+    if (launch_map_set_keyframes(st, D, h + CNP_HDR_SLOT, 1, W.row, n ? d_octaves : (const uint8_t *)W.row,
+                                 D.cap, h + CNP_HDR_N, W.centre, h + CNP_HDR_FLAGS))
+        return set_err(ORBG_EIO, "k_map_set_kf launch failed");
+    if (d_feat_flags && launch_map_set_features(st, D, h + CNP_HDR_SLOT, 1, d_feat_flags, D.cap, h + CNP_HDR_N))
+        return set_err(ORBG_EIO, "k_map_set_features launch failed");
+    if (launch_map_set_poses(st, D, h + CNP_HDR_SLOT, 1, d_Tcw, h + CNP_HDR_MNID))
+        return set_err(ORBG_EIO, "k_loop_set_poses launch failed");
+    m->dirty = m->tree_dirty = true;
+    if ((rc = map_create_update(c, m))) return rc;
+    return orbg_map_update_connections_batch_device(c, m, h + CNP_HDR_SLOT, 1);
+}
+
+extern "C" int orbg_map_process_new_keyframe(orbg_ctx *c, orbg_map *m, int slot,
+                                             const int32_t *point_ids, const uint8_t *octaves,
+                                             const uint8_t *feat_flags, int n, const float *Tcw,
+                                             int mnid, int kf_flags, const uint8_t *in_keyframe,
+                                             int32_t *recent, int recent_cap, int32_t *nrecent,
+                                             int32_t *out)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (n < 0 || n > m->D.cap) return set_err(ORBG_EINVAL, "%d features (kf_cap %d)", n, m->D.cap);
+    if (recent_cap < 0 || !Tcw || !nrecent || !out || (recent_cap && !recent) ||
+        (n && (!point_ids || !octaves)))
+        return set_err(ORBG_EINVAL, "bad recent_cap / NULL array");
+    const int n0 = *nrecent;
+    if (n0 < 0 || n0 > recent_cap) return set_err(ORBG_EINVAL, "*nrecent %d outside [0, %d]", n0, recent_cap);
+    const size_t cn = (size_t)std::max(n, 1);
+    Layout L;
+    const size_t o_p = L.take(cn * 4), o_o = L.take(cn), o_f = L.take(cn), o_k = L.take(cn);
+    const size_t o_T = L.take(48), o_r = L.take((size_t)recent_cap * 4), o_n = L.take(4), o_out = L.take(16);
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
+    hipStream_t st = c->stream;
+    if (n) {
+        HIPCHK(hipMemcpyAsync(b + o_p, point_ids, (size_t)n * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(b + o_o, octaves, (size_t)n, hipMemcpyHostToDevice, st));
+        if (feat_flags) HIPCHK(hipMemcpyAsync(b + o_f, feat_flags, (size_t)n, hipMemcpyHostToDevice, st));
+        if (in_keyframe) HIPCHK(hipMemcpyAsync(b + o_k, in_keyframe, (size_t)n, hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(hipMemcpyAsync(b + o_T, Tcw, 48, hipMemcpyHostToDevice, st));
+    if (n0) HIPCHK(hipMemcpyAsync(b + o_r, recent, (size_t)n0 * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b + o_n, &n0, 4, hipMemcpyHostToDevice, st));
+    rc = orbg_map_process_new_keyframe_device(
+        c, m, slot, L.at<int32_t>(b, o_p), b + o_o, (n && feat_flags) ? b + o_f : nullptr, n,
+        L.at<float>(b, o_T), mnid, kf_flags, (n && in_keyframe) ? b + o_k : nullptr,
+        L.at<int32_t>(b, o_r), recent_cap, L.at<int32_t>(b, o_n), L.at<int32_t>(b, o_out));
+    if (rc) {
+        hipStreamSynchronize(st);
+        return rc;
+    }
+    int32_t n1 = 0;
+    HIPCHK(hipMemcpyAsync(&n1, b + o_n, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(out, b + o_out, 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (n1 > n0) HIPCHK(hipMemcpy(recent + n0, b + o_r + (size_t)n0 * 4, (size_t)(n1 - n0) * 4, hipMemcpyDeviceToHost));
+    c->prof.collect();
+    *nrecent = n1;
+    if (out[3] & ORBG_CNP_RECENT_RANGE)
+        return set_err(ORBG_ERANGE, "%d ids for the recent list, %d appended (recent_cap %d)", out[2],
+                       out[0], recent_cap);
     return ORBG_OK;
 }
 

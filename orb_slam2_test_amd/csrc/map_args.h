@@ -1,7 +1,7 @@
 // map_args.h -- device layout and launch arguments of the covisibility Map (map_kernels.hip:
 // KeyFrame::UpdateConnections, Tracking::UpdateLocalKeyFrames / UpdateLocalPoints,
 // MapPoint::UpdateNormalAndDepth; map_cull_kernels.hip; map_edit_kernels.hip;
-// map_loop_kernels.hip, map_lba_kernels.hip), shared with the
+// map_loop_kernels.hip, map_lba_kernels.hip, map_create_kernels.hip), shared with the
 // host entry points (api_map.hip).
 #pragma once
 
@@ -289,5 +289,62 @@ int launch_map_lba_window(hipStream_t st, const MapDev &M, const MapAttach &A, c
 int launch_map_lba_apply(hipStream_t st, const MapDev &M, const MapLbaWs &W, const MapLbaWindow &O,
                          const uint8_t *erase, orbg_frustum_camera *cams_out, int32_t *out,
                          Prof *prof);
+
+// map_create_kernels.hip: LocalMapping::CreateNewMapPoints and ProcessNewKeyFrame on the table.
+// The attached geometry (orbg_map_attach_keyframe_geometry, not owned) and the map-owned
+// workspace of one call; acap = the attached row length, cap = the Map's.
+#define ORBG_CNP_MAX_NEIGH 20         // GetBestCovisibilityKeyFrames(20), monocular
+struct MapGeom {
+    const orbg_keypoint *kps_raw;     // [K][acap] mvKeys, NULL: mvKeysUn
+    const float *depth;               // [K][acap] mvDepth
+    const orbg_kf_camera *cams;       // [K] fx .. mbf read
+};
+struct MapCreateWs {
+    int32_t acap;
+    int32_t *hdr;                     // [16] CNP_HDR_*
+    int32_t *kf1, *kf2;               // [20] the pair launches' keyframes (skipped: the slot twice)
+    int32_t *nstat;                   // [20] the neighbours' statuses
+    int32_t *counts, *nfv;            // [K] N / mFeatVec size of the running pair's keyframes
+    orbg_kf_camera *cams;             // [K] stored Tcw + attached intrinsics, current and neighbours
+    uint8_t *has_mp;                  // [K][acap] row[idx] >= 0 of the running pair's keyframes
+    orbg_triangulation_pair *geo;     // [20]
+    int32_t *match;                   // [acap] the running pair's vMatches12
+    int32_t *nm;                      // [1]
+    float *x3d;                       // [acap][3]
+    int8_t *tst;                      // [acap] ORBG_TRI_*
+    int32_t *nnew;                    // [1]
+    uint8_t *virt;                    // [acap] the current keyframe's features whose point a cap left out
+    int32_t *ids;                     // [cap + 1] the points to update, -1 padded, their count behind
+    int32_t *row;                     // [cap] ProcessNewKeyFrame: the row as it is stored
+    float *centre;                    // [3] its camera centre
+};
+#define CNP_HDR_NN 0                  // neighbours taken from the list
+#define CNP_HDR_NNEW 1                // points created so far
+#define CNP_HDR_NEED 2                // points a large enough cap would have created
+#define CNP_HDR_BITS 3                // ORBG_CNP_*
+#define CNP_HDR_ABORT 4               // the latched d_abort
+#define CNP_HDR_REC0 5                // d_nrecent[0] when the call started
+#define CNP_HDR_SLOT 8                // ProcessNewKeyFrame: slot, N, kf flags, mnId
+#define CNP_HDR_N 9
+#define CNP_HDR_FLAGS 10
+#define CNP_HDR_MNID 11
+// the neighbours, their statuses (baseline / median depth, one workgroup each) and cameras
+int launch_map_cnp_neighbours(hipStream_t st, const MapDev &M, const MapAttach &A, const MapGeom &G,
+                              const MapCreateWs &W, int slot, int monocular, const int32_t *nrecent,
+                              int32_t *neigh);
+// before pair i's search: the abort latch, N / nfv and has_mp of both keyframes from the rows
+int launch_map_cnp_pair(hipStream_t st, const MapDev &M, const MapAttach &A, const MapCreateWs &W,
+                        int slot, int i, const int32_t *abort);
+// after pair i's triangulation: ids by an in-order scan, records, both rows, recent
+int launch_map_cnp_insert(hipStream_t st, const MapDev &M, const MapCreateWs &W, int slot, int i,
+                          int current_kf_id, int first_id, int32_t *recent, int recent_cap,
+                          int32_t *nrecent, int32_t *nmatches, int32_t *nnew, int8_t *tri_status);
+int launch_map_cnp_finish(hipStream_t st, const MapDev &M, const MapCreateWs &W, int first_id,
+                          int32_t *neigh_status, int32_t *out);
+// ProcessNewKeyFrame: the row with bad / out-of-range ids as -1, the centre, recent and W.ids
+int launch_map_pnk_prepare(hipStream_t st, const MapDev &M, const MapCreateWs &W, int slot,
+                           const int32_t *point_ids, int n, const float *Tcw, int mnid, int flags,
+                           const uint8_t *in_keyframe, int32_t *recent, int recent_cap,
+                           int32_t *nrecent, int32_t *out);
 
 }  // namespace orbg

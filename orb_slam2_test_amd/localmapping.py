@@ -12,8 +12,9 @@ src/KeyFrame.cc:798-814 (UnprojectStereo).
     nnew, x3D, status = lm.Triangulate(pKF1, pKF2, cam1, cam2, vMatches12)
 
 The reference's per-neighbour loop (GetBestCovisibilityKeyFrames, the baseline test, the
-MapPoint creation for every status == TRI_NEW in feature order) is host control flow and stays
-the caller's; batches of pairs go through orbg_triangulation_geometry_batch_device /
+MapPoint creation for every status == TRI_NEW in feature order) is the caller's with these
+per-pair calls, and one device call on a Map (Map.CreateNewMapPoints, RunOnMap below); batches
+of pairs go through orbg_triangulation_geometry_batch_device /
 orbg_triangulate_batch_device (include/orbg.h).  ``pKF`` here is any object with mvKeysUn and,
 for stereo, mvuRight / mvDepth (mvKeys: the distorted keypoints UnprojectStereo reads; None:
 mvKeysUn).  There is no CPU path: without liborbg the calls raise.
@@ -56,7 +57,8 @@ class LocalMapping:
         """The triangulation loop of CreateNewMapPoints over one neighbour's vMatchedPairs
         (given as vMatches12, SearchForTriangulation's per-feature form) -> (nnew, x3D[N1, 3],
         status[N1]): status[i] == TRI_NEW where the reference creates a MapPoint at x3D[i];
-        the other TRI_* codes name the test that rejected the pair."""
+        the other TRI_* codes name the test that rejected the pair.  (The whole loop on a device
+        Map is Map.CreateNewMapPoints.)"""
         keep = []
 
         def side(fr):
@@ -85,11 +87,14 @@ class LocalMapping:
         return n.value, x[:a.n].copy(), st[:a.n].copy()
 
     def RunOnMap(self, m, slot, current_kf_id, monocular, recent, create_new_map_points=None,
-                 local_bundle_adjustment=None, th=3.0, stop_flag=None, d_cams_out=None):
+                 local_bundle_adjustment=None, th=3.0, stop_flag=None, d_cams_out=None,
+                 first_id=None, abort=None):
         """One keyframe's pass of LocalMapping::Run (src/LocalMapping.cc:55-120) over a device
         Map `m` whose row `slot` ProcessNewKeyFrame has uploaded: MapPointCulling of `recent`,
         create_new_map_points(recent) -> recent (the caller's: the triangulation above, then
-        Map.SetPoints and Map.AddObservations for the new ids), SearchInNeighbors,
+        Map.SetPoints and Map.AddObservations for the new ids; True runs
+        m.CreateNewMapPoints(slot, current_kf_id, monocular, first_id, recent, abort) on the table
+        and leaves its report in self.create_report), SearchInNeighbors,
         local bundle adjustment, KeyFrameCulling.  local_bundle_adjustment: True runs
         m.LocalBundleAdjustment(slot, stop_flag, d_cams_out) (Optimizer::LocalBundleAdjustment on
         the table: d_cams_out keeps the attached cameras' Tcw current for the next keyframe's
@@ -97,7 +102,12 @@ class LocalMapping:
         step edits the one table in HBM.  Returns (mlpRecentAddedMapPoints, vpTargetKFs, the nFused of each
         target's Fuse, the second pass's, the CULL_RECORD_DTYPE records)."""
         recent, _ = m.MapPointCulling(recent, current_kf_id, monocular)
-        if create_new_map_points is not None:
+        if create_new_map_points is True:
+            if first_id is None:
+                raise ValueError("create_new_map_points=True needs first_id")
+            recent, self.create_report = m.CreateNewMapPoints(slot, current_kf_id, monocular,
+                                                              first_id, recent, abort)
+        elif create_new_map_points is not None:
             recent = create_new_map_points(recent)
         targets, nfused, second = m.SearchInNeighbors(slot, current_kf_id, monocular, th)
         if local_bundle_adjustment is True:

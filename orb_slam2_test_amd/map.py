@@ -31,6 +31,8 @@ ascending slot (include/orbg.h).
     m.ApplyCorrection(cur, vs, Scw_v, Siw, Tiw); m.AddLoopEdge(loop, cur)
     report, counts = m.CorrectLoop(cur, loop, Scw, matched, loop_points, bFixScale)  # all of it
     report = m.LocalBundleAdjustment(slot, stop_flag)         # Optimizer.cc:633-979 on the table
+    recent, _ = m.ProcessNewKeyFrame(slot, ids, octs, feats, Tcw, mnId, in_keyframe, recent)
+    recent, report = m.CreateNewMapPoints(slot, mnId, monocular, first_id, recent)
     w = m.LbaWindow(slot); m.LbaApply(w, poses, points, erase)  # its two ends, one at a time
 """
 import ctypes as C
@@ -410,16 +412,20 @@ class Map:
         return out[:n.value]
 
     # ---- MapPoint::Replace, ORBmatcher::Fuse, LocalMapping::SearchInNeighbors ----
-    def AttachKeyFrames(self, d_desc, d_kps, d_uright, d_counts, cap, d_cams):
+    def AttachKeyFrames(self, d_desc, d_kps, d_uright, d_counts, cap, d_cams, d_fv_nodes=None,
+                        d_fv_off=None, d_fv_feats=None, d_nfv=None):
         """The keyframes' data the search and ComputeDistinctiveDescriptors read, as device
         pointers (ints) indexed by slot: mDescriptors [K][cap][32], mvKeysUn [K][cap]
         (KEYPOINT records), mvuRight [K][cap] (None: monocular), N [K], FRUSTUM_DTYPE cameras
-        [K].  Not owned: the arrays must outlive the attachment.  d_desc None detaches."""
+        [K]; d_fv_*: mFeatVec in orbg_bow_transform_batch_device's layout, read by
+        CreateNewMapPoints only.  Not owned: the arrays must outlive the attachment.  d_desc
+        None detaches."""
         if d_desc is None:
             L.check(L.lib().orbg_map_attach_keyframes(self._c(), self._h, None, 0, None),
                     "orbg_map_attach_keyframes")
             return
-        k = L.KeyFrames(d_desc, d_kps, d_uright, None, d_counts, None, None, None, None)
+        k = L.KeyFrames(d_desc, d_kps, d_uright, None, d_counts, d_fv_nodes, d_fv_off, d_fv_feats,
+                        d_nfv)
         L.check(L.lib().orbg_map_attach_keyframes(self._c(), self._h, C.byref(k), int(cap), d_cams),
                 "orbg_map_attach_keyframes")
 
@@ -797,3 +803,89 @@ class Map:
                    do_more=int(rep.lba.do_more), n_outliers=int(rep.lba.n_outliers),
                    n_erase=int(rep.lba.n_erase))
         return out
+
+    # ---- LocalMapping::ProcessNewKeyFrame / CreateNewMapPoints on the table ----
+    def AttachKeyFrameGeometry(self, d_kps_raw, d_depth, d_kf_cams):
+        """What the triangulation reads beside AttachKeyFrames' arrays, device pointers indexed
+        by slot with the attached cap: mvKeys (None: mvKeysUn), mvDepth (needed with mvuRight),
+        KF_CAMERA_DTYPE records of which the intrinsics fx .. mbf are read (the pose is the
+        Map's own, SetPoses).  d_kf_cams None detaches."""
+        L.check(L.lib().orbg_map_attach_keyframe_geometry(self._c(), self._h, d_kps_raw, d_depth,
+                                                          d_kf_cams),
+                "orbg_map_attach_keyframe_geometry")
+
+    def create_new_points_device(self, slot, current_kf_id, monocular, first_id, d_abort, d_recent,
+                                 recent_cap, d_nrecent, d_neigh, d_neigh_status, d_nmatches,
+                                 d_nnew, d_tri_status, d_out, ctx=None):
+        L.check(L.lib().orbg_map_create_new_points_device(
+            self._c(ctx), self._h, int(slot), int(current_kf_id), int(bool(monocular)),
+            int(first_id), d_abort, d_recent, int(recent_cap), d_nrecent, d_neigh, d_neigh_status,
+            d_nmatches, d_nnew, d_tri_status, d_out), "orbg_map_create_new_points_device")
+
+    def CreateNewMapPoints(self, slot, current_kf_id, monocular, first_id, recent, abort=None,
+                           recent_cap=None, tri_status=False):
+        """LocalMapping::CreateNewMapPoints on the table: the new points get the ids first_id,
+        first_id + 1, .. in creation order and are appended to `recent`.  abort: None or an
+        int (CheckNewKeyFrames() from the second neighbour on).  Returns (recent, report);
+        report: neigh, status (0 processed, 1 baseline, 2 aborted, 3 unusable), nmatches, nnew
+        per neighbour, created, needed, bits (CNP_*), rc (ORBG_OK or ORBG_ERANGE when a cap cut
+        the creation short) and, if asked for, tri_status [neighbours][kf_cap]."""
+        r = _i32(recent)
+        cap = len(r) + self.kf_cap if recent_cap is None else int(recent_cap)
+        buf = np.full(max(cap, 1), -1, np.int32)
+        buf[:len(r)] = r
+        n = C.c_int32(len(r))
+        ab = None if abort is None else np.array([int(abort)], np.int32)
+        ng, st, nm, nw = (np.zeros(20, np.int32) for _ in range(4))
+        ts = np.zeros((20, self.kf_cap), np.int8) if tri_status else None
+        out = np.zeros(4, np.int32)
+        rc = L.lib().orbg_map_create_new_points(
+            self._c(), self._h, int(slot), int(current_kf_id), int(bool(monocular)), int(first_id),
+            L.ptr(ab), L.ptr(buf), cap, C.byref(n), L.ptr(ng), L.ptr(st), L.ptr(nm), L.ptr(nw),
+            L.ptr(ts), L.ptr(out))
+        if rc != L.ORBG_ERANGE:
+            L.check(rc, "orbg_map_create_new_points")
+        k = int(out[0])
+        rep = dict(neigh=ng[:k].tolist(), status=st[:k].tolist(), nmatches=nm[:k].tolist(),
+                   nnew=nw[:k].tolist(), created=int(out[1]), needed=int(out[2]), bits=int(out[3]),
+                   rc=rc)
+        if tri_status:
+            rep["tri_status"] = ts[:k]
+        return buf[:n.value].copy(), rep
+
+    def process_new_keyframe_device(self, slot, d_point_ids, d_octaves, d_feat_flags, n, d_Tcw,
+                                    mnid, kf_flags, d_in_keyframe, d_recent, recent_cap, d_nrecent,
+                                    d_out, ctx=None):
+        L.check(L.lib().orbg_map_process_new_keyframe_device(
+            self._c(ctx), self._h, int(slot), d_point_ids, d_octaves, d_feat_flags, int(n), d_Tcw,
+            int(mnid), int(kf_flags), d_in_keyframe, d_recent, int(recent_cap), d_nrecent, d_out),
+            "orbg_map_process_new_keyframe_device")
+
+    def ProcessNewKeyFrame(self, slot, point_ids, octaves, feat_flags, Tcw, mnid, in_keyframe=None,
+                           recent=(), root=False, recent_cap=None):
+        """The table side of LocalMapping::ProcessNewKeyFrame: the row, features, pose and mnId
+        of `slot` are stored (a bad or out-of-range id as -1), the ids flagged in_keyframe
+        (pMP->IsInKeyFrame(pKF) as Tracking left it) are appended to `recent`, the other good
+        points get UpdateNormalAndDepth and ComputeDistinctiveDescriptors, then
+        UpdateConnections(slot).  Returns (recent, report)."""
+        p = _i32(point_ids)
+        o = np.ascontiguousarray(octaves, np.uint8).reshape(-1)
+        f = None if feat_flags is None else np.ascontiguousarray(feat_flags, np.uint8).reshape(-1)
+        k = None if in_keyframe is None else np.ascontiguousarray(np.asarray(in_keyframe) != 0,
+                                                                   np.uint8).reshape(-1)
+        if len(o) != len(p) or any(x is not None and len(x) != len(p) for x in (f, k)):
+            raise ValueError("the row's arrays differ in length")
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(12)
+        r = _i32(recent)
+        cap = len(r) + len(p) if recent_cap is None else int(recent_cap)
+        buf = np.full(max(cap, 1), -1, np.int32)
+        buf[:len(r)] = r
+        n = C.c_int32(len(r))
+        out = np.zeros(4, np.int32)
+        rc = L.lib().orbg_map_process_new_keyframe(
+            self._c(), self._h, int(slot), L.ptr(p), L.ptr(o), L.ptr(f), len(p), L.ptr(T), int(mnid),
+            KF_ROOT if root else 0, L.ptr(k), L.ptr(buf), cap, C.byref(n), L.ptr(out))
+        if rc != L.ORBG_ERANGE:
+            L.check(rc, "orbg_map_process_new_keyframe")
+        return buf[:n.value].copy(), dict(appended=int(out[0]), updated=int(out[1]),
+                                          needed=int(out[2]), bits=int(out[3]), rc=rc)

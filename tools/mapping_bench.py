@@ -24,6 +24,15 @@ oracle (oracle/mapping_oracle.c) on one host core over a bounded sample:
              Per-thread ALU (a 4x4 Jacobi in double, glibc atan2f / cosf), so latency- and
              ALU-bound: the HBM fraction is low by construction.
 
+  create_points  LocalMapping::CreateNewMapPoints on the device Map (csrc/map_create_kernels.hip):
+             one orbg_map_create_new_points_device call for a 2000-feature keyframe with 20
+             (monocular) / 10 (stereo) neighbours of 2000 features, host clock around the call
+             and a synchronise, against the same step done with the per-pair host forms
+             (orbg_triangulation_geometry, orbg_search_for_triangulation, orbg_triangulate,
+             then SetPoints / SetPointStats / AddObservations per neighbour and the descriptors
+             and normals at the end), alternating, on the same map state: ms per call, median
+             and least of --steps repeats, and the launches the device form issues.
+
     python tools/mapping_bench.py [--steps 20] [--warmup 3] [--no-cpu] [--only NAME]
 """
 import argparse
@@ -76,6 +85,111 @@ def dev(a):
     return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
 
 
+def create_points_bench(ctx, args):
+    import types
+    import torch
+    from orb_slam2_test_amd import _lib as L
+    from orb_slam2_test_amd.localmapping import LocalMapping
+    from orb_slam2_test_amd.orbmatcher import ORBmatcher
+    import ref_create_points as RP
+    import test_gpu_create_points as TG
+    lm, matcher = LocalMapping(), ORBmatcher(0.6, False)
+    for mono in (True, False):
+        nn = 20 if mono else 10
+        d = RP.create_dataset(77, not mono, ncur=2000, nkf=nn + 1, cap=2048, nanchor=60,
+                              nfresh=4200, spacing=0.12, nfeat=2000, anchor_all=True)
+        G = TG.GpuCreateMap(d["nkf"], d["cap"], d["npts"])
+        RP.build_create_map(G, d)
+        cur, first = d["cur"], d["first_id"]
+        neigh = G.m.connections(cur)[0][:nn]
+
+        def restore():
+            for s in [cur] + neigh:
+                G.set_keyframe(s, d["rows"][s], d["octs"][s], d["centre"][s], root=(s == 0))
+                G.set_keyframe_features(s, d["featfl"][s])
+
+        t_rec = torch.zeros(4096, dtype=torch.int32, device="cuda")
+        t_n = torch.zeros(1, dtype=torch.int32, device="cuda")
+        t_o = [torch.zeros(20, dtype=torch.int32, device="cuda") for _ in range(5)]
+
+        def device_form():
+            t_n.zero_()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            G.m.create_new_points_device(cur, 10 + cur, mono, first, None, t_rec.data_ptr(), 4096,
+                                         t_n.data_ptr(), *[t.data_ptr() for t in t_o[:4]], None,
+                                         t_o[4].data_ptr())
+            ctx.sync()
+            return time.perf_counter() - t0, t_o[4].tolist()[1]
+
+        def frame(s, has):
+            return types.SimpleNamespace(mvKeysUn=d["kps"][s], mvKeys=None, mDescriptors=d["kdesc"][s],
+                                         mvuRight=d["uright"][s], mvDepth=d["depth"][s], has_mp=has,
+                                         mFeatVec=d["fv"][s])
+
+        cams = [np.array(d["intr"][s], L.KF_CAMERA_DTYPE) for s in range(d["nkf"])]
+        for s in range(d["nkf"]):
+            cams[s]["Tcw"] = np.asarray(d["poses"][s], np.float32).reshape(12)
+
+        def per_pair_forms():
+            """the caller's loop: the pair calls and the uploads, neighbour by neighbour"""
+            ctx.sync()
+            t0 = time.perf_counter()
+            has = {s: np.array([p >= 0 for p in d["rows"][s]], np.uint8) for s in [cur] + neigh}
+            nxt, made = first, []
+            for nb in G.m.connections(cur)[0][:nn]:
+                g = lm.ComputeF12(cams[cur], cams[nb])
+                _, m12 = matcher.SearchForTriangulation(frame(cur, has[cur]), frame(nb, has[nb]), g)
+                _, x3d, st = lm.Triangulate(frame(cur, None), frame(nb, None), cams[cur], cams[nb], m12)
+                i1 = np.nonzero(st == L.TRI_NEW)[0]
+                if not len(i1):
+                    continue
+                ids = np.arange(nxt, nxt + len(i1), dtype=np.int32)
+                rec = np.zeros(len(i1), L.MAPPOINT_DTYPE)
+                rec["x"], rec["y"], rec["z"], rec["flags"] = x3d[i1, 0], x3d[i1, 1], x3d[i1, 2], L.MP_VALID
+                G.m.SetPoints(nxt, rec, np.zeros((len(i1), 32), np.uint8), [cur] * len(i1))
+                G.m.SetPointStats(nxt, [10 + cur] * len(i1), [1] * len(i1), [1] * len(i1))
+                G.m.AddObservations([cur] * len(i1) + [nb] * len(i1), list(i1) + list(m12[i1]),
+                                    list(ids) + list(ids))
+                has[cur][i1] = 1
+                nxt += len(i1)
+                made += ids.tolist()
+            if made:
+                G.m.ComputeDistinctiveDescriptors(made)
+                G.m.UpdateNormalAndDepth(made)
+            ctx.sync()
+            return time.perf_counter() - t0, len(made)
+
+        ta, tb, na, nb_ = [], [], None, None
+        for it in range(args.warmup + args.steps):
+            restore()
+            a, na = device_form()
+            restore()
+            b, nb_ = per_pair_forms()
+            if it >= args.warmup:
+                ta.append(a)
+                tb.append(b)
+        restore()
+        ctx.profile(True)
+        ctx.profile_reset()
+        device_form()
+        kern = ctx.profile_read()
+        ctx.profile(False)
+        print(json.dumps({
+            "metric": "create_points_%s_ms" % ("mono" if mono else "stereo"),
+            "value": round(float(np.median(ta)) * 1e3, 3), "unit": "ms per call",
+            "higher_is_better": False, "data": "synthetic",
+            "config": {"workload": "2000-feature keyframe, %d neighbours of 2000 features" % nn,
+                       "steps": args.steps, "warmup": args.warmup},
+            "device_form_ms": {"median": round(float(np.median(ta)) * 1e3, 3),
+                               "min": round(min(ta) * 1e3, 3), "max": round(max(ta) * 1e3, 3)},
+            "per_pair_host_forms_ms": {"median": round(float(np.median(tb)) * 1e3, 3),
+                                       "min": round(min(tb) * 1e3, 3), "max": round(max(tb) * 1e3, 3)},
+            "points_created": {"device_form": na, "per_pair_host_forms": nb_},
+            "launches_of_its_own": 4 * nn + 3,
+            "profiled_kernels_ms": {k: round(v[0], 4) for k, v in sorted(kern.items())}}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -92,6 +206,9 @@ def main():
         from oracle import pyoracle as O
     ctx = _ctx()
     h = ctx.handle
+
+    if args.only in ("", "create_points"):
+        create_points_bench(ctx, args)
 
     if args.only in ("", "tri_match"):
         NQ, REP, cap = 64, 16, 2048
