@@ -2435,6 +2435,137 @@ int orbg_gba_correct_points_device(orbg_ctx *ctx, const float *d_Tcw_before,
                                    const float *d_Twc_after, int nkf, const int32_t *d_ref,
                                    const float *d_points, int n, float *d_out);
 
+/* ---- Optimizer::GlobalBundleAdjustemnt(pMap, ...) and RunGlobalBundleAdjustment on the Map ----
+ * src/Optimizer.cc:105-320 and src/LoopClosing.cc:1024-1128 in three stages and two chaining
+ * calls.  The keyframe data must be attached (orbg_map_attach_keyframes: mvKeysUn, mvuRight, the
+ * cameras) and every keyframe that is not bad needs a pose.  The `_device` forms run on the
+ * context stream without synchronising and allocate nothing after the first call on a map; the
+ * host forms take host arrays and synchronise.  Pointer order is slot order / id order.
+ *
+ * State the Map holds for it.  Per slot mTcwGBA and mTcwBefGBA (float [12], 3x4 row-major) and
+ * KeyFrame::mnBAGlobalForKF (int32); per point mPosGBA (float [3]) and MapPoint::mnBAGlobalForKF.
+ * Both mnBAGlobalForKF are 0 after orbg_map_create / orbg_map_clear; a slot that becomes live
+ * (orbg_map_set_keyframe[s] on a slot that was not live, orbg_map_process_new_keyframe) and a
+ * point created by orbg_map_create_new_points[_device] start with 0.  A map that never uses them
+ * behaves as before.  set / get copy the ranges [first_slot, first_slot + nslots) and
+ * [first_point, first_point + npoints); any array may be NULL (that part is left alone). */
+int orbg_map_set_gba_state(orbg_ctx *ctx, orbg_map *map, int first_slot, int nslots,
+                           const float *TcwGBA, const float *TcwBefGBA, const int32_t *kf_ba_global,
+                           int first_point, int npoints, const float *PosGBA,
+                           const int32_t *mp_ba_global);
+int orbg_map_get_gba_state(orbg_ctx *ctx, orbg_map *map, int first_slot, int nslots, float *TcwGBA,
+                           float *TcwBefGBA, int32_t *kf_ba_global, int first_point, int npoints,
+                           float *PosGBA, int32_t *mp_ba_global);
+/* The flags of slots first .. first + n - 1 (host): ORBG_MAP_KF_ROOT | ORBG_MAP_KF_BAD, and 4 for a
+ * live slot.  The live ORBG_MAP_KF_ROOT slots are what a caller without its own list passes as
+ * mvpKeyFrameOrigins. */
+int orbg_map_get_keyframe_flags(orbg_ctx *ctx, orbg_map *map, int first, int n, int32_t *flags);
+/* The window (Optimizer.cc:113-246), exactly what the compat layer's
+ * orbg_compat::ref::BundleAdjustment builds from GetAllKeyFrames() / GetAllMapPoints() of the same
+ * map:
+ *   kf_slots [npose]   the slots that are live and not ORBG_MAP_KF_BAD, ascending.
+ *   poses [npose]      Converter::toSE3Quat(kf_Tcw) as orbg_map_lba_window computes it; fixed = 1
+ *                      iff the stored mnId is 0 (the slot does not decide it).
+ *   point_ids [npoint] the ORBG_MP_VALID points with at least one edge, ascending id.  A good point
+ *                      whose observers are all bad or absent is left out (vbNotIncludedMP, :236-244).
+ *   points [npoint][3] the stored float positions as doubles.
+ *   edges [nedge], edge_feat [nedge]
+ *                      per window point, per observer that is live and not bad (ascending slot),
+ *                      every field as orbg_map_lba_window fills it, except robust = the argument
+ *                      and huber_delta = (float)sqrt(5.99) / (float)sqrt(7.815) (:157-158: 5.99, not
+ *                      5.991).  pose and point index the two lists.  The reference's other test,
+ *                      mnId > maxKFid (:184), can never hold for a keyframe that is not bad.
+ *   counts [4]         npose, npoint, nedge, the good points left out: always the full counts.
+ *   status [4]         [0] = ORBG_LBA_NO_POSE | ORBG_LBA_RANGE | ORBG_LBA_FEATURE bits.
+ * Nothing in the Map changes.  The host form returns ORBG_ERANGE when a cap is exceeded (counts
+ * hold what is needed) and ORBG_EINVAL for nothing attached, a vertex keyframe without a pose or
+ * an observation whose feature index is past the attached count. */
+int orbg_map_gba_window_device(orbg_ctx *ctx, orbg_map *map, int robust, int32_t *d_kf_slots,
+                               orbg_pose *d_poses, int pose_cap, int32_t *d_point_ids,
+                               double *d_points, int point_cap, orbg_edge *d_edges,
+                               int32_t *d_edge_feat, int edge_cap, int32_t *d_counts,
+                               int32_t *d_status);
+int orbg_map_gba_window(orbg_ctx *ctx, orbg_map *map, int robust, int32_t *kf_slots,
+                        orbg_pose *poses, int pose_cap, int32_t *point_ids, double *points,
+                        int point_cap, orbg_edge *edges, int32_t *edge_feat, int edge_cap,
+                        int32_t *counts);
+/* The store (:273-318) of a window's kf_slots / point_ids (d_counts as the window left them) and
+ * the optimised d_poses / d_points.  A keyframe that has gone bad or dead and a point that has
+ * gone bad since the window was built are skipped (:279, :303).
+ *   loop_kf == 0   SetPose(Converter::toCvMat(pose)) of every window keyframe, the fixed one
+ *                  included, the centres as orbg_map_set_keyframe_poses writes them, the Tcw of
+ *                  their entries in d_cams_out (may be NULL); then SetWorldPos((float) estimate)
+ *                  of every window point and UpdateNormalAndDepth over the current observation
+ *                  index.
+ *   loop_kf != 0   mTcwGBA = that pose, mPosGBA = that position, both mnBAGlobalForKF = loop_kf.
+ *                  Poses, centres, positions, normals and rows do not change.
+ * d_out [2]: keyframes written, points written. */
+int orbg_map_gba_store_device(orbg_ctx *ctx, orbg_map *map, const int32_t *d_kf_slots, int pose_cap,
+                              const int32_t *d_point_ids, int point_cap, const int32_t *d_counts,
+                              const orbg_pose *d_poses, const double *d_points, int loop_kf,
+                              orbg_frustum_camera *d_cams_out, int32_t *d_out);
+int orbg_map_gba_store(orbg_ctx *ctx, orbg_map *map, const int32_t *kf_slots, int npose,
+                       const int32_t *point_ids, int npoint, const orbg_pose *poses,
+                       const double *points, int loop_kf, orbg_frustum_camera *d_cams_out,
+                       int32_t *out);
+/* The map update of RunGlobalBundleAdjustment (LoopClosing.cc:1056-1116).  origins [norigins]:
+ * mvpKeyFrameOrigins as slots.
+ *   keyframes  The walk visits every slot reachable from an origin over the children lists (the
+ *              slots whose parents lead to an origin).  It does not look at ORBG_MAP_KF_BAD, as
+ *              the reference does not; a dead slot ends it.  A visited child whose
+ *              mnBAGlobalForKF != loop_kf gets mTcwGBA = (Tcw_child * Twc_parent) * mTcwGBA_parent
+ *              and mnBAGlobalForKF = loop_kf: both products the 4x4 float cv::Mat product (each
+ *              entry's terms summed in double over k in order, rounded once to float; the
+ *              intermediate is a float matrix), Twc_parent = [Rcw^T | Ow] with the stored Ow, both
+ *              poses the ones from before this call.  Every visited keyframe then gets
+ *              mTcwBefGBA = Tcw, SetPose(mTcwGBA) and its Tcw in d_cams_out (may be NULL).  The
+ *              result does not depend on the order in which the slots are handled.
+ *   points     every good point: mnBAGlobalForKF == loop_kf: position = mPosGBA.  Otherwise, when
+ *              its reference keyframe was visited: orbg_gba_correct_points_device's move with that
+ *              keyframe's mTcwBefGBA and its GetPoseInverse() after the walk.  Otherwise it stays.
+ *              No UpdateNormalAndDepth: the reference runs none here.
+ *   departure  a point whose reference keyframe is -1, is dead, or carries loop_kf but was not
+ *              visited in this call stays where it is and is counted; the reference dereferences
+ *              a null pointer or reads a stale mTcwBefGBA there.
+ * d_out [6]: keyframes visited, of them propagated, points set from mPosGBA, points moved, points
+ * skipped by the departure, 0.  d_status [4]: [0] = ORBG_GBA_* bits; when one is set nothing is
+ * written.  ORBG_GBA_ORIGIN: an origin is no slot, is dead, has no pose or has
+ * mnBAGlobalForKF != loop_kf.  ORBG_GBA_CYCLE: the parents of live slots form a cycle (a walk of
+ * more than max_keyframes steps).  ORBG_GBA_NO_POSE: a visited keyframe has no pose.  The host form
+ * returns ORBG_EINVAL for any of them and for loop_kf == 0 (both forms). */
+#define ORBG_GBA_ORIGIN 1
+#define ORBG_GBA_CYCLE 2
+#define ORBG_GBA_NO_POSE 4
+int orbg_map_gba_update_device(orbg_ctx *ctx, orbg_map *map, const int32_t *d_origins, int norigins,
+                               int loop_kf, orbg_frustum_camera *d_cams_out, int32_t *d_out,
+                               int32_t *d_status);
+int orbg_map_gba_update(orbg_ctx *ctx, orbg_map *map, const int32_t *origins, int norigins,
+                        int loop_kf, orbg_frustum_camera *d_cams_out, int32_t *out);
+/* Optimizer::GlobalBundleAdjustemnt(pMap, iterations, control->force_stop, loop_kf, robust): the
+ * window, orbg_global_ba_optimize's optimisation on the window's device arrays (the estimates
+ * never reach the host; the edge records and the fixed flags are read once for
+ * orbg_ba_graph_create and the sparse plan), the store.  The workspace belongs to the map and
+ * grows on demand.  An empty edge set optimises nothing and stores nothing.  ORBG_ENOTSUP of the
+ * plan is returned with the Map untouched.  The store runs whether or not force_stop was raised,
+ * as in the reference.  control may be NULL.  Synchronises. */
+typedef struct {
+    orbg_gba_report gba;
+    int32_t nposes, npoints, nedges, nleft_out; /* the window's counts */
+    int32_t store[2];                           /* orbg_map_gba_store's d_out */
+    int32_t update[6];                          /* orbg_map_gba_update's d_out */
+    int32_t stopped, pad;
+} orbg_map_gba_report;
+int orbg_map_global_ba(orbg_ctx *ctx, orbg_map *map, int iterations, int robust, int loop_kf,
+                       const orbg_lm_control *control, orbg_frustum_camera *d_cams_out,
+                       orbg_map_gba_report *report);
+/* LoopClosing::RunGlobalBundleAdjustment(loop_kf): orbg_map_global_ba with 10 iterations, not
+ * robust, then the update unless *control->force_stop != 0 (:1040): then stopped = 1 and poses
+ * and positions are untouched (the GBA state is stored).  ORBG_EINVAL for loop_kf == 0 and for
+ * the update's status bits. */
+int orbg_map_run_global_ba(orbg_ctx *ctx, orbg_map *map, const int32_t *origins, int norigins,
+                           int loop_kf, const orbg_lm_control *control,
+                           orbg_frustum_camera *d_cams_out, orbg_map_gba_report *report);
+
 /* ---------------- Initializer (Tracking::MonocularInitialization) ----------------
  * src/Initializer.cc:73-187 and everything below it, batched over frame pairs:
  * Initializer::Initialize(CurrentFrame, vMatches12, R21, t21, vP3D, vbTriangulated) with

@@ -189,6 +189,16 @@ class MapLbaReport(C.Structure):
 LBA_NO_POSE, LBA_RANGE, LBA_DEAD, LBA_FEATURE = 1, 2, 4, 8   # ORBG_LBA_*
 
 
+class MapGbaReport(C.Structure):
+    """orbg_map_gba_report (include/orbg.h)."""
+    _fields_ = [("gba", GbaReport), ("nposes", C.c_int32), ("npoints", C.c_int32),
+                ("nedges", C.c_int32), ("nleft_out", C.c_int32), ("store", C.c_int32 * 2),
+                ("update", C.c_int32 * 6), ("stopped", C.c_int32), ("pad", C.c_int32)]
+
+
+GBA_ORIGIN, GBA_CYCLE, GBA_NO_POSE = 1, 2, 4                  # ORBG_GBA_*
+
+
 class KeyFrames(C.Structure):
     """orbg_keyframes (include/orbg.h): a set of KeyFrames in device memory."""
     _fields_ = [("desc", C.c_void_p), ("kps", C.c_void_p), ("uright", C.c_void_p),
@@ -542,6 +552,17 @@ def lib():
                                             vp]),
         "orbg_map_lba_apply": (i32, [vp, vp, vp, i32, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
         "orbg_map_local_ba": (i32, [vp, vp, i32, P(LmControl), vp, P(MapLbaReport)]),
+        "orbg_map_set_gba_state": (i32, [vp, vp, i32, i32, vp, vp, vp, i32, i32, vp, vp]),
+        "orbg_map_get_gba_state": (i32, [vp, vp, i32, i32, vp, vp, vp, i32, i32, vp, vp]),
+        "orbg_map_get_keyframe_flags": (i32, [vp, vp, i32, i32, vp]),
+        "orbg_map_gba_window_device": (i32, [vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp]),
+        "orbg_map_gba_window": (i32, [vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp]),
+        "orbg_map_gba_store_device": (i32, [vp, vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp]),
+        "orbg_map_gba_store": (i32, [vp, vp, vp, i32, vp, i32, vp, vp, i32, vp, vp]),
+        "orbg_map_gba_update_device": (i32, [vp, vp, vp, i32, i32, vp, vp, vp]),
+        "orbg_map_gba_update": (i32, [vp, vp, vp, i32, i32, vp, vp]),
+        "orbg_map_global_ba": (i32, [vp, vp, i32, i32, i32, P(LmControl), vp, P(MapGbaReport)]),
+        "orbg_map_run_global_ba": (i32, [vp, vp, vp, i32, i32, P(LmControl), vp, P(MapGbaReport)]),
         "orbg_map_attach_keyframe_geometry": (i32, [vp, vp, vp, vp, vp]),
         "orbg_map_create_new_points_device": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp,
                                                     vp, vp, vp, vp, vp]),

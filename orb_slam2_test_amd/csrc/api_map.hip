@@ -39,6 +39,13 @@ struct orbg_map {
     std::vector<orbg_edge> lb_edges;           // its edge records, fixed flags and vToErase on the host
     std::vector<int32_t> lb_fixed;
     std::vector<uint8_t> lb_fixed8, lb_erase;
+    MapGbaWs GW{};               // GlobalBundleAdjustment's marks (sized by K and P), allocated at the first call
+    void *d_gw = nullptr;
+    MapLbaWindow GB{};           // orbg_map_global_ba's window, its edges grown on demand
+    void *d_gb = nullptr;
+    std::vector<orbg_edge> gb_edges;           // its edge records and fixed flags on the host
+    std::vector<int32_t> gb_fixed;
+    std::vector<uint8_t> gb_fixed8;
 };
 
 static int map_reset(orbg_map *m, hipStream_t st)
@@ -97,6 +104,8 @@ extern "C" int orbg_map_create(orbg_ctx *c, int max_keyframes, int kf_cap, int m
     const size_t o_lt = L.take(K * 48), o_lc = L.take(K * 12), o_lp = L.take(K * 4);
     const size_t o_lh = L.take(64), o_sn = L.take(K * 2);
     const size_t o_cs2 = L.take(P * 4), o_vm = L.take(K * 4), o_ec2 = L.take((K + 1) * 4);
+    const size_t o_gt = L.take(K * 48), o_gb = L.take(K * 48), o_gk = L.take(K * 4);
+    const size_t o_gp = L.take(P * 12), o_gq = L.take(P * 4);
     auto *m = new orbg_map();
     m->device = c->device;
     if (hipMalloc(&m->d_mem, L.total()) != hipSuccess) {
@@ -166,6 +175,11 @@ extern "C" int orbg_map_create(orbg_ctx *c, int max_keyframes, int kf_cap, int m
     D.mp_corr_slot = L.at<int32_t>(b, o_cs2);
     D.lp_vmap = L.at<int32_t>(b, o_vm);
     D.lp_ecnt = L.at<int32_t>(b, o_ec2);
+    D.kf_TcwGBA = L.at<float>(b, o_gt);
+    D.kf_TcwBef = L.at<float>(b, o_gb);
+    D.kf_gba = L.at<int32_t>(b, o_gk);
+    D.mp_posGBA = L.at<float>(b, o_gp);
+    D.mp_gba = L.at<int32_t>(b, o_gq);
     int rc = map_reset(m, c->stream);
     if (!rc && hipStreamSynchronize(c->stream) != hipSuccess)
         rc = set_err(ORBG_EIO, "Map: the initial clear failed");
@@ -190,6 +204,8 @@ extern "C" void orbg_map_destroy(orbg_map *m)
     if (m->d_lw) hipFree(m->d_lw);
     if (m->d_lb) hipFree(m->d_lb);
     if (m->d_cw) hipFree(m->d_cw);
+    if (m->d_gw) hipFree(m->d_gw);
+    if (m->d_gb) hipFree(m->d_gb);
     if (m->d_mem) hipFree(m->d_mem);
     delete m;
 }
@@ -2542,5 +2558,434 @@ extern "C" int orbg_map_local_ba(orbg_ctx *c, orbg_map *m, int slot, const orbg_
     c->prof.collect();
     report->nerased = o2[0];
     report->npoints_bad = o2[1];
+    return ORBG_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Optimizer::GlobalBundleAdjustemnt and LoopClosing::RunGlobalBundleAdjustment on the Map
+// (map_gba_kernels.hip)
+// ---------------------------------------------------------------------------
+extern "C" int orbg_map_set_gba_state(orbg_ctx *c, orbg_map *m, int first_slot, int nslots,
+                                      const float *TcwGBA, const float *TcwBefGBA,
+                                      const int32_t *kf_ba_global, int first_point, int npoints,
+                                      const float *PosGBA, const int32_t *mp_ba_global)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (nslots < 0 || first_slot < 0 || (int64_t)first_slot + nslots > m->D.K)
+        return set_err(ORBG_EINVAL, "slots %d .. %lld outside [0, %d)", first_slot,
+                       (long long)first_slot + nslots, m->D.K);
+    if ((rc = map_range_ok(m, first_point, npoints))) return rc;
+    const MapDev &D = m->D;
+    hipStream_t st = c->stream;
+    const size_t s0 = (size_t)first_slot, ns = (size_t)nslots, p0 = (size_t)first_point, np = (size_t)npoints;
+    if (ns && TcwGBA) HIPCHK(hipMemcpyAsync(D.kf_TcwGBA + s0 * 12, TcwGBA, ns * 48, hipMemcpyHostToDevice, st));
+    if (ns && TcwBefGBA) HIPCHK(hipMemcpyAsync(D.kf_TcwBef + s0 * 12, TcwBefGBA, ns * 48, hipMemcpyHostToDevice, st));
+    if (ns && kf_ba_global) HIPCHK(hipMemcpyAsync(D.kf_gba + s0, kf_ba_global, ns * 4, hipMemcpyHostToDevice, st));
+    if (np && PosGBA) HIPCHK(hipMemcpyAsync(D.mp_posGBA + p0 * 3, PosGBA, np * 12, hipMemcpyHostToDevice, st));
+    if (np && mp_ba_global) HIPCHK(hipMemcpyAsync(D.mp_gba + p0, mp_ba_global, np * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    m->touched = true;
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_get_gba_state(orbg_ctx *c, orbg_map *m, int first_slot, int nslots,
+                                      float *TcwGBA, float *TcwBefGBA, int32_t *kf_ba_global,
+                                      int first_point, int npoints, float *PosGBA,
+                                      int32_t *mp_ba_global)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (nslots < 0 || first_slot < 0 || (int64_t)first_slot + nslots > m->D.K)
+        return set_err(ORBG_EINVAL, "slots %d .. %lld outside [0, %d)", first_slot,
+                       (long long)first_slot + nslots, m->D.K);
+    if ((rc = map_range_ok(m, first_point, npoints))) return rc;
+    const MapDev &D = m->D;
+    hipStream_t st = c->stream;
+    const size_t s0 = (size_t)first_slot, ns = (size_t)nslots, p0 = (size_t)first_point, np = (size_t)npoints;
+    if (ns && TcwGBA) HIPCHK(hipMemcpyAsync(TcwGBA, D.kf_TcwGBA + s0 * 12, ns * 48, hipMemcpyDeviceToHost, st));
+    if (ns && TcwBefGBA) HIPCHK(hipMemcpyAsync(TcwBefGBA, D.kf_TcwBef + s0 * 12, ns * 48, hipMemcpyDeviceToHost, st));
+    if (ns && kf_ba_global) HIPCHK(hipMemcpyAsync(kf_ba_global, D.kf_gba + s0, ns * 4, hipMemcpyDeviceToHost, st));
+    if (np && PosGBA) HIPCHK(hipMemcpyAsync(PosGBA, D.mp_posGBA + p0 * 3, np * 12, hipMemcpyDeviceToHost, st));
+    if (np && mp_ba_global) HIPCHK(hipMemcpyAsync(mp_ba_global, D.mp_gba + p0, np * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_get_keyframe_flags(orbg_ctx *c, orbg_map *m, int first, int n, int32_t *flags)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (n < 0 || first < 0 || (int64_t)first + n > m->D.K)
+        return set_err(ORBG_EINVAL, "slots %d .. %lld outside [0, %d)", first, (long long)first + n, m->D.K);
+    if (n == 0) return ORBG_OK;
+    if (!flags) return set_err(ORBG_EINVAL, "NULL array");
+    HIPCHK(hipMemcpyAsync(flags, m->D.kf_flags + first, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return ORBG_OK;
+}
+
+// the marks of a window, a store or an update: sized by K and P, allocated once
+static int map_gba_ws(orbg_ctx *c, orbg_map *m)
+{
+    if (m->d_gw) return ORBG_OK;
+    const size_t K = (size_t)m->D.K, P = (size_t)m->D.P;
+    Layout L;
+    const size_t o_h = L.take(16 * 4), o_x = L.take(K * 4), o_f = L.take(K * 4), o_n = L.take(P * 4);
+    const size_t o_p = L.take(P * 4), o_e = L.take(P * 4), o_i = L.take(P * 4), o_o = L.take(K * 4);
+    const size_t o_v = L.take(K * 4), o_g = L.take(K * 48);
+    if (hipMalloc(&m->d_gw, L.total()) != hipSuccess) {
+        m->d_gw = nullptr;
+        return set_err(ORBG_ENOMEM, "Map: hipMalloc(%zu bytes) for the global BA marks", L.total());
+    }
+    HIPCHK(hipMemsetAsync(m->d_gw, 0, L.total(), c->stream));
+    uint8_t *b = (uint8_t *)m->d_gw;
+    MapGbaWs &W = m->GW;
+    W.hdr = L.at<int32_t>(b, o_h);
+    W.pidx = L.at<int32_t>(b, o_x);
+    W.fixed = L.at<int32_t>(b, o_f);
+    W.ne = L.at<int32_t>(b, o_n);
+    W.pi = L.at<int32_t>(b, o_p);
+    W.eoff = L.at<int32_t>(b, o_e);
+    W.ids = L.at<int32_t>(b, o_i);
+    W.org = L.at<int32_t>(b, o_o);
+    W.vis = L.at<int32_t>(b, o_v);
+    W.gT = L.at<float>(b, o_g);
+    return ORBG_OK;
+}
+
+static int map_gba_window_status(int bits, const int32_t *cnt, int pose_cap, int point_cap, int edge_cap)
+{
+    if (bits & ORBG_LBA_NO_POSE) return set_err(ORBG_EINVAL, "GlobalBundleAdjustment: a keyframe that is not bad has no pose");
+    if (bits & ORBG_LBA_RANGE)
+        return set_err(ORBG_ERANGE, "GlobalBundleAdjustment: %d poses, %d points, %d edges (caps %d, %d, %d)",
+                       cnt[0], cnt[1], cnt[2], pose_cap, point_cap, edge_cap);
+    if (bits & ORBG_LBA_FEATURE)
+        return set_err(ORBG_EINVAL, "GlobalBundleAdjustment: an observation's feature index is past the attached count");
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_gba_window_device(orbg_ctx *c, orbg_map *m, int robust, int32_t *d_kf_slots,
+                                          orbg_pose *d_poses, int pose_cap, int32_t *d_point_ids,
+                                          double *d_points, int point_cap, orbg_edge *d_edges,
+                                          int32_t *d_edge_feat, int edge_cap, int32_t *d_counts,
+                                          int32_t *d_status)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (pose_cap < 0 || point_cap < 0 || edge_cap < 0) return set_err(ORBG_EINVAL, "negative cap");
+    if ((pose_cap && (!d_kf_slots || !d_poses)) || (point_cap && (!d_point_ids || !d_points)) ||
+        (edge_cap && (!d_edges || !d_edge_feat)) || !d_counts || !d_status)
+        return set_err(ORBG_EINVAL, "NULL device array");
+    if ((rc = map_attached(m))) return rc;
+    if ((rc = map_gba_ws(c, m))) return rc;
+    if ((rc = orbg_map_rebuild(c, m))) return rc;
+    MapLbaWindow O{};
+    O.kf_slots = d_kf_slots;
+    O.poses = d_poses;
+    O.point_ids = d_point_ids;
+    O.points = d_points;
+    O.edges = d_edges;
+    O.edge_feat = d_edge_feat;
+    O.pose_cap = pose_cap;
+    O.point_cap = point_cap;
+    O.edge_cap = edge_cap;
+    O.counts = d_counts;
+    MapLbaConst C{};
+    for (int i = 0; i < 16; i++) C.inv_sigma2[i] = c->inv_sigma2[i];
+    const float hm = std::sqrt(5.99), hs = std::sqrt(7.815);  // float in the reference (Optimizer.cc:157-158)
+    C.huber_mono = hm;
+    C.huber_stereo = hs;
+    if ((rc = launch_map_gba_window(c->stream, m->D, m->att, m->GW, robust ? 1 : 0, O, C, d_status, &c->prof)))
+        return set_err(rc, "k_gba window launch failed");
+    m->touched = true;
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_gba_window(orbg_ctx *c, orbg_map *m, int robust, int32_t *kf_slots,
+                                   orbg_pose *poses, int pose_cap, int32_t *point_ids, double *points,
+                                   int point_cap, orbg_edge *edges, int32_t *edge_feat, int edge_cap,
+                                   int32_t *counts)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (pose_cap < 0 || point_cap < 0 || edge_cap < 0) return set_err(ORBG_EINVAL, "negative cap");
+    if ((pose_cap && (!kf_slots || !poses)) || (point_cap && (!point_ids || !points)) ||
+        (edge_cap && (!edges || !edge_feat)) || !counts)
+        return set_err(ORBG_EINVAL, "NULL array");
+    const size_t np = (size_t)pose_cap, nq = (size_t)point_cap, ne = (size_t)edge_cap;
+    Layout L;
+    const size_t o_k = L.take(np * 4), o_p = L.take(np * sizeof(orbg_pose)), o_i = L.take(nq * 4);
+    const size_t o_x = L.take(nq * 24), o_e = L.take(ne * sizeof(orbg_edge)), o_f = L.take(ne * 4);
+    const size_t o_h = L.take(32);  // counts [4], status [4]
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
+    int32_t *h = L.at<int32_t>(b, o_h);
+    HIPCHK(hipMemsetAsync(h, 0, 32, c->stream));
+    if ((rc = orbg_map_gba_window_device(c, m, robust, L.at<int32_t>(b, o_k), L.at<orbg_pose>(b, o_p),
+                                         pose_cap, L.at<int32_t>(b, o_i), L.at<double>(b, o_x),
+                                         point_cap, L.at<orbg_edge>(b, o_e), L.at<int32_t>(b, o_f),
+                                         edge_cap, h, h + 4)))
+        return rc;
+    int32_t out[8];
+    HIPCHK(hipMemcpyAsync(out, h, 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->prof.collect();
+    for (int i = 0; i < 4; i++) counts[i] = out[i];
+    if ((rc = map_gba_window_status(out[4], out, pose_cap, point_cap, edge_cap))) return rc;
+    if (out[0]) {
+        HIPCHK(hipMemcpy(kf_slots, b + o_k, (size_t)out[0] * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(poses, b + o_p, (size_t)out[0] * sizeof(orbg_pose), hipMemcpyDeviceToHost));
+    }
+    if (out[1]) {
+        HIPCHK(hipMemcpy(point_ids, b + o_i, (size_t)out[1] * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(points, b + o_x, (size_t)out[1] * 24, hipMemcpyDeviceToHost));
+    }
+    if (out[2]) {
+        HIPCHK(hipMemcpy(edges, b + o_e, (size_t)out[2] * sizeof(orbg_edge), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(edge_feat, b + o_f, (size_t)out[2] * 4, hipMemcpyDeviceToHost));
+    }
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_gba_store_device(orbg_ctx *c, orbg_map *m, const int32_t *d_kf_slots,
+                                         int pose_cap, const int32_t *d_point_ids, int point_cap,
+                                         const int32_t *d_counts, const orbg_pose *d_poses,
+                                         const double *d_points, int loop_kf,
+                                         orbg_frustum_camera *d_cams_out, int32_t *d_out)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (pose_cap < 0 || point_cap < 0) return set_err(ORBG_EINVAL, "negative cap");
+    if ((pose_cap && (!d_kf_slots || !d_poses)) || (point_cap && (!d_point_ids || !d_points)) ||
+        !d_counts || !d_out)
+        return set_err(ORBG_EINVAL, "NULL device array");
+    if ((rc = map_gba_ws(c, m))) return rc;
+    HIPCHK(hipMemsetAsync(d_out, 0, 8, c->stream));
+    if ((rc = launch_map_gba_store(c->stream, m->D, m->GW, d_counts, d_kf_slots, pose_cap, d_point_ids,
+                                   point_cap, d_poses, d_points, loop_kf, d_cams_out, d_out, &c->prof)))
+        return set_err(rc, "k_gba_store launch failed");
+    m->touched = true;
+    const int n = std::min(point_cap, m->D.P);
+    if (loop_kf != 0 || n == 0) return ORBG_OK;
+    return orbg_map_update_normal_and_depth_batch_device(c, m, m->GW.ids, n);
+}
+
+extern "C" int orbg_map_gba_store(orbg_ctx *c, orbg_map *m, const int32_t *kf_slots, int npose,
+                                  const int32_t *point_ids, int npoint, const orbg_pose *poses,
+                                  const double *points, int loop_kf, orbg_frustum_camera *d_cams_out,
+                                  int32_t *out)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (npose < 0 || npose > m->D.K || npoint < 0 || npoint > m->D.P)
+        return set_err(ORBG_EINVAL, "npose %d / npoint %d outside [0, %d] / [0, %d]", npose, npoint, m->D.K, m->D.P);
+    if ((npose && (!kf_slots || !poses)) || (npoint && (!point_ids || !points)))
+        return set_err(ORBG_EINVAL, "NULL array");
+    for (int i = 0; i < npose; i++)
+        if ((rc = map_slot_ok(m, kf_slots[i]))) return rc;
+    for (int i = 0; i < npoint; i++)
+        if (point_ids[i] < 0 || point_ids[i] >= m->D.P)
+            return set_err(ORBG_EINVAL, "point id %d outside [0, %d)", point_ids[i], m->D.P);
+    const size_t np = (size_t)npose, nq = (size_t)npoint;
+    Layout L;
+    const size_t o_k = L.take(np * 4), o_p = L.take(np * sizeof(orbg_pose)), o_i = L.take(nq * 4);
+    const size_t o_x = L.take(nq * 24), o_h = L.take(32);  // counts [4], out [2]
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
+    const int32_t hdr[8] = {npose, npoint, 0, 0, 0, 0, 0, 0};
+    hipStream_t st = c->stream;
+    if (np) {
+        HIPCHK(hipMemcpyAsync(b + o_k, kf_slots, np * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(b + o_p, poses, np * sizeof(orbg_pose), hipMemcpyHostToDevice, st));
+    }
+    if (nq) {
+        HIPCHK(hipMemcpyAsync(b + o_i, point_ids, nq * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(b + o_x, points, nq * 24, hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(hipMemcpyAsync(b + o_h, hdr, 32, hipMemcpyHostToDevice, st));
+    int32_t *h = L.at<int32_t>(b, o_h);
+    if ((rc = orbg_map_gba_store_device(c, m, L.at<int32_t>(b, o_k), npose, L.at<int32_t>(b, o_i), npoint,
+                                        h, L.at<orbg_pose>(b, o_p), L.at<double>(b, o_x), loop_kf,
+                                        d_cams_out, h + 4)))
+        return rc;
+    int32_t o2[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(o2, h + 4, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    c->prof.collect();
+    if (out) {
+        out[0] = o2[0];
+        out[1] = o2[1];
+    }
+    return ORBG_OK;
+}
+
+static int map_gba_update_status(int bits)
+{
+    if (bits & ORBG_GBA_ORIGIN)
+        return set_err(ORBG_EINVAL, "RunGlobalBundleAdjustment: an origin is dead, has no pose or was not in the global BA");
+    if (bits & ORBG_GBA_CYCLE) return set_err(ORBG_EINVAL, "RunGlobalBundleAdjustment: the parents form a cycle");
+    if (bits & ORBG_GBA_NO_POSE) return set_err(ORBG_EINVAL, "RunGlobalBundleAdjustment: a visited keyframe has no pose");
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_gba_update_device(orbg_ctx *c, orbg_map *m, const int32_t *d_origins,
+                                          int norigins, int loop_kf, orbg_frustum_camera *d_cams_out,
+                                          int32_t *d_out, int32_t *d_status)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (norigins < 0) return set_err(ORBG_EINVAL, "negative size");
+    if (loop_kf == 0) return set_err(ORBG_EINVAL, "loop_kf is 0");
+    if ((norigins && !d_origins) || !d_out || !d_status) return set_err(ORBG_EINVAL, "NULL device array");
+    if ((rc = map_gba_ws(c, m))) return rc;
+    HIPCHK(hipMemsetAsync(d_out, 0, 24, c->stream));
+    HIPCHK(hipMemsetAsync(d_status, 0, 16, c->stream));
+    if ((rc = launch_map_gba_update(c->stream, m->D, m->GW, d_origins, norigins, loop_kf, d_cams_out,
+                                    d_out, d_status, &c->prof)))
+        return set_err(rc, "k_gba update launch failed");
+    m->touched = true;
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_gba_update(orbg_ctx *c, orbg_map *m, const int32_t *origins, int norigins,
+                                   int loop_kf, orbg_frustum_camera *d_cams_out, int32_t *out)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (norigins < 0) return set_err(ORBG_EINVAL, "negative size");
+    if (loop_kf == 0) return set_err(ORBG_EINVAL, "loop_kf is 0");
+    if (norigins && !origins) return set_err(ORBG_EINVAL, "NULL array");
+    for (int i = 0; i < norigins; i++)
+        if ((rc = map_slot_ok(m, origins[i]))) return rc;
+    Layout L;
+    const size_t o_o = L.take((size_t)norigins * 4), o_h = L.take(48);  // out [6], pad [2], status [4]
+    uint8_t *b;
+    if ((rc = L.device(c, &b))) return rc;
+    hipStream_t st = c->stream;
+    if (norigins) HIPCHK(hipMemcpyAsync(b + o_o, origins, (size_t)norigins * 4, hipMemcpyHostToDevice, st));
+    int32_t *h = L.at<int32_t>(b, o_h);
+    if ((rc = orbg_map_gba_update_device(c, m, L.at<int32_t>(b, o_o), norigins, loop_kf, d_cams_out, h, h + 8)))
+        return rc;
+    int32_t o[12] = {0};
+    HIPCHK(hipMemcpyAsync(o, h, 48, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    c->prof.collect();
+    if ((rc = map_gba_update_status(o[8]))) return rc;
+    if (out)
+        for (int i = 0; i < 6; i++) out[i] = o[i];
+    return ORBG_OK;
+}
+
+// orbg_map_global_ba's window arrays: poses and points by K and P, the edges grown to edge_cap
+static int map_gba_chain_ws(orbg_ctx *c, orbg_map *m, int edge_cap)
+{
+    MapLbaWindow &B = m->GB;
+    if (m->d_gb && edge_cap <= B.edge_cap) return ORBG_OK;
+    edge_cap = std::max(edge_cap, B.edge_cap);
+    if (m->d_gb) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipFree(m->d_gb));
+        m->d_gb = nullptr;
+        B = MapLbaWindow{};
+    }
+    const size_t np = (size_t)m->D.K, nq = (size_t)m->D.P, ne = (size_t)edge_cap;
+    Layout L;
+    const size_t o_k = L.take(np * 4), o_p = L.take(np * sizeof(orbg_pose)), o_i = L.take(nq * 4);
+    const size_t o_x = L.take(nq * 24), o_e = L.take(ne * sizeof(orbg_edge)), o_f = L.take(ne * 4);
+    const size_t o_h = L.take(64);  // counts [4], status [4], the store's out [2]
+    if (hipMalloc(&m->d_gb, L.total()) != hipSuccess) {
+        m->d_gb = nullptr;
+        return set_err(ORBG_ENOMEM, "Map: hipMalloc(%zu bytes) for the global BA window", L.total());
+    }
+    uint8_t *b = (uint8_t *)m->d_gb;
+    B.kf_slots = L.at<int32_t>(b, o_k);
+    B.poses = L.at<orbg_pose>(b, o_p);
+    B.point_ids = L.at<int32_t>(b, o_i);
+    B.points = L.at<double>(b, o_x);
+    B.edges = L.at<orbg_edge>(b, o_e);
+    B.edge_feat = L.at<int32_t>(b, o_f);
+    B.counts = L.at<int32_t>(b, o_h);
+    B.pose_cap = m->D.K;
+    B.point_cap = m->D.P;
+    B.edge_cap = edge_cap;
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_global_ba(orbg_ctx *c, orbg_map *m, int iterations, int robust, int loop_kf,
+                                  const orbg_lm_control *control, orbg_frustum_camera *d_cams_out,
+                                  orbg_map_gba_report *report)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (!report) return set_err(ORBG_EINVAL, "report is NULL");
+    if (iterations < 0) return set_err(ORBG_EINVAL, "negative iterations");
+    if ((rc = map_attached(m))) return rc;
+    *report = orbg_map_gba_report{};
+    const MapDev &D = m->D;
+    const int64_t rows = (int64_t)D.K * D.cap;
+    if (!m->d_gb && (rc = map_gba_chain_ws(c, m, (int)std::min<int64_t>(rows, 1 << 18)))) return rc;
+    hipStream_t st = c->stream;
+    int32_t h[8] = {0};
+    for (int pass = 0;; pass++) {
+        const MapLbaWindow &B = m->GB;
+        if ((rc = orbg_map_gba_window_device(c, m, robust, B.kf_slots, B.poses, B.pose_cap, B.point_ids,
+                                             B.points, B.point_cap, B.edges, B.edge_feat, B.edge_cap,
+                                             B.counts, B.counts + 4)))
+            return rc;
+        HIPCHK(hipMemcpyAsync(h, B.counts, 32, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (!(h[4] & ORBG_LBA_RANGE) || (h[4] & ORBG_LBA_NO_POSE) || pass) break;
+        if ((rc = map_gba_chain_ws(c, m, h[2]))) return rc;  // the poses and points always fit
+    }
+    const MapLbaWindow &B = m->GB;
+    if ((rc = map_gba_window_status(h[4], h, B.pose_cap, B.point_cap, B.edge_cap))) return rc;
+    report->nposes = h[0];
+    report->npoints = h[1];
+    report->nedges = h[2];
+    report->nleft_out = h[3];
+    const int npose = h[0], npoint = h[1], nedge = h[2];
+    if (nedge == 0) {  // initializeOptimization of an empty graph fails: nothing optimised or stored
+        c->prof.collect();
+        return ORBG_OK;
+    }
+    m->gb_edges.resize((size_t)nedge);
+    m->gb_fixed.resize((size_t)npose);
+    m->gb_fixed8.resize((size_t)npose);
+    HIPCHK(hipMemcpyAsync(m->gb_edges.data(), B.edges, (size_t)nedge * sizeof(orbg_edge), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(m->gb_fixed.data(), m->GW.fixed, (size_t)npose * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int i = 0; i < npose; i++) m->gb_fixed8[i] = m->gb_fixed[i] ? 1 : 0;
+    if ((rc = gba_optimize_device(c, B.poses, npose, B.points, npoint, m->gb_edges.data(), nedge,
+                                  m->gb_fixed8.data(), iterations, control, &report->gba)))
+        return rc;
+    if ((rc = orbg_map_gba_store_device(c, m, B.kf_slots, B.pose_cap, B.point_ids, B.point_cap, B.counts,
+                                        B.poses, B.points, loop_kf, d_cams_out, B.counts + 8)))
+        return rc;
+    HIPCHK(hipMemcpyAsync(report->store, B.counts + 8, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    c->prof.collect();
+    return ORBG_OK;
+}
+
+extern "C" int orbg_map_run_global_ba(orbg_ctx *c, orbg_map *m, const int32_t *origins, int norigins,
+                                      int loop_kf, const orbg_lm_control *control,
+                                      orbg_frustum_camera *d_cams_out, orbg_map_gba_report *report)
+{
+    int rc = map_enter(c, m);
+    if (rc) return rc;
+    if (!report) return set_err(ORBG_EINVAL, "report is NULL");
+    if (norigins < 0) return set_err(ORBG_EINVAL, "negative size");
+    if (loop_kf == 0) return set_err(ORBG_EINVAL, "loop_kf is 0");
+    if (norigins && !origins) return set_err(ORBG_EINVAL, "NULL array");
+    for (int i = 0; i < norigins; i++)
+        if ((rc = map_slot_ok(m, origins[i]))) return rc;
+    // Optimizer::GlobalBundleAdjustemnt(mpMap, 10, &mbStopGBA, nLoopKF, false); the cameras follow SetPose only
+    if ((rc = orbg_map_global_ba(c, m, 10, 0, loop_kf, control, nullptr, report))) return rc;
+    if (control && control->force_stop && *control->force_stop != 0) {  // LoopClosing.cc:1040
+        report->stopped = 1;
+        return ORBG_OK;
+    }
+    if ((rc = orbg_map_gba_update(c, m, origins, norigins, loop_kf, d_cams_out, report->update))) return rc;
     return ORBG_OK;
 }

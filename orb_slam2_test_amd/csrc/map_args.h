@@ -1,7 +1,7 @@
 // map_args.h -- device layout and launch arguments of the covisibility Map (map_kernels.hip:
 // KeyFrame::UpdateConnections, Tracking::UpdateLocalKeyFrames / UpdateLocalPoints,
 // MapPoint::UpdateNormalAndDepth; map_cull_kernels.hip; map_edit_kernels.hip;
-// map_loop_kernels.hip, map_lba_kernels.hip, map_create_kernels.hip), shared with the
+// map_loop_kernels.hip, map_lba_kernels.hip, map_gba_kernels.hip, map_create_kernels.hip), shared with the
 // host entry points (api_map.hip).
 #pragma once
 
@@ -88,6 +88,12 @@ struct MapDev {
     int32_t *mp_corr_slot;      // [P] the slot Propagate wrote mnCorrectedReference for (a hint: checked against kf_mnid)
     int32_t *lp_vmap;           // [K] essential graph: slot -> vertex, -1 = none
     int32_t *lp_ecnt;           // [K + 1] its kind-1 edges per vertex, then their offsets
+    // map_gba_kernels.hip: what global BA leaves for LoopClosing::RunGlobalBundleAdjustment
+    float *kf_TcwGBA;           // [K][12] mTcwGBA, 3x4 row-major
+    float *kf_TcwBef;           // [K][12] mTcwBefGBA
+    int32_t *kf_gba;            // [K] KeyFrame::mnBAGlobalForKF, 0 for a slot that becomes live
+    float *mp_posGBA;           // [P][3] mPosGBA
+    int32_t *mp_gba;            // [P] MapPoint::mnBAGlobalForKF, 0 for a created point
 };
 #define LOOP_HDR_SLOT 0               // the slot of the running UpdateConnections, -1 = none
 #define LOOP_HDR_NSET 1               // members the running call acts on
@@ -289,6 +295,40 @@ int launch_map_lba_window(hipStream_t st, const MapDev &M, const MapAttach &A, c
 int launch_map_lba_apply(hipStream_t st, const MapDev &M, const MapLbaWs &W, const MapLbaWindow &O,
                          const uint8_t *erase, orbg_frustum_camera *cams_out, int32_t *out,
                          Prof *prof);
+
+// map_gba_kernels.hip: Optimizer::GlobalBundleAdjustemnt's window and store (src/Optimizer.cc:
+// 113-320) and RunGlobalBundleAdjustment's map update (src/LoopClosing.cc:1056-1116).  The
+// map-owned marks of one call, sized by K and P alone:
+struct MapGbaWs {
+    int32_t *hdr;                     // [16] GBA_HDR_*
+    int32_t *pidx;                    // [K] slot -> pose index, -1 = no vertex
+    int32_t *fixed;                   // [K] pose index -> the vertex is fixed
+    int32_t *ne;                      // [P] edges of the point, 0 = not in the window
+    int32_t *pi;                      // [P] id -> window position, -1 = none
+    int32_t *eoff;                    // [P] id -> its first edge
+    int32_t *ids;                     // [P] Store: the points written, -1 elsewhere
+    int32_t *org;                     // [K] Update: 1 = an origin
+    int32_t *vis;                     // [K] Update: 0 not visited, else 1 + parents up to the nearest slot in the BA
+    float *gT;                        // [K][12] Update: the propagated mTcwGBA, staged
+};
+#define GBA_HDR_NPOSE 0
+#define GBA_HDR_NPOINT 1
+#define GBA_HDR_NEDGE 2
+#define GBA_HDR_LEFT 3                // good points without an edge (vbNotIncludedMP)
+#define GBA_HDR_BITS 4                // ORBG_LBA_*
+// O.counts [4]: npose, npoint, nedge, points left out; status [4]: [0] = ORBG_LBA_* bits
+int launch_map_gba_window(hipStream_t st, const MapDev &M, const MapAttach &A, const MapGbaWs &W,
+                          int robust, const MapLbaWindow &O, const MapLbaConst &C, int32_t *status,
+                          Prof *prof);
+// counts as the window left them; out [2] (zeroed by the caller): keyframes, points written
+int launch_map_gba_store(hipStream_t st, const MapDev &M, const MapGbaWs &W, const int32_t *counts,
+                         const int32_t *kf_slots, int pose_cap, const int32_t *point_ids,
+                         int point_cap, const orbg_pose *poses, const double *points, int loop_kf,
+                         orbg_frustum_camera *cams_out, int32_t *out, Prof *prof);
+// out [6] and status [4] zeroed by the caller; status [0] = ORBG_GBA_* bits
+int launch_map_gba_update(hipStream_t st, const MapDev &M, const MapGbaWs &W, const int32_t *origins,
+                          int norigins, int loop_kf, orbg_frustum_camera *cams_out, int32_t *out,
+                          int32_t *status, Prof *prof);
 
 // map_create_kernels.hip: LocalMapping::CreateNewMapPoints and ProcessNewKeyFrame on the table.
 // The attached geometry (orbg_map_attach_keyframe_geometry, not owned) and the map-owned

@@ -217,6 +217,7 @@ __global__ __launch_bounds__(MAP_T) void k_cnp_insert(MapDev M, MapCreateWs W, i
             M.mp_corr_kf[id] = 0;
             M.mp_corr_ref[id] = 0;
             M.mp_corr_slot[id] = 0;
+            M.mp_gba[id] = 0;
             M.kf_points[(size_t)slot * M.cap + k] = id;
             // two idx1 may hold the same idx2 (vbMatched2 is never set): the later one keeps it
             atomicMax(&M.kf_points[(size_t)nb * M.cap + j], id);

@@ -1,5 +1,6 @@
 // map_device.h -- what the Map's kernel files share (map_kernels.hip, map_cull_kernels.hip,
-// map_edit_kernels.hip, map_loop_kernels.hip, map_lba_kernels.hip, map_create_kernels.hip): the workgroup size, the sort-key layout, the workgroup scan, the LDS
+// map_edit_kernels.hip, map_loop_kernels.hip, map_lba_kernels.hip, map_gba_kernels.hip,
+// map_create_kernels.hip): the workgroup size, the sort-key layout, the workgroup scan, the LDS
 // bitonic sort, the store of an ordered list and the test of an entry of a stale observation
 // index.  Every kernel file that includes it has its own map_smem.
 #pragma once

@@ -76,6 +76,7 @@ __global__ __launch_bounds__(MAP_T) void k_map_set_kf(MapDev M, const int32_t *s
             M.parent[s] = -1;
             M.first_conn[s] = 1;
             M.kf_erase[s] = 0;
+            M.kf_gba[s] = 0;
         }
     }
 }

@@ -27,7 +27,8 @@
 //                  so the points are independent and the result is the sequential one.
 //   k_lba_write    SetPose of the local keyframes (Converter::toCvMat(SE3Quat)), the attached
 //                  cameras' Tcw, SetWorldPos of every window point.
-// UpdateNormalAndDepth is map_kernels.hip's, over a rebuilt observation index.
+// UpdateNormalAndDepth is map_kernels.hip's, over a rebuilt observation index.  The conversions and
+// the edge record are map_ba_device.h's, shared with map_gba_kernels.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,6 +38,7 @@
 #include "../../include/orbg.h"
 #include "map_args.h"
 #include "map_device.h"
+#include "map_ba_device.h"
 #include "orbg_launch.h"
 
 #pragma clang fp contract(off)
@@ -44,89 +46,6 @@
 namespace orbg {
 
 #define LBA_POS_MASK 0x7FFFFu
-
-__device__ __forceinline__ bool lba_kf_good(const MapDev &M, int s)
-{
-    return (M.kf_flags[s] & (MAP_KF_LIVE | ORBG_MAP_KF_BAD)) == MAP_KF_LIVE;
-}
-
-// Eigen's Quaterniond(Matrix3d) when the trace is not positive: I the largest diagonal entry
-template <int I>
-__device__ __forceinline__ void lba_quat_diag(const double (&R)[3][3], double (&q)[4])
-{
-    constexpr int J = (I + 1) % 3, K = (J + 1) % 3;
-    double s = sqrt(R[I][I] - R[J][J] - R[K][K] + 1.0);
-    q[I] = 0.5 * s;
-    s = 0.5 / s;
-    q[3] = (R[K][J] - R[J][K]) * s;
-    q[J] = (R[J][I] + R[I][J]) * s;
-    q[K] = (R[K][I] + R[I][K]) * s;
-}
-
-// Converter::toSE3Quat of a float 3x4 pose: Eigen's branch, w >= 0, one normalisation
-__device__ __forceinline__ void lba_se3quat(const float *T, int fixed, orbg_pose *o)
-{
-    double R[3][3], q[4];
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) R[i][j] = (double)T[4 * i + j];
-    const double tr = R[0][0] + R[1][1] + R[2][2];
-    if (tr > 0) {
-        double s = sqrt(tr + 1.0);
-        q[3] = 0.5 * s;
-        s = 0.5 / s;
-        q[0] = (R[2][1] - R[1][2]) * s;
-        q[1] = (R[0][2] - R[2][0]) * s;
-        q[2] = (R[1][0] - R[0][1]) * s;
-    } else {
-        int i = 0;
-        if (R[1][1] > R[0][0]) i = 1;
-        if (i == 0 ? R[2][2] > R[0][0] : R[2][2] > R[1][1]) i = 2;
-        if (i == 0)
-            lba_quat_diag<0>(R, q);
-        else if (i == 1)
-            lba_quat_diag<1>(R, q);
-        else
-            lba_quat_diag<2>(R, q);
-    }
-    if (q[3] < 0) {
-        q[0] = -q[0];
-        q[1] = -q[1];
-        q[2] = -q[2];
-        q[3] = -q[3];
-    }
-    const double nq = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    o->q[0] = q[0] / nq;
-    o->q[1] = q[1] / nq;
-    o->q[2] = q[2] / nq;
-    o->q[3] = q[3] / nq;
-    o->t[0] = (double)T[3];
-    o->t[1] = (double)T[7];
-    o->t[2] = (double)T[11];
-    o->fixed = fixed;
-    o->pad = 0;
-}
-
-// Converter::toCvMat(SE3Quat): Eigen's toRotationMatrix, every element cast to float
-__device__ __forceinline__ void lba_tcw(const orbg_pose &p, float *T)
-{
-    const double *q = p.q;
-    const double tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2];
-    const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
-    const double txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
-    const double tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
-    T[0] = (float)(1 - (tyy + tzz));
-    T[1] = (float)(txy - twz);
-    T[2] = (float)(txz + twy);
-    T[3] = (float)p.t[0];
-    T[4] = (float)(txy + twz);
-    T[5] = (float)(1 - (txx + tzz));
-    T[6] = (float)(tyz - twx);
-    T[7] = (float)p.t[1];
-    T[8] = (float)(txz - twy);
-    T[9] = (float)(tyz + twx);
-    T[10] = (float)(1 - (txx + tyy));
-    T[11] = (float)p.t[2];
-}
 
 // ---------------------------------------------------------------------------
 // the window
@@ -362,32 +281,7 @@ __global__ __launch_bounds__(MAP_T) void k_lba_edges(MapDev M, MapAttach A, MapL
         const int k = at++;
         if (k >= edge_cap) continue;
         orbg_edge E;
-        E.point = i;
-        E.pose = W.pidx[u];
-        E.stereo = 0;
-        E.robust = 1;
-        E.active = 1;
-        E.pad = 0;
-        E.obs[0] = E.obs[1] = E.obs[2] = 0.0;
-        E.inv_sigma2 = 0.0;
-        if (j < min(A.kfs.counts[u], A.cap)) {
-            const orbg_keypoint kp = A.kfs.kps[(size_t)u * A.cap + j];
-            const float ur = A.kfs.uright ? A.kfs.uright[(size_t)u * A.cap + j] : -1.0f;
-            E.stereo = ur < 0 ? 0 : 1;
-            E.obs[0] = (double)kp.x;
-            E.obs[1] = (double)kp.y;
-            E.obs[2] = E.stereo ? (double)ur : 0.0;
-            E.inv_sigma2 = (double)C.inv_sigma2[min(max(kp.octave, 0), 15)];
-        } else {
-            atomicOr(&status[0], ORBG_LBA_FEATURE);
-        }
-        const orbg_frustum_camera *cam = A.cams + u;
-        E.fx = (double)cam->fx;
-        E.fy = (double)cam->fy;
-        E.cx = (double)cam->cx;
-        E.cy = (double)cam->cy;
-        E.bf = (double)cam->bf;
-        E.huber_delta = E.stereo ? C.huber_stereo : C.huber_mono;
+        if (!lba_fill_edge(A, C, u, j, i, W.pidx[u], 1, &E)) atomicOr(&status[0], ORBG_LBA_FEATURE);
         edges[k] = E;
         edge_feat[k] = j;
     }

@@ -3718,6 +3718,33 @@ extern "C" int orbg_local_ba_optimize(orbg_ctx *c, orbg_pose *poses, int npose, 
     return ORBG_OK;
 }
 
+namespace orbg {
+// orbg_global_ba_optimize's body on device-resident estimates: the graph from the host edge
+// records, the sparse plan with fixed [npose] (host), optimize(iterations).  The estimates stay
+// where they are.
+int gba_optimize_device(orbg_ctx *c, orbg_pose *d_poses, int npose, double *d_points, int npoint,
+                        const orbg_edge *edges, int nedge, const uint8_t *fixed, int iterations,
+                        const orbg_lm_control *control, orbg_gba_report *rep)
+{
+    orbg_gba_report R{};
+    orbg_ba_graph *g = nullptr;
+    int rc = orbg_ba_graph_create(c, edges, nedge, npose, npoint, &g);
+    if (rc) return rc;
+    struct Guard {
+        orbg_ba_graph *g;
+        ~Guard()
+        {
+            if (g) orbg_ba_graph_destroy(g);
+        }
+    } guard{g};
+    if ((rc = orbg_ba_graph_schur_plan_sparse(c, g, fixed, &R.plan))) return rc;
+    if ((rc = orbg_ba_graph_optimize_ctl(c, g, d_poses, d_points, iterations, control, &R.lm)))
+        return rc;
+    if (rep) *rep = R;
+    return ORBG_OK;
+}
+}  // namespace orbg
+
 // Optimizer::BundleAdjustment's optimisation (Optimizer.cc:113-247) from host arrays: see
 // include/orbg.h
 extern "C" int orbg_global_ba_optimize(orbg_ctx *c, orbg_pose *poses, int npose, double *points,
@@ -3736,19 +3763,14 @@ extern "C" int orbg_global_ba_optimize(orbg_ctx *c, orbg_pose *poses, int npose,
         return ORBG_OK;
     }
     HIPCHK(hipSetDevice(c->device));
-    orbg_ba_graph *g = nullptr;
-    int rc = orbg_ba_graph_create(c, edges, nedge, npose, npoint, &g);
-    if (rc) return rc;
     uint8_t *dmem = nullptr;
     struct Guard {
-        orbg_ba_graph *g;
         uint8_t **m;
         ~Guard()
         {
             if (*m) hipFree(*m);
-            if (g) orbg_ba_graph_destroy(g);
         }
-    } guard{g, &dmem};
+    } guard{&dmem};
     const size_t np = (size_t)std::max(npose, 1), nq = (size_t)std::max(npoint, 1);
     const size_t o_q = al256(np * sizeof(orbg_pose));
     HIPCHK(hipMalloc((void **)&dmem, o_q + al256(nq * 24)));
@@ -3761,9 +3783,9 @@ extern "C" int orbg_global_ba_optimize(orbg_ctx *c, orbg_pose *poses, int npose,
         HIPCHK(hipMemcpyAsync(d_points, points, (size_t)npoint * 24, hipMemcpyHostToDevice, st));
     std::vector<uint8_t> fixed(np, 0);
     for (int i = 0; i < npose; i++) fixed[i] = poses[i].fixed ? 1 : 0;
-    if ((rc = orbg_ba_graph_schur_plan_sparse(c, g, fixed.data(), &R.plan))) return rc;
-    if ((rc = orbg_ba_graph_optimize_ctl(c, g, d_poses, d_points, iterations, control, &R.lm)))
-        return rc;
+    int rc = gba_optimize_device(c, d_poses, npose, d_points, npoint, edges, nedge, fixed.data(),
+                                 iterations, control, &R);
+    if (rc) return rc;
     if (npose)
         HIPCHK(hipMemcpyAsync(poses, d_poses, (size_t)npose * sizeof(orbg_pose), hipMemcpyDeviceToHost, st));
     if (npoint)

@@ -395,6 +395,11 @@ int lba_optimize_device(orbg_ctx *c, orbg_pose *d_poses, int npose, double *d_po
                         const orbg_lm_control *control,
                         int (*point_is_bad)(void *user, int point), void *user, uint8_t *erase,
                         orbg_lba_report *rep);
+// orbg_api.hip: orbg_global_ba_optimize's body on device-resident estimates (the graph, the
+// sparse plan with fixed [npose], optimize(iterations)); api_map.hip runs it on the Map's window
+int gba_optimize_device(orbg_ctx *c, orbg_pose *d_poses, int npose, double *d_points, int npoint,
+                        const orbg_edge *edges, int nedge, const uint8_t *fixed, int iterations,
+                        const orbg_lm_control *control, orbg_gba_report *rep);
 
 // Byte layout of the buffers of an entry point on host arrays: take() hands out the offsets
 // of 256-byte-aligned sub-buffers (an empty array still gets 256 bytes of its own, so it

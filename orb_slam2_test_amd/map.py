@@ -34,6 +34,9 @@ ascending slot (include/orbg.h).
     recent, _ = m.ProcessNewKeyFrame(slot, ids, octs, feats, Tcw, mnId, in_keyframe, recent)
     recent, report = m.CreateNewMapPoints(slot, mnId, monocular, first_id, recent)
     w = m.LbaWindow(slot); m.LbaApply(w, poses, points, erase)  # its two ends, one at a time
+    report = m.GlobalBundleAdjustment(20)                     # CreateInitialMapMonocular's call
+    report = m.RunGlobalBundleAdjustment(loop_kf, stop_flag=flag)   # LoopClosing.cc:1024-1128
+    w = m.GbaWindow(robust); m.GbaStore(w, poses, points, loop_kf); m.GbaUpdate(loop_kf)
 """
 import ctypes as C
 
@@ -803,6 +806,161 @@ class Map:
                    do_more=int(rep.lba.do_more), n_outliers=int(rep.lba.n_outliers),
                    n_erase=int(rep.lba.n_erase))
         return out
+
+    # ---- Optimizer::GlobalBundleAdjustemnt and RunGlobalBundleAdjustment on the table ----
+    def gba_state(self, first_slot=0, nslots=None, first_point=0, npoints=None):
+        """dict of mTcwGBA / mTcwBefGBA float32 [n, 3, 4] and kf_ba_global int32 [n] of the slot
+        range, mPosGBA float32 [m, 3] and mp_ba_global int32 [m] of the point range"""
+        ns = self.max_keyframes - first_slot if nslots is None else int(nslots)
+        npt = self.max_points - first_point if npoints is None else int(npoints)
+        out = dict(TcwGBA=np.zeros((ns, 3, 4), np.float32), TcwBefGBA=np.zeros((ns, 3, 4), np.float32),
+                   kf_ba_global=np.zeros(ns, np.int32), PosGBA=np.zeros((npt, 3), np.float32),
+                   mp_ba_global=np.zeros(npt, np.int32))
+        L.check(L.lib().orbg_map_get_gba_state(
+            self._c(), self._h, int(first_slot), ns, L.ptr(out["TcwGBA"]), L.ptr(out["TcwBefGBA"]),
+            L.ptr(out["kf_ba_global"]), int(first_point), npt, L.ptr(out["PosGBA"]),
+            L.ptr(out["mp_ba_global"])), "orbg_map_get_gba_state")
+        return out
+
+    def SetGbaState(self, first_slot=0, TcwGBA=None, TcwBefGBA=None, kf_ba_global=None,
+                    first_point=0, PosGBA=None, mp_ba_global=None):
+        """Uploads the global BA state of a map built from host objects; None leaves that array
+        as it is.  The slot arrays share one length, the point arrays another."""
+        T = None if TcwGBA is None else np.ascontiguousarray(TcwGBA, np.float32).reshape(-1, 12)
+        B = None if TcwBefGBA is None else np.ascontiguousarray(TcwBefGBA, np.float32).reshape(-1, 12)
+        k = None if kf_ba_global is None else _i32(kf_ba_global)
+        X = None if PosGBA is None else np.ascontiguousarray(PosGBA, np.float32).reshape(-1, 3)
+        q = None if mp_ba_global is None else _i32(mp_ba_global)
+        ns = {len(a) for a in (T, B, k) if a is not None}
+        npt = {len(a) for a in (X, q) if a is not None}
+        if len(ns) > 1 or len(npt) > 1:
+            raise ValueError("the state arrays differ in length")
+        L.check(L.lib().orbg_map_set_gba_state(
+            self._c(), self._h, int(first_slot), ns.pop() if ns else 0, L.ptr(T), L.ptr(B), L.ptr(k),
+            int(first_point), npt.pop() if npt else 0, L.ptr(X), L.ptr(q)), "orbg_map_set_gba_state")
+
+    def GbaWindow(self, robust, pose_cap=None, point_cap=None, edge_cap=None):
+        """The graph Optimizer::BundleAdjustment builds from every keyframe and map point
+        (Optimizer.cc:113-246) as a dict: kf_slots (live and not bad, ascending), poses POSE_DTYPE
+        (fixed iff mnId 0), point_ids (good, with an edge), points float64 [n, 3], edges
+        EDGE_DTYPE, edge_feat, left_out (good points without an edge).  The keyframe data must be
+        attached and the poses set."""
+        K = self.max_keyframes
+        pc = K if pose_cap is None else int(pose_cap)
+        qc = self.max_points if point_cap is None else int(point_cap)
+        ec = K * self.kf_cap if edge_cap is None else int(edge_cap)
+        ks, po = np.zeros(pc, np.int32), np.zeros(pc, L.POSE_DTYPE)
+        ids, pts = np.zeros(qc, np.int32), np.zeros((qc, 3), np.float64)
+        ed, ef = np.zeros(ec, L.EDGE_DTYPE), np.zeros(ec, np.int32)
+        cnt = np.zeros(4, np.int32)
+        rc = L.lib().orbg_map_gba_window(self._c(), self._h, int(bool(robust)), L.ptr(ks), L.ptr(po),
+                                         pc, L.ptr(ids), L.ptr(pts), qc, L.ptr(ed), L.ptr(ef), ec,
+                                         L.ptr(cnt))
+        self.gba_counts = cnt.tolist()      # the full counts, also after ORBG_ERANGE
+        L.check(rc, "orbg_map_gba_window")
+        npo, nq, ne, left = cnt.tolist()
+        return dict(kf_slots=ks[:npo], poses=po[:npo], point_ids=ids[:nq], points=pts[:nq],
+                    edges=ed[:ne], edge_feat=ef[:ne], left_out=left)
+
+    def gba_window_device(self, robust, d_kf_slots, d_poses, pose_cap, d_point_ids, d_points,
+                          point_cap, d_edges, d_edge_feat, edge_cap, d_counts, d_status, ctx=None):
+        L.check(L.lib().orbg_map_gba_window_device(
+            self._c(ctx), self._h, int(bool(robust)), d_kf_slots, d_poses, int(pose_cap), d_point_ids,
+            d_points, int(point_cap), d_edges, d_edge_feat, int(edge_cap), d_counts, d_status),
+            "orbg_map_gba_window_device")
+
+    def GbaStore(self, window, poses, points, loop_kf, d_cams_out=None):
+        """Optimizer.cc:273-318 for a window of GbaWindow.  loop_kf == 0: SetPose, SetWorldPos and
+        UpdateNormalAndDepth; otherwise mTcwGBA / mPosGBA and mnBAGlobalForKF = loop_kf.  Returns
+        (keyframes written, points written)."""
+        ks, ids = _i32(window["kf_slots"]), _i32(window["point_ids"])
+        po = np.ascontiguousarray(poses, L.POSE_DTYPE).reshape(-1)
+        pts = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+        if len(po) != len(ks) or len(pts) != len(ids):
+            raise ValueError("the window and the estimates differ in length")
+        out = np.zeros(2, np.int32)
+        L.check(L.lib().orbg_map_gba_store(self._c(), self._h, L.ptr(ks), len(ks), L.ptr(ids),
+                                           len(ids), L.ptr(po), L.ptr(pts), int(loop_kf), d_cams_out,
+                                           L.ptr(out)), "orbg_map_gba_store")
+        return int(out[0]), int(out[1])
+
+    def gba_store_device(self, d_kf_slots, pose_cap, d_point_ids, point_cap, d_counts, d_poses,
+                         d_points, loop_kf, d_cams_out, d_out, ctx=None):
+        L.check(L.lib().orbg_map_gba_store_device(
+            self._c(ctx), self._h, d_kf_slots, int(pose_cap), d_point_ids, int(point_cap), d_counts,
+            d_poses, d_points, int(loop_kf), d_cams_out, d_out), "orbg_map_gba_store_device")
+
+    def keyframe_flags(self, first=0, n=None):
+        """KF_ROOT | KF_BAD per slot, and 4 for a live slot"""
+        n = self.max_keyframes - first if n is None else int(n)
+        out = np.zeros(n, np.int32)
+        L.check(L.lib().orbg_map_get_keyframe_flags(self._c(), self._h, int(first), n, L.ptr(out)),
+                "orbg_map_get_keyframe_flags")
+        return out
+
+    def _origins(self, origins):
+        """mvpKeyFrameOrigins as slots; None: the live KF_ROOT slots"""
+        if origins is not None:
+            return _i32(origins)
+        f = self.keyframe_flags()
+        return _i32(np.nonzero((f & (4 | KF_ROOT)) == (4 | KF_ROOT))[0])
+
+    def GbaUpdate(self, loop_kf, origins=None, d_cams_out=None):
+        """The map update of LoopClosing::RunGlobalBundleAdjustment (LoopClosing.cc:1056-1116):
+        the spanning-tree propagation from the origins (mvpKeyFrameOrigins as slots) and the map
+        points.  Returns [visited, propagated, points from mPosGBA, points moved, points skipped,
+        0]."""
+        o = self._origins(origins)
+        out = np.zeros(6, np.int32)
+        L.check(L.lib().orbg_map_gba_update(self._c(), self._h, L.ptr(o), len(o), int(loop_kf),
+                                            d_cams_out, L.ptr(out)), "orbg_map_gba_update")
+        return out.tolist()
+
+    def gba_update_device(self, d_origins, norigins, loop_kf, d_cams_out, d_out, d_status, ctx=None):
+        L.check(L.lib().orbg_map_gba_update_device(
+            self._c(ctx), self._h, d_origins, int(norigins), int(loop_kf), d_cams_out, d_out,
+            d_status), "orbg_map_gba_update_device")
+
+    @staticmethod
+    def _gba_report(rep):
+        from .optimizer import _lm_report
+        out = {k: int(getattr(rep, k)) for k in ("nposes", "npoints", "nedges", "nleft_out", "stopped")}
+        out.update(lm=_lm_report(rep.gba.lm), store=list(rep.store), update=list(rep.update),
+                   plan={k: int(getattr(rep.gba.plan, k)) for k, _ in L.BaSparseInfo._fields_})
+        return out
+
+    def _lm_control(self, stop_flag, post_iteration):
+        from .optimizer import _stop_flag_address
+        ctl = L.LmControl()
+        ctl.force_stop = _stop_flag_address(stop_flag)
+        pi = L.LM_POST_ITERATION((lambda u, it: post_iteration(it)) if post_iteration else 0)
+        ctl.post_iteration = pi
+        return ctl, pi
+
+    def GlobalBundleAdjustment(self, iterations=5, stop_flag=None, loop_kf=0, robust=True,
+                               d_cams_out=None, post_iteration=None):
+        """Optimizer::GlobalBundleAdjustemnt(map, iterations, stop_flag, loop_kf, robust) in one
+        call: the window, optimize(iterations) on the device estimates, the store.  Returns the
+        report as a dict."""
+        rep = L.MapGbaReport()
+        ctl, keep = self._lm_control(stop_flag, post_iteration)
+        L.check(L.lib().orbg_map_global_ba(self._c(), self._h, int(iterations), int(bool(robust)),
+                                           int(loop_kf), C.byref(ctl), d_cams_out, C.byref(rep)),
+                "orbg_map_global_ba")
+        return self._gba_report(rep)
+
+    def RunGlobalBundleAdjustment(self, loop_kf, origins=None, stop_flag=None, d_cams_out=None,
+                                  post_iteration=None):
+        """LoopClosing::RunGlobalBundleAdjustment(loop_kf): global BA with 10 iterations, not
+        robust, then the map update unless the flag is up (stopped = 1: the GBA state is stored,
+        poses and positions are untouched)."""
+        o = self._origins(origins)
+        rep = L.MapGbaReport()
+        ctl, keep = self._lm_control(stop_flag, post_iteration)
+        L.check(L.lib().orbg_map_run_global_ba(self._c(), self._h, L.ptr(o), len(o), int(loop_kf),
+                                               C.byref(ctl), d_cams_out, C.byref(rep)),
+                "orbg_map_run_global_ba")
+        return self._gba_report(rep)
 
     # ---- LocalMapping::ProcessNewKeyFrame / CreateNewMapPoints on the table ----
     def AttachKeyFrameGeometry(self, d_kps_raw, d_depth, d_kf_cams):
